@@ -40,7 +40,8 @@ import torch.distributed as dist  # noqa: E402
 
 from caelo import synth  # noqa: E402
 import caelo  # noqa: E402
-caelo.configure_runtime()  # before the first device call: 8 hardware queues, so that the pipeline's fourth stream gets its own
+caelo.configure_runtime()  # before the first device call (the hardware-queue count is left to the caller: three pipeline streams by default)
+from caelo import _ffi  # noqa: E402
 from caelo import dist as cdist  # noqa: E402
 from caelo.engine import Engine, FrameBatch, FrameFeatures, ransac_draws  # noqa: E402
 
@@ -151,6 +152,8 @@ def bench_dense128(args, eng, world, rank, backend, dev):
         tmax = torch.tensor([dt], device=dev if backend == "nccl" else "cpu", dtype=torch.float64)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if args.dump_outputs and rank == 0 and K > 0:   # the last timed step: one frame
+        dump_outputs(args.dump_outputs, frame_outputs(ff.rows[None], ff.key_pixels[None], ff.n_key, ff.status[None])[0])
     if rank == 0:
         vmap = eng.voxmap(max(eng.max_points, big))
         eng.voxelize(pool[0], vmap)
@@ -261,6 +264,37 @@ def _pmc_busy():
     return None
 
 
+DUMP_LIMIT = 64 << 20   # bytes: --dump-outputs writes at most this much
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one .npy per array, float32 kept as is, every other type widened to float64 (exact for the integers here)"""
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float32 if np.asarray(v).dtype == np.float32 else np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    assert total <= DUMP_LIMIT, "--dump-outputs: %d bytes > %d" % (total, DUMP_LIMIT)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+    print("bench.py: %d arrays (%.2f MB) written to %s" % (len(arrays), total / 1e6, path), file=sys.stderr)
+
+
+def frame_outputs(rows, key_pixels, n_key, status):
+    """a caller's view of extracted frames [F, ...]: slots past a frame's key-point count are not part of the result (zeroed)"""
+    n_key = n_key.cpu().numpy().astype(np.int64)
+    valid = np.arange(rows.shape[1])[None, :] < n_key[:, None]
+    rows = rows.cpu().numpy()
+    return {"descriptors": np.where(valid[..., None], rows[:, :, 0:60], 0), "key_pts": np.where(valid[..., None], rows[:, :, 60:63], 0),
+            "key_pixels": np.where(valid[..., None], key_pixels.cpu().numpy(), 0), "n_key": n_key, "status": status.cpu().numpy()}, valid
+
+
+def pose_outputs(res, masks, pair_idx, valid):
+    """the pairs' results: poses (PoseResult fields), inlier masks and NN match indices of each frame's key points"""
+    out = {"pose_" + f: res[f] for f in res.dtype.names}
+    out["inlier_mask"] = np.where(valid, masks, 0)
+    out["pair_idx"] = np.where(valid, pair_idx.cpu().numpy(), 0)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -297,6 +331,9 @@ def main():
                          "gather, default) or each rank's last frame only (all that consecutive-pair matching needs)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: --steps batches per rank; strong: --steps batches in total, split over the ranks (one workload, 1/2/4/8 a curve)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned for its LAST step (rank 0's frames) as DIR/<name>.npy, "
+                         "float32 / float64: descriptors, key points, poses, inlier sets (the inputs are the same seeded scans in every run)")
     args = ap.parse_args()
     global CERTIFY
     CERTIFY = not args.no_certify
@@ -504,6 +541,16 @@ def main():
                 sc_.synchronize()
             print("staging block, 16 MB at element %d: %.1f GB/s" % (off, 4 * (1 << 24) / (time.perf_counter() - t_) / 1e9), file=sys.stderr)
         print("timed region: %.2f ms (run_with_uploads returned at %.2f, finish_ranks at %.2f) for %d frames  %s" % (1e3 * dt, 1e3 * t_ru, 1e3 * t_fr, K, {k_: (round(v_, 1) if isinstance(v_, float) else v_) for k_, v_ in pipe.last_upload_times.items()}), pipe.cert_stats(), file=sys.stderr)
+    if args.dump_outputs and rank == 0 and K >= B:
+        last = batch.view(K - B, B)          # the last timed step: one batch of B frames
+        arrays, valid = frame_outputs(last.rows, last.key_pixels, last.n_key, last.status)
+        if not args.extract_only:
+            if last.exact is not None:       # the certified results are delivered in host arrays
+                res, masks = last.exact[0], last.exact[1]
+            else:
+                res, masks = last.result.cpu().numpy().view(_ffi.POSE_DTYPE).reshape(B), last.inlier_mask.cpu().numpy()
+            arrays.update(pose_outputs(res, masks, last.pair_idx, valid))
+        dump_outputs(args.dump_outputs, arrays)
     host = pipe.stats()
     cert = pipe.cert_stats() if (CERTIFY and not args.extract_only) else None
     # sanity: every pose solved (not timed)
@@ -679,7 +726,7 @@ def main():
         streams_note = None
         if host["streams"] != 4:
             streams_note = ("%d pipeline streams instead of 4: GPU_MAX_HW_QUEUES was %r when HIP initialised (needs >= 8 before the first "
-                            "device call, caelo.configure_runtime()) or the runtime refused a stream" % (host["streams"], os.environ.get("GPU_MAX_HW_QUEUES")))
+                            "device call; the package leaves it to the caller) or the runtime refused a stream" % (host["streams"], os.environ.get("GPU_MAX_HW_QUEUES")))
             print("bench.py: " + streams_note, file=sys.stderr)
         # ---- secondary legs: other configs / scenes / shortcuts through the SAME pipeline object, after the timed region, never
         # part of `value` (one driver-written record carries them all)

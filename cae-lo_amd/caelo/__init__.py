@@ -11,28 +11,25 @@ Sub-modules are imported lazily so that the light ones (h5lite, synth) work with
 """
 import importlib
 import os
-import sys
 
 def configure_runtime(hw_queues=8):
-    """Opt in to the pipeline's fourth stream (voxel maps beside the key-point chain).
+    """Report whether the pipeline's fourth stream (voxel maps beside the key-point chain) has the hardware
+    queues it needs.
 
     ROCclr deals HIP streams onto GPU_MAX_HW_QUEUES hardware queues (default 4) and reads the variable once, when HIP
-    initialises at the first device call.  An entry point that owns its process (bench.py, run_sequence.py, the test
-    session) calls this BEFORE touching the GPU; a library user who imports caelo into a bigger application decides for
-    himself -- importing caelo never changes the environment.  Returns True when the variable is in effect for this
-    process (set here or by the user to >= hw_queues), False when HIP was already up (three streams then; the pipeline
-    reports what it runs with through caelo_pipeline_stats)."""
+    initialises at the first device call.  The fourth stream only pays with >= 8 queues; with the default the pipeline runs
+    three streams (same results, a few per cent less throughput).  The queue count is a setting of the device, which other
+    processes share, so the package never raises it: whoever runs the process sets it before the first device call.
+    Entry points that own their process (bench.py, run_sequence.py, the test session) still call this before touching the
+    GPU.  Returns True when the variable is in effect with >= hw_queues, False otherwise (the pipeline reports what it runs
+    with through caelo_pipeline_stats)."""
     cur = os.environ.get("GPU_MAX_HW_QUEUES")
-    if cur is not None:
-        try:
-            return int(cur.strip() or 0) >= hw_queues
-        except ValueError:   # the runtime reads it with atoi: a value it would take for 0 leaves the default of four queues
-            return False
-    torch_mod = sys.modules.get("torch")
-    if torch_mod is not None and torch_mod.cuda.is_initialized():
+    if cur is None:
         return False
-    os.environ["GPU_MAX_HW_QUEUES"] = str(hw_queues)
-    return True
+    try:
+        return int(cur.strip() or 0) >= hw_queues
+    except ValueError:   # the runtime reads it with atoi: a value it would take for 0 leaves the default of four queues
+        return False
 
 
 __all__ = ["api", "engine", "dist", "h5lite", "synth", "_ffi", "hostblas", "hostexact", "configure_runtime"]

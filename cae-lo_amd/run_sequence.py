@@ -28,7 +28,7 @@ import torch.distributed as dist  # noqa: E402
 
 from caelo import _ffi, stageio, synth  # noqa: E402
 import caelo  # noqa: E402
-caelo.configure_runtime()  # this script owns its process: ask for 8 hardware queues before HIP starts
+caelo.configure_runtime()  # this script owns its process: before HIP starts (the queue count is left to the caller)
 from caelo import dist as cdist  # noqa: E402
 from caelo.engine import Engine, FrameBatch, FrameFeatures, raise_status, ransac_draws  # noqa: E402
 

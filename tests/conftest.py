@@ -9,7 +9,7 @@ for p in (os.path.join(REPO, "cae-lo_amd"), os.path.join(REPO, "oracle"), REPO):
         sys.path.insert(0, p)
 
 import caelo  # noqa: E402  (before anything can initialise HIP)
-caelo.configure_runtime()  # the test session owns its process: four pipeline streams
+caelo.configure_runtime()  # the test session owns its process
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
 WEIGHTS = os.path.join(REPO, "weights")
