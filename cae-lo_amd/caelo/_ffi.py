@@ -44,6 +44,8 @@ class FrameJob(C.Structure):
 
 
 PAIR_NONE, PAIR_CHAIN, PAIR_EXPLICIT = 0, 1, 2
+EXTRACT_EXACT_VOXELS, EXTRACT_NO_DEDUP, EXTRACT_EXACT_PATCHES = 1, 2, 4   # caelo_extract / caelo_frame_job.mode bits (include/caelo.h)
+ST_TIES_LEFT = 64   # status bit of the EXTRACT_EXACT_PATCHES mode: a kd build gave up, a tie-split patch kept the canonical rule
 ABI_VERSION = 5   # include/caelo.h CAELO_ABI_VERSION
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 

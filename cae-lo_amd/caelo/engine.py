@@ -23,6 +23,7 @@ NET_H, NET_W = 64, 1792
 MAX_K = 1024
 
 ST_COL_OOB, ST_VOXEL_OOB, ST_MAP_FULL, ST_FEW_VOXELS, ST_FEW_KEYPTS, ST_NONFINITE = 1, 2, 4, 8, 16, 32
+ST_TIES_LEFT = _ffi.ST_TIES_LEFT   # not an error: the exact_patches mode left a tie-split patch on the canonical rule
 
 _DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "weights")
 RESPOND_H5 = os.path.join(_DEFAULT_WEIGHTS, "SphericalRingPCRespondLayer.h5")
@@ -51,6 +52,24 @@ def raise_status(st):
         raise AssertionError("KeyPts.shape[0] > 50")                               # SphericalRing.py:286
     if st & ST_MAP_FULL:
         raise _ffi.CaeloError("voxel map overflow")
+
+
+def extract_mode(exact_voxels=False, dedup=True, exact_patches=False):
+    """The CAELO_EXTRACT_* mode word of caelo_extract / caelo_frame_job."""
+    return ((_ffi.EXTRACT_EXACT_VOXELS if exact_voxels else 0) | (0 if dedup else _ffi.EXTRACT_NO_DEDUP)
+            | (_ffi.EXTRACT_EXACT_PATCHES if exact_patches else 0))
+
+
+def note_ties_left(eng, st):
+    """Status word(s) already read by the caller: where CAELO_ST_TIES_LEFT is set (exact_patches mode: a kd build gave up, a tie-split
+    patch kept the canonical rule and flags & 2), record it in ``eng.last_tie_unresolved`` and warn, like ``Engine.resolve_ties_many``.
+    -> number of frames concerned."""
+    n = int(np.count_nonzero(np.asarray(st) & ST_TIES_LEFT))
+    if n:
+        eng.last_tie_unresolved = n
+        import warnings
+        warnings.warn("%d frame(s) kept tie-split patch(es) on the canonical rule: the kd-tree redo gave up (flags & 2 still set)" % n)
+    return n
 
 
 def read_keras_weights(path):
@@ -172,14 +191,14 @@ class Pipeline:
         return {"jobs": int(out[0]), "issue_us_per_frame": out[1] / n / 1e3, "batches": int(out[2]), "batch": int(out[3]),
                 "buffers": int(out[4]), "streams": int(out[5])}
 
-    def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None):
+    def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None, exact_patches=False):
         """The run's jobs as one record array, filled column-wise, handed over in ONE foreign call (a ctypes call per frame
         costs ~10 us: 380 us for a 20-frame run, most of it before the first launch)."""
         k = len(ptrs)
         jobs = np.zeros(k, dtype=_ffi.JOB_DTYPE)
         idx = np.arange(k, dtype=np.uint64)
         jobs["pc"], jobs["n"] = ptrs, counts
-        jobs["dist_channels"], jobs["mode"] = int(dist_channels), (1 if exact_voxels else 0) | (0 if dedup else 2)
+        jobs["dist_channels"], jobs["mode"] = int(dist_channels), extract_mode(exact_voxels, dedup, exact_patches)
         jobs["rows"] = out.rows.data_ptr() + idx * (MAX_K * 256)
         jobs["key_pixels"] = out.key_pixels.data_ptr() + idx * (MAX_K * 16)
         jobs["n_key"] = out.n_key.data_ptr() + idx * 4
@@ -247,7 +266,7 @@ class Pipeline:
         _ffi.check(self.eng.lib.caelo_pipeline_sync_encoded(self.h, int(lag)))
 
     def run(self, scans, rands=None, prev=None, dist_channels=5, exact_voxels=False, out=None, pairs=True, dedup=True, on_batch=None,
-            on_encoded=None, certify=False, rands_host=None, publish=True):
+            on_encoded=None, certify=False, rands_host=None, publish=True, exact_patches=False):
         """scans: K device tensors [n,4] f32; rands: K device tensors of RANSAC draws ([1500,4] f64).
         Frame i is matched against frame i-1 (pose in ``result[i]``); frame 0 against ``prev``
         (FrameFeatures) when given; ``pairs=False`` extracts only (BASELINE configs[1]).  Returns a FrameBatch; the
@@ -263,7 +282,9 @@ class Pipeline:
         WRITTEN (the calling thread has waited for them: caelo_pipeline_sync_encoded, one batch behind the issue) -- what it
         enqueues on any stream may read them at once; a caller ships finished rows that way while later batches run.
         ``on_batch(lo, hi)`` is called right after frames [lo, hi) have been issued (with ``wait_encoded`` the device-side form of
-        the same hand-over, which costs the pipeline a quarter of its rate: DESIGN.md 6)."""
+        the same hand-over, which costs the pipeline a quarter of its rate: DESIGN.md 6).  ``exact_patches=True``: the reference's
+        patches (caelo_extract's CAELO_EXTRACT_EXACT_PATCHES) -- tie-split patches are redone on the device inside the run, so the
+        descriptors, matches and RANSAC results are the reference's with no host redo; ``out.status`` may carry ST_TIES_LEFT."""
         eng, lib, k = self.eng, self.eng.lib, len(scans)
         out = out or FrameBatch(eng, k)
         assert out.k >= k and (not pairs or len(rands) >= k)
@@ -276,7 +297,7 @@ class Pipeline:
             assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         _t0 = time.perf_counter()
         jobs = self._jobs([pc.data_ptr() for pc in scans], [pc.shape[0] for pc in scans], rands, prev, out, pairs, dist_channels,
-                          exact_voxels, dedup, certify, rands_host)
+                          exact_voxels, dedup, certify, rands_host, exact_patches)
         _t1 = time.perf_counter()
         tail = None   # a partial last batch is only issued by the flush: its callbacks come after that
         issued = []   # batches issued, not yet reported to on_encoded
@@ -353,7 +374,7 @@ class Pipeline:
         self.pace = int(lag)
 
     def run_uploading(self, host_scans, rands=None, prev=None, dist_channels=5, out=None, pairs=True, dedup=True, ahead=4, certify=False,
-                      rands_host=None):
+                      rands_host=None, exact_patches=False):
         """``run`` for scans that live in (pinned) HOST memory: a copy stream uploads batch b + ``ahead`` while the pipeline works on
         batch b, into ``ahead + 2`` sets of device buffers -- the overlap of the reference's producer process, which prepares
         frame i + 1 while frame i is matched (PoseEstimation.py:214-245).  The hand-overs are paced by the calling thread, not by
@@ -362,7 +383,7 @@ class Pipeline:
         copies overwrite were read by a front stage at least two batches back) and for the arrival of the next batch's scans (an
         event on the copy stream).  ``ahead``: 13.5 / 15.3 / 15.9 / 16.1 k frames/s for 1 / 2 / 3 / 4 (18.6 k resident; an arrival is
         late by up to 0.3 ms now and then, and a batch of scans is 17 MB of device memory).  Device-side waits for the same hand-overs (caelo_pipeline_wait_stream / _release_scans) cost
-        8 - 15 % of the resident rate EACH, however rarely they were issued."""
+        8 - 15 % of the resident rate EACH, however rarely they were issued.  ``exact_patches``: as in ``run``."""
         te0_ = time.perf_counter()
         eng, lib, k, B = self.eng, self.eng.lib, len(host_scans), self.batch
         out = out or FrameBatch(eng, k)
@@ -408,7 +429,7 @@ class Pipeline:
         bufs, _, copy = st
         stream = eng.stream
         jobs = self._jobs([bufs[(i // B) % slots][i % B].data_ptr() for i in range(k)], [int(pc.shape[0]) for pc in host_scans], rands, prev, out,
-                          pairs, dist_channels, False, dedup, certify, rands_host)
+                          pairs, dist_channels, False, dedup, certify, rands_host, exact_patches)
         arrived = [torch.cuda.Event() for _ in range(nb)]
 
         # the copies of a batch go out behind ONE native call (caelo_upload_many): eight sliced torch copies cost the issuing thread
@@ -532,10 +553,12 @@ class SeqLoader:
             pass
 
 
-def _run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_channels=5, dedup=True, certify=True, ahead=4, publish=True):
+def _run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_channels=5, dedup=True, certify=True, ahead=4, publish=True,
+                exact_patches=False):
     """Batches [b0, b0 + nb) of a SeqLoader through the pipeline: a batch's scans AND draws go up behind ONE copy command (the loader's
     slot layout, mirrored on the device), the jobs are built column-wise for the whole call, and nothing here is per-frame Python.
-    Paced like ``run_uploading`` (the copies go out before the thread waits for the encoder).  -> (FrameBatch, frames)."""
+    Paced like ``run_uploading`` (the copies go out before the thread waits for the encoder).  ``exact_patches``: as in ``Pipeline.run``.
+    -> (FrameBatch, frames)."""
     eng, lib, B = self.eng, self.eng.lib, self.batch
     assert loader.batch == B and ahead >= 1 and b0 + nb <= loader.n_batches
     k = min(loader.n - b0 * B, nb * B)
@@ -558,7 +581,8 @@ def _run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_chan
         eng.host_blas()
         eng._blas_bound = True
     tj0_ = time.perf_counter()
-    jobs = self._jobs(pcs, np.zeros(k, np.int64), rnd, prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None)
+    jobs = self._jobs(pcs, np.zeros(k, np.int64), rnd, prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None,
+                      exact_patches)
     tj1_ = time.perf_counter()
     stream = eng.stream
     # the whole paced loop natively (caelo_pipeline_run_uploading: wait for a batch's arrival, submit it, queue the copy `ahead` further
@@ -1036,7 +1060,7 @@ class Engine:
         return _ffi.PoseResult.from_buffer_copy(res.cpu().numpy().tobytes())
 
     # ---- fused hot path ------------------------------------------------------------------------------
-    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True):
+    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True, exact_patches=False):
         """scan [N,4] f32 (device) -> FrameFeatures, ONE C-ABI call (caelo_extract), no host sync:
         project -> response CNN -> keypoints -> voxelize -> patch gather -> 3x encoder.
         dist_channels: 5 = demo calling mode (SphericalRing.py:414), 3 = batch mode
@@ -1044,7 +1068,10 @@ class Engine:
         The default one-pass voxelization and ``exact_voxels=True`` (the two-pass first-touch kernels of
         ``voxelize``, Voxel.py:139-141) produce the same voxel sets on every cloud, points on voxel faces
         included (metrically quantised scans have some in every frame).  ``dedup=False`` encodes
-        every patch even when it is a bit-identical copy of another one of the frame (same result, more work)."""
+        every patch even when it is a bit-identical copy of another one of the frame (same result, more work).
+        ``exact_patches=True``: GetPatchesList's patches where the 496-nearest cut splits a class of equidistant voxels too (the
+        canonical rule's patches are redone on the device in the library's order before the encoder runs, flags & 4) -- what
+        ``extract`` + ``resolve_ties`` give, in the same single call.  ``status[0]`` may carry ST_TIES_LEFT (see ``note_ties_left``)."""
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
         vmap = vmap or self.voxmap(max(self.max_points, pc.shape[0]))
@@ -1056,7 +1083,7 @@ class Engine:
         status = self.empty((4,), torch.int32)
         base = rows.data_ptr()
         _ffi.check(self.lib.caelo_extract(self.ctx, vmap.h, _ptr(pc), pc.shape[0], dist_channels,
-                                          (1 if exact_voxels else 0) | (0 if dedup else 2),
+                                          extract_mode(exact_voxels, dedup, exact_patches),
                                           C.c_void_p(base + 240), 64, C.c_void_p(base), 64, C.c_void_p(base + 252), 64,
                                           _ptr(kpix), _ptr(nkey), _ptr(flags), _ptr(status), _ptr(ws),
                                           self.stream))

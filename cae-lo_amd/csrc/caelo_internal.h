@@ -115,6 +115,11 @@ struct caelo_voxmap {
     // export scratch
     void *scratch;
     int64_t scratch_bytes;
+    // CAELO_EXTRACT_EXACT_PATCHES (export.hip): the scale-0 block table of the list ordering, and -- on the map of a set's frame 0 --
+    // the set's sort buffers for xo_frames frames; allocated by exact_patches_prepare, freed with the kd storage
+    char *xo_base;
+    size_t xo_bytes;
+    int xo_frames;
 };
 
 void kd_destroy(caelo_voxmap *m);
@@ -123,7 +128,13 @@ int kd_begin_device_lists(caelo_voxmap *m, int16_t *vox_out[3], int32_t **n_out,
 int kd_resolve(const caelo_voxmap *m, const float *pts, int pts_ld, int64_t k_max, const int32_t *n_key, uint64_t *bits, uint8_t *flags,
                hipStream_t s);
 int kd_resolve_many(int n, const caelo_voxmap *const *maps, const float *const *pts, int pts_ld, int64_t k_max, const int32_t *const *n_key,
-                    uint64_t *const *bits, uint8_t *const *flags, hipStream_t s);
+                    uint64_t *const *bits, uint8_t *const *flags, hipStream_t s, bool queues_clear = false);  // queues_clear: the maps' kd state words
+                                                                                                             // are known to be zero (no memsets)
+// CAELO_EXTRACT_EXACT_PATCHES: the kd storage of a map (allocated here if missing): the lists' storage vox[3] and the state words
+#define KD_ST_CENSUS 20   // kd state words [20..22]: tie-split patches per scale counted by the fused path (export.hip)
+int kd_fused_storage(caelo_voxmap *m, int16_t *vox_out[3], int32_t **state_out);
+// after kd_resolve_many: CAELO_ST_TIES_LEFT into status[i] where a kd build of map i gave up with tie-split patches queued
+int kd_report_left(int n, const caelo_voxmap *const *maps, int32_t *const *status, hipStream_t s);
 
 struct SuspectTables {
     unsigned long long *sp_keys, *sb_keys;
@@ -332,6 +343,12 @@ int extract_front_launch(const caelo_extract_args &a, hipStream_t s);
 int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipStream_t s_vox = nullptr, hipEvent_t ev_fork = nullptr,
                       hipEvent_t ev_join = nullptr);  // s_vox: build the voxel maps beside the key-point chain  // n frames, the launches of one   // everything up to the bit-packed patches
 int extract_encode_launch(const caelo_extract_args &a, hipStream_t s);  // the four encoder kernels
+// CAELO_EXTRACT_EXACT_PATCHES (export.hip).  prepare: every device allocation the mode needs, for sets of up to n_frames frames led by
+// maps[0] (host only, before any launch of the batch).  clear_item: the map's kd state words for the set's clear list.  redo: after
+// k_patches, the tie-split patches of the set again in the library's order -- census, gated list ordering, kd / brute redo, report.
+int exact_patches_prepare(caelo_voxmap *const *maps, int n_frames);
+void exact_patches_clear_item(caelo_voxmap *m, caelo_clear_list &list);
+int exact_patches_redo(caelo_voxmap *const *maps, const caelo_frame_set &fs, const caelo_extract_args *args, int n, hipStream_t s);
 
 #define CAELO_KP_HIST_BINS 2048
 

@@ -162,18 +162,24 @@ int extract_front_launch(const caelo_extract_args &a, hipStream_t s) { return ex
 int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipStream_t s_vox, hipEvent_t ev_fork, hipEvent_t ev_join) {
     CAELO_REQUIRE(n >= 1 && n <= CAELO_FB_MAX, "bad frame count");
     const ExtractLayout L = extract_layout();
-    const bool exact_vox = (args[0].mode & CAELO_EXTRACT_EXACT_VOXELS) != 0;
+    // CAELO_EXTRACT_EXACT_PATCHES: the first-touch build (its order words too), then the tie-split patches redone before dedup / encoder
+    const bool exact_pat = (args[0].mode & CAELO_EXTRACT_EXACT_PATCHES) != 0;
+    const bool exact_vox = exact_pat || (args[0].mode & CAELO_EXTRACT_EXACT_VOXELS) != 0;
     const bool dd = dedup_enabled(args[0].mode);
     caelo_frame_set fs = {};
     fs.n = n;
     caelo_clear_list cl[CAELO_FB_MAX];
     caelo_voxmap *maps[CAELO_FB_MAX];
     for (int i = 0; i < n; ++i) {
+        CAELO_REQUIRE(args[i].mode == args[0].mode, "the frames of a set share one mode");
+        maps[i] = args[i].map;
+    }
+    int rc = CAELO_OK;
+    if (exact_pat && (rc = exact_patches_prepare(maps, n))) return rc;   // (allocates once, before the set's first launch)
+    for (int i = 0; i < n; ++i) {
         const caelo_extract_args &a = args[i];
-        CAELO_REQUIRE(a.mode == args[0].mode, "the frames of a set share one mode");
         char *ws = (char *)a.ws;
         caelo_frame_dev &d = fs.f[i];
-        maps[i] = a.map;
         frame_dev_set_map(d, a.map);
         d.pc = a.pc; d.n = a.n; d.pc_stride = 4; d.dist_c = a.dist_channels;
         d.ring = (float *)(ws + L.ring); d.counter = nullptr; d.winner = (int32_t *)(ws + L.winner);  // (occupied = has a winner)
@@ -187,10 +193,10 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
         cl[i].item[cl[i].n++] = {d.winner, L.cand_count - L.winner, 0xFFFFFFFFu};
         cl[i].item[cl[i].n++] = {d.cand_count, L.ring - L.cand_count, 0u};
         cl[i].item[cl[i].n++] = {a.status, 16, 0u};  // status is int32[4], 16-byte aligned (word 0 carries the bits)
-        if (exact_vox) vox_clear_items(a.map, 1, cl[i]);
+        if (exact_vox) vox_clear_items(a.map, exact_pat ? 2 : 1, cl[i]);
+        if (exact_pat) exact_patches_clear_item(a.map, cl[i]);   // the map's kd state words (census, list lengths, build flags)
         if (i == 0) dedup_clear_item(ws + L.dd, n, cl[i]);  // the set's table lives in frame 0's scratch
     }
-    int rc = CAELO_OK;
     if (!exact_vox && (rc = vox_clear_for_fast_build_set(maps, n, cl, s))) return rc;  // wipes the previous frames' bricks only
     if ((rc = caelo_clear_many_set(cl, n, s))) return rc;
     // The voxel map only needs the points: with a second stream (the frame pipeline passes one when the runtime has hardware
@@ -201,7 +207,7 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
         CAELO_HIP(hipStreamWaitEvent(s_vox, ev_fork, 0));
     }
     // ---- voxel map
-    if (exact_vox) rc = vox_build_set(maps, fs, false, sv);
+    if (exact_vox) rc = vox_build_set(maps, fs, exact_pat, sv);
     else rc = vox_build_fast_set(maps, fs, sv);
     if (rc) return rc;
     if (s_vox) CAELO_HIP(hipEventRecord(ev_join, s_vox));
@@ -215,6 +221,10 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     // equal patches are encoded once (dedup.hip): k_patches enters every patch into the hash table, the tables land
     // behind the frame's bits
     if ((rc = vox_patches_set(fs, CAELO_MAX_KEYPTS, true, s))) return rc;
+    // The redo comes before dedup: k_patches entered the canonical bits' hashes, so a redone patch's hash is stale -- k_dd_verify
+    // compares every patch word by word with its group's representative (whose own bits, redone or not, are what it reads), so such a
+    // patch shares only with a patch that is equal bit for bit, or represents itself: exact, at worst some sharing lost.
+    if (exact_pat && (rc = exact_patches_redo(maps, fs, args, n, s))) return rc;
     return dedup_set(fs, dd, s);
 }
 

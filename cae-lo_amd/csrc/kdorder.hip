@@ -20,8 +20,9 @@
 // (flag bit 2); only THOSE are redone here, and only when the voxel lists are known in the reference's order -- a map filled by
 // caelo_voxmap_from_lists (the staged API: api.GetPatchesList) -- and long enough for the kd-tree.  A redone patch carries flag 4
 // instead of 2.  Rare by construction: 0 of 614 400 patches on the KITTI-shaped scene, 115 on the clutter scene (200 frames each).
-// The fused path (caelo_extract, caelo_pipeline) builds voxel SETS, not lists in first-touch order: its flagged patches keep the
-// canonical rule and bit 2 (INTEGRATION.md says what a caller who needs them exact does).
+// The fused path (caelo_extract, caelo_pipeline) builds voxel SETS, not lists in first-touch order: by default its flagged patches keep
+// the canonical rule and bit 2.  With CAELO_EXTRACT_EXACT_PATCHES it builds the first-touch tables too, orders the lists of the tied
+// (frame, scale) pairs on the device (export.hip) and redoes those patches here before the encoder runs.
 //
 // Lists of 496 .. 993 voxels (round 6): `auto` is BRUTE FORCE there -- squared distances to every list entry in list order (exact
 // integers), then np.argpartition(dist, 495)[:496] (scikit-learn 0.24.2 _kneighbors_reduce_func; the sort that follows only reorders
@@ -687,6 +688,12 @@ __global__ void __launch_bounds__(64) k_brute_query(const caelo_kd_set S_) {
 }  // namespace
 
 void kd_destroy(caelo_voxmap *m) {
+    if (m->xo_base) {
+        (void)hipFree(m->xo_base);
+        m->xo_base = nullptr;
+        m->xo_bytes = 0;
+        m->xo_frames = 0;
+    }
     if (m->kd) {
         if (m->kd->base) (void)hipFree(m->kd->base);
         delete m->kd;
@@ -760,6 +767,43 @@ int kd_begin_device_lists(caelo_voxmap *m, int16_t *vox_out[3], int32_t **n_out,
     return CAELO_OK;
 }
 
+// CAELO_EXTRACT_EXACT_PATCHES: the fused path writes the lists straight into the tree's storage and counts its tie-split patches into the
+// state words (which the set's clear zeroes before every build)
+int kd_fused_storage(caelo_voxmap *m, int16_t *vox_out[3], int32_t **state_out) {
+    const int rc = kd_alloc(m);
+    if (rc != CAELO_OK) return rc;
+    for (int i = 0; i < 3; ++i) vox_out[i] = m->kd->s[i].vox;
+    *state_out = m->kd->state;
+    return CAELO_OK;
+}
+
+namespace {
+struct KdLeftSet {
+    int32_t *state[CAELO_FB_MAX];
+    int32_t *status[CAELO_FB_MAX];
+};
+// a scale whose queue is not empty and whose tree was not built (a quickselect gave up, or too many nodes): its patches stay on the
+// canonical rule with flag 2 -- say so in the frame's status word
+__global__ void k_kd_report_left(const KdLeftSet S) {
+    const int32_t *state = S.state[blockIdx.z];
+    const int sc = threadIdx.x;
+    if (sc < 3 && state[sc] > 0 && state[4 + sc] == 2) atomicOr(S.status[blockIdx.z], CAELO_ST_TIES_LEFT);
+}
+}  // namespace
+
+int kd_report_left(int n, const caelo_voxmap *const *maps, int32_t *const *status, hipStream_t s) {
+    CAELO_REQUIRE(n >= 1 && n <= CAELO_FB_MAX, "kd_report_left: 1 .. 8 maps");
+    KdLeftSet S = {};
+    for (int i = 0; i < n; ++i) {
+        CAELO_REQUIRE(maps[i]->kd, "kd_report_left: a map without kd storage");
+        S.state[i] = maps[i]->kd->state;
+        S.status[i] = status[i];
+    }
+    k_kd_report_left<<<dim3(1, 1, n), 64, 0, s>>>(S);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
 // caelo_patches, after k_patches: the tie-split patches again, in the library's order
 int kd_resolve(const caelo_voxmap *m, const float *pts, int pts_ld, int64_t k_max, const int32_t *n_key, uint64_t *bits, uint8_t *flags,
                hipStream_t s) {
@@ -773,7 +817,7 @@ int kd_resolve(const caelo_voxmap *m, const float *pts, int pts_ld, int64_t k_ma
 
 // the same for n maps (each with its own lists) behind one launch of each kernel; maps without lists are skipped
 int kd_resolve_many(int n, const caelo_voxmap *const *maps, const float *const *pts, int pts_ld, int64_t k_max, const int32_t *const *n_key,
-                    uint64_t *const *bits, uint8_t *const *flags, hipStream_t s) {
+                    uint64_t *const *bits, uint8_t *const *flags, hipStream_t s, bool queues_clear) {
     CAELO_REQUIRE(n >= 1 && n <= CAELO_FB_MAX, "kd_resolve_many: 1 .. 8 maps");
     caelo_kd_set S = {};
     int64_t cap = 0, k_cap = 0;
@@ -790,7 +834,8 @@ int kd_resolve_many(int n, const caelo_voxmap *const *maps, const float *const *
     if (S.n == 0) return CAELO_OK;
     S.pts_ld = pts_ld;
     for (int64_t k0 = 0; k0 < k_max; k0 += k_cap) {   // (the queues hold k_cap key points: longer point lists go chunk by chunk)
-        for (int i = 0; i < S.n; ++i) CAELO_HIP(hipMemsetAsync(S.k[i].state, 0, 12, s));   // queue lengths (the built flags stay)
+        if (!queues_clear || k0 > 0)
+            for (int i = 0; i < S.n; ++i) CAELO_HIP(hipMemsetAsync(S.k[i].state, 0, 12, s));   // queue lengths (the built flags stay)
         k_kd_collect<<<dim3((unsigned)((k_cap * 3 + 255) / 256), 1, S.n), 256, 0, s>>>(S, k0, k_max);
         CAELO_LAUNCH_CHECK();
         k_kd_build_top<<<dim3(3, 1, S.n), KD_T, 0, s>>>(S);

@@ -725,6 +725,11 @@ CAELO_API int caelo_pipeline_submit(caelo_pipeline *p, const caelo_frame_job *jo
         caelo_set_error("caelo_pipeline_submit: the first job has no predecessor to chain to");
         return CAELO_ERR_ARG;
     }
+    if ((job->mode & CAELO_EXTRACT_EXACT_PATCHES) && !(p->maps[0]->xo_base && p->maps[0]->xo_frames >= p->batch)) {
+        // the first job in this mode: kd storage + ordering scratch of every frame slot's map, before any launch of its batch
+        const int rc = exact_patches_prepare(p->maps, p->batch);
+        if (rc) return rc;
+    }
     if (!p->pending.empty() && (p->pending[0].mode != job->mode)) {  // the frames of a launch share one mode
         const int rc = issue_batch(p);
         if (rc) return rc;

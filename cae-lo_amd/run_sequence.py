@@ -30,7 +30,7 @@ from caelo import _ffi, stageio, synth  # noqa: E402
 import caelo  # noqa: E402
 caelo.configure_runtime()  # this script owns its process: before HIP starts (the queue count is left to the caller)
 from caelo import dist as cdist  # noqa: E402
-from caelo.engine import Engine, FrameBatch, FrameFeatures, raise_status, ransac_draws  # noqa: E402
+from caelo.engine import Engine, FrameBatch, FrameFeatures, note_ties_left, raise_status, ransac_draws  # noqa: E402
 
 
 def pose_rows(batch, k):
@@ -49,7 +49,7 @@ def _parse_poses(raw, k):
 
 
 def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-              loader_threads=4, certify=True):
+              loader_threads=4, certify=True, native_ties=False):
     """Frames [lo, hi) of this rank.  Returns per-pair rows for pairs (i-1, i), i in (lo, hi) -- the pair (lo-1, lo)
     is the caller's (it needs the previous rank's last frame) -- plus the first and last frame's features.
 
@@ -59,6 +59,7 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
       * inside a chunk, a copy stream uploads batch b + 4 while the pipeline works on batch b (Pipeline.run_uploading, paced by this thread);
       * the poses and status words of chunk c come back through pinned buffers on a side stream and are parsed after chunk
         c + 1 has been issued.
+    ``native_ties``: the pipeline redoes tie-split patches itself (Pipeline.run_uploading(exact_patches=True)): no host redo, no re-match.
     """
     import queue
     import threading
@@ -152,6 +153,7 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
         t_ = time.time()
         for st in st_h.numpy()[:, 0]:
             raise_status(int(st))
+        note_ties_left(eng, st_h.numpy()[:, 0])
         r, o, t, n = _parse_poses(res_h.numpy(), k)
         s = 0 if has_prev else 1                                   # slot 0 of the first chunk has no predecessor here
         rel.append(r[s:]); ok.append(o[s:]); thr.append(t[s:]); nin.append(n[s:])
@@ -171,10 +173,11 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
         # GPU; the call returns when this chunk's inlier sets and poses -- the reference's bits -- are in batch.result / inlier_mask)
         dn_ = draws.numpy()
         batch = pipe.run_uploading(scans, [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels,
-                                   certify=certify, rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None)
+                                   certify=certify, rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None,
+                                   exact_patches=native_ties)
         ht["pipeline"] += time.time() - t_
         t_ = time.time()
-        if strict_ties:
+        if strict_ties and not native_ties:
             # Frames whose 496-nearest cut (Voxel.py:195-196) splits a class of equidistant voxels: the fused path's canonical rule is
             # replaced by scikit-learn's kd-tree order (Engine.resolve_ties: ordered voxel lists, all on the device), then the pairs
             # such a frame is part of are matched again.  One synchronisation per chunk; rare (none on KITTI-shaped scans).
@@ -236,7 +239,7 @@ def _parse_poses_fast(raw, k):
 
 
 def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-                    loader_threads=16, certify=True, device_results=False):
+                    loader_threads=16, certify=True, device_results=False, native_ties=False):
     """run_local for scans that are FILES (round 6): the native loader (caelo_seqloader: pread into a pinned ring + the RANSAC draws,
     csrc/seqload.hip) works ahead on its own threads, a chunk of batches goes through Pipeline.run_loaded (one copy command per batch
     for scans and draws, jobs built column-wise), results come back through pinned buffers and are parsed as one record array.
@@ -288,6 +291,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
         if st.any():
             for v in st[st != 0]:
                 raise_status(int(v))
+            note_ties_left(eng, st)
         r, o, t, n = _parse_poses_fast(res_h if isinstance(res_h, np.ndarray) else res_h.numpy(), k)
         s_ = 0 if has_prev else 1
         rel.append(r[s_:]); ok.append(o[s_:]); thr.append(t[s_:]); nin.append(n[s_:])
@@ -301,7 +305,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
         # published to the device and copied back (publish=False: 51 ms of 0.40 s for 4 541 frames)
         # (device_results -- the artefact writer reads masks and pair indices from the device tensors -- publishes them as before)
         batch, k = pipe.run_loaded(loader, b0, nb, prev=prev, out=outs[ci % 2], dist_channels=dist_channels, certify=certify,
-                                   publish=device_results or not certify)
+                                   publish=device_results or not certify, exact_patches=native_ties)
         host_res = batch.exact[0][:k].copy().view(np.uint8).reshape(k, -1) if certify else None
         ht["pipeline"] += time.time() - t_
         ht["starved"] += pipe.last_loaded_times["starved_s"]
@@ -309,7 +313,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
             ht["loaded_" + k_] = ht.get("loaded_" + k_, 0.0) + v_
         c0 = lo + b0 * B
         t_ = time.time()
-        if strict_ties and bool((batch.flags[:k] & 2).any().item()):
+        if strict_ties and not native_ties and bool((batch.flags[:k] & 2).any().item()):
             # (as run_local: the tied frames' scans are read again -- rare -- and redone in scikit-learn's kd-tree order, their pairs matched again)
             fl = (batch.flags[:k] & 2).reshape(k, -1).any(dim=1).cpu().numpy()
             items = [(batch.frame(j), torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device) if fl[j] else None) for j in range(k)]
@@ -389,6 +393,8 @@ def main():
     ap.add_argument("--save-artifacts", action="store_true", help="write Features/*.mat and InliersIdx/*.mat next to the scans")
     ap.add_argument("--no-strict-ties", action="store_true", help="keep the fused path's canonical rule where the 496-nearest cut splits a "
                                                                   "tie class (default: such frames are redone in scikit-learn's kd-tree order)")
+    ap.add_argument("--native-ties", action="store_true", help="the pipeline redoes tie-split patches itself in scikit-learn's order "
+                                                               "(CAELO_EXTRACT_EXACT_PATCHES): no host redo and re-match; same results")
     ap.add_argument("--no-certify", action="store_true", help="the kernels' own RANSAC results (float64 fits) without the host half that makes "
                                                               "inlier sets and poses the reference's bits (csrc/certify.hip)")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
@@ -475,11 +481,12 @@ def main():
     if args.scans and not args.python_loader:
         rel, ok, thr, nin, first, last = run_local_files(eng, files, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                          args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
-                                                         loader_threads=args.loader_threads, certify=not args.no_certify, device_results=args.save_artifacts)
+                                                         loader_threads=args.loader_threads, certify=not args.no_certify, device_results=args.save_artifacts,
+                                                         native_ties=args.native_ties)
     else:
         rel, ok, thr, nin, first, last = run_local(eng, load, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                    args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
-                                                   loader_threads=args.loader_threads, certify=not args.no_certify)
+                                                   loader_threads=args.loader_threads, certify=not args.no_certify, native_ties=args.native_ties)
     if tie_log:
         print("rank %d: %d frame(s) redone in scikit-learn's tie order (%d patches): %s" % (
             rank, len(tie_log), sum(n for _, n in tie_log), [f for f, _ in tie_log][:20]), file=sys.stderr)

@@ -58,6 +58,9 @@ typedef enum {
                                         sets on every input, points on voxel faces included (tests compare them) */
 #define CAELO_EXTRACT_NO_DEDUP 2     /* caelo_extract mode bit: encode every patch, also bit-identical copies of another one
                                         (by default equal patches of a frame are encoded once: same descriptors, bit for bit) */
+#define CAELO_EXTRACT_EXACT_PATCHES 4 /* caelo_extract / caelo_frame_job.mode bit: GetPatchesList's patches on every input (see caelo_extract) */
+#define CAELO_ST_TIES_LEFT 64     /* CAELO_EXTRACT_EXACT_PATCHES only: a kd-tree build gave up on its pass budget and a tie-split patch was
+                                   * left on the canonical rule (flags & 2 still set) */
 
 typedef struct caelo_ctx caelo_ctx;
 typedef struct caelo_voxmap caelo_voxmap;
@@ -308,7 +311,18 @@ int caelo_host_certify(const void *certs_host, int64_t k, const double *const *r
  * [1024][feat_ld] (60 used), valid (optional) [1024] with stride valid_ld = 1.0 for rows < K,
  * key_pixels [1024][2], n_key [1], flags [1024][3] (caelo_patches), status int32[4] 16-byte aligned
  * (word 0 = CAELO_ST_* bits, cleared by the call).  ws: caelo_extract_ws_bytes() bytes, 256-byte aligned, zero-filled
- * once by its owner before the first call (it embeds an encoder workspace), one ws per stream. */
+ * once by its owner before the first call (it embeds an encoder workspace), one ws per stream.
+ * mode: CAELO_EXTRACT_* bits.  By default the voxel maps are SETS: where the 496-nearest cut (Voxel.py:195-196) splits a class of
+ * equidistant voxels the patch follows a canonical rule and carries flags & 2.  CAELO_EXTRACT_EXACT_PATCHES returns the reference's
+ * patches instead, in the same call and with no host involvement: the two-pass first-touch voxelization (implies
+ * CAELO_EXTRACT_EXACT_VOXELS), a device-side count of the tie-split patches per scale, the first-touch lists of only the (frame, scale)
+ * pairs that hold one, and the redo of those patches before the encoder runs -- scikit-learn's kd-tree from 994 voxels on,
+ * np.argpartition's introselect below (what caelo_voxelize + caelo_voxmap_order + caelo_patches + caelo_encode give).  Redone
+ * patches carry flags & 4.  A kd build that gives up on its pass budget leaves its patches on the canonical rule (flags & 2) and
+ * sets CAELO_ST_TIES_LEFT in the status word.  The first call in this mode allocates the map's kd storage (about
+ * 3 x max_points x 30 B plus 3 x 16384 x 20 B of node tables) and its ordering scratch (about 12 B per first-touch table slot plus
+ * 3 x max_points x 24 B of sort buffers); later calls allocate nothing.  Frames without a tie-split patch get the default mode's
+ * results, bit for bit. */
 int64_t caelo_extract_ws_bytes(void);
 int caelo_extract(caelo_ctx *ctx, caelo_voxmap *map, const float *pc, int64_t n, int dist_channels, int mode, float *key_pts,
                   int kp_ld, float *features, int feat_ld, float *valid, int valid_ld, int64_t *key_pixels,
@@ -389,7 +403,10 @@ typedef struct caelo_frame_job {
     const float *pc;            /* [n][4] f32 */
     int64_t n;
     int32_t dist_channels;      /* 5 | 3, see caelo_extract */
-    int32_t mode;               /* CAELO_EXTRACT_* bits */
+    int32_t mode;               /* CAELO_EXTRACT_* bits (CAELO_EXTRACT_EXACT_PATCHES: the reference's patches, see caelo_extract; the
+                                   status word then also reports CAELO_ST_TIES_LEFT.  The first job in this mode allocates, before its batch
+                                   is launched, the kd storage and ordering scratch of every frame slot's map -- per slot what caelo_extract
+                                   lists, and on slot 0 the batch's sort buffers, batch x 3 x max_points x 24 B) */
     float *rows;                /* [1024][64] f32 out */
     int64_t *key_pixels;        /* [1024][2] out */
     int32_t *n_key;             /* [1] out */

@@ -1,0 +1,200 @@
+"""CAELO_EXTRACT_EXACT_PATCHES: the fused path (caelo_extract, caelo_pipeline) returns GetPatchesList's patches on every input -- the
+tie-split patches (the 496-nearest cut of Voxel.py:195-196 inside a class of equidistant voxels) are redone on the device in the
+library's order before the encoder runs, so descriptors, matches and RANSAC results equal what the host-orchestrated redo
+(Engine.resolve_ties(_many) + Engine.match_pose_exact_many) gives, in one pass.  Clutter frames 20..27 hold tie-split patches
+(frame 23: 11, tests/golden/frame_c23.npz); mm-quantised boxes frames (the bench workload) hold none."""
+import os
+import re
+
+import numpy as np
+import pytest
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+GOLDEN = os.path.join(REPO, "tests", "golden")
+CLUTTER = list(range(20, 28))
+
+
+def _header_defines():
+    src = open(os.path.join(REPO, "include", "caelo.h")).read()
+    return {m.group(1): int(m.group(2)) for m in re.finditer(r"#define\s+(CAELO_\w+)\s+(\d+)\b", src)}
+
+
+def test_mode_and_status_bits_match_the_header():
+    from caelo import _ffi, engine
+    d = _header_defines()
+    assert d["CAELO_EXTRACT_EXACT_PATCHES"] == 4 == _ffi.EXTRACT_EXACT_PATCHES
+    assert d["CAELO_ST_TIES_LEFT"] == 64 == _ffi.ST_TIES_LEFT == engine.ST_TIES_LEFT
+    assert d["CAELO_EXTRACT_EXACT_VOXELS"] == _ffi.EXTRACT_EXACT_VOXELS and d["CAELO_EXTRACT_NO_DEDUP"] == _ffi.EXTRACT_NO_DEDUP
+    # the status bit is none of the error bits raise_status maps to exceptions
+    assert d["CAELO_ST_TIES_LEFT"] not in (d["CAELO_ST_COL_OOB"], d["CAELO_ST_VOXEL_OOB"], d["CAELO_ST_MAP_FULL"], d["CAELO_ST_FEW_VOXELS"],
+                                           d["CAELO_ST_FEW_KEYPTS"], d["CAELO_ST_NONFINITE"])
+    assert engine.extract_mode() == 0 and engine.extract_mode(exact_patches=True) == 4
+    assert engine.extract_mode(exact_voxels=True, dedup=False, exact_patches=True) == 7
+
+
+def test_ties_left_is_noted_not_raised():
+    import warnings
+    from caelo import engine
+
+    class _E:
+        pass
+    e = _E()
+    assert engine.note_ties_left(e, np.array([0, 0], np.int32)) == 0 and not hasattr(e, "last_tie_unresolved")
+    engine.raise_status(engine.ST_TIES_LEFT)        # not an error of the reference
+    with warnings.catch_warnings(record=True) as w:
+        warnings.simplefilter("always")
+        assert engine.note_ties_left(e, np.array([0, 64, 64 | 8], np.int32)) == 2
+    assert e.last_tie_unresolved == 2 and len(w) == 1
+
+
+def _clutter(engine, scans, ids=CLUTTER):
+    import torch
+    return [torch.from_numpy(scans(i, quantum=1e-3, scene_kind="clutter")).to(engine.device) for i in ids]
+
+
+@pytest.mark.gpu
+def test_single_call_equals_extract_then_resolve_ties(engine, scans):
+    import torch
+    gc = np.load(os.path.join(GOLDEN, "frame_c23.npz"))
+    seen4 = 0
+    for i, pc in zip(CLUTTER, _clutter(engine, scans)):
+        ex = engine.extract(pc, exact_patches=True)
+        ref = engine.extract(pc)
+        n_t = engine.resolve_ties(ref, pc)
+        torch.cuda.synchronize()
+        assert torch.equal(ex.rows, ref.rows), "frame %d" % i
+        assert torch.equal(ex.flags, ref.flags), "frame %d" % i
+        assert int(ex.status[0].item()) == 0
+        k = int(ex.n_key.item())
+        fl = ex.flags[:k].cpu().numpy()
+        assert not (fl & 2).any()
+        assert int(((fl & 4) != 0).sum()) == n_t
+        seen4 += n_t
+        if i == 23:
+            assert n_t == 11 and (fl & 4).any()
+            assert np.abs(ex.rows[:k, 0:60].cpu().numpy() - gc["features"][:k]).max() <= 1e-4
+    assert seen4 > 11
+
+
+@pytest.fixture(scope="module")
+def host_redo(engine, scans):
+    """The host-orchestrated reference of a pipeline run over clutter frames 20..27: run + resolve_ties_many + match_pose_exact_many on
+    the pairs that touch a redone frame."""
+    import torch
+    from caelo.engine import ransac_draws
+    pcs = _clutter(engine, scans)
+    draws = [ransac_draws(70 + i) for i in CLUTTER]
+    rnd = [torch.from_numpy(d).to(engine.device) for d in draws]
+    a = engine.pipeline(4, 3).run(pcs, rnd, certify=True, rands_host=draws)
+    tied, _ = engine.resolve_ties_many([(a.frame(j), pcs[j]) for j in range(len(pcs))], batch=a)
+    assert 3 in tied
+    redo = sorted({t for u in tied for t in (u, u + 1) if 0 < t < len(pcs)})
+    rs, ms, xs = engine.match_pose_exact_many([(a.frame(j - 1), a.frame(j)) for j in redo], [rnd[j] for j in redo], [draws[j] for j in redo])
+    sel = torch.tensor(redo, device=engine.device)
+    a.result[sel] = torch.from_numpy(rs.view(np.uint8).reshape(len(redo), -1).copy()).to(engine.device)
+    a.inlier_mask[sel] = torch.from_numpy(ms).to(engine.device)
+    for q, j in enumerate(redo):
+        a.pair_idx[j].copy_(xs[q])
+    torch.cuda.synchronize()
+    return dict(pcs=pcs, draws=draws, rnd=rnd, out=a, redo=redo)
+
+
+def _assert_same_run(got, want, k):
+    import torch
+    assert torch.equal(got.rows[:k], want.rows[:k])
+    assert torch.equal(got.flags[:k], want.flags[:k])
+    assert torch.equal(got.pair_idx[1:k], want.pair_idx[1:k])
+    assert torch.equal(got.result[1:k], want.result[1:k])
+    assert torch.equal(got.inlier_mask[1:k], want.inlier_mask[1:k])
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("dedup", [True, False])
+@pytest.mark.parametrize("batch,buffers", [(1, 2), (1, 3), (4, 2), (4, 3), (8, 2), (8, 3)])
+def test_pipeline_equals_host_orchestrated_redo(engine, host_redo, batch, buffers, dedup):
+    import torch
+    h = host_redo
+    k = len(h["pcs"])
+    pipe = engine.pipeline(batch, buffers)
+    e = pipe.run(h["pcs"], h["rnd"], exact_patches=True, certify=True, rands_host=h["draws"], dedup=dedup)
+    torch.cuda.synchronize()
+    _assert_same_run(e, h["out"], k)
+    assert not (e.status[:k, 0].cpu().numpy() & 64).any() and (e.status[:k, 0].cpu().numpy() == 0).all()
+    res, masks, _, st = e.exact
+    assert (st[1:k] == 0).all()
+    want = h["out"].result[1:k].cpu().numpy()
+    assert res[1:k].view(np.uint8).reshape(k - 1, -1).tobytes() == want.tobytes()
+    assert np.array_equal(masks[1:k], h["out"].inlier_mask[1:k].cpu().numpy())
+
+
+@pytest.mark.gpu
+def test_no_ties_no_change(engine, scans):
+    """Boxes frames (mm-quantised, the bench workload) have no tie-split patch: the mode returns the default mode's bits, a partial
+    last batch included."""
+    import torch
+    from caelo.engine import ransac_draws
+    ids = list(range(10))
+    pcs = [torch.from_numpy(scans(i, quantum=1e-3)).to(engine.device) for i in ids]
+    rnd = [torch.from_numpy(ransac_draws(300 + i)).to(engine.device) for i in ids]
+    pipe = engine.pipeline(4, 3)
+    d = pipe.run(pcs, rnd)
+    e = pipe.run(pcs, rnd, exact_patches=True)
+    torch.cuda.synchronize()
+    k = len(ids)
+    assert not (d.flags[:k] & 2).any()
+    _assert_same_run(e, d, k)
+    assert torch.equal(e.status[:k], d.status[:k])
+
+
+@pytest.mark.gpu
+def test_mixed_modes_on_one_pipeline(engine, scans):
+    """Exact and default jobs alternate on one pipeline (a mode change issues the batch): each frame gets its own mode's results."""
+    import ctypes as C
+    import torch
+    from caelo import _ffi
+    from caelo.engine import FrameBatch, extract_mode
+    pcs = _clutter(engine, scans)
+    k = len(pcs)
+    pipe = engine.pipeline(4, 2)
+    want_d = pipe.run(pcs, None, pairs=False)
+    want_e = pipe.run(pcs, None, pairs=False, exact_patches=True)
+    out = FrameBatch(engine, k)
+    jobs = pipe._jobs([pc.data_ptr() for pc in pcs], [pc.shape[0] for pc in pcs], None, None, out, False, 5, False, True, exact_patches=True)
+    jobs["mode"][0::2] = extract_mode()
+    lib = engine.lib
+    _ffi.check(lib.caelo_pipeline_expect(pipe.h, 0))
+    _ffi.check(lib.caelo_pipeline_begin(pipe.h, engine.stream))
+    try:
+        _ffi.check(lib.caelo_pipeline_submit_many(pipe.h, C.c_void_p(jobs.ctypes.data), k))
+    finally:
+        _ffi.check(lib.caelo_pipeline_flush(pipe.h, engine.stream))
+    torch.cuda.synchronize()
+    assert (want_d.flags[:k] & 2).any() and not (want_e.flags[:k] & 2).any()
+    for j in range(k):
+        want = want_d if j % 2 == 0 else want_e
+        assert torch.equal(out.rows[j], want.rows[j]) and torch.equal(out.flags[j], want.flags[j]), "frame %d" % j
+
+
+@pytest.mark.gpu
+def test_uploading_and_run_sequence_native_ties(engine, scans, host_redo):
+    import importlib.util
+    import torch
+    h = host_redo
+    k = len(h["pcs"])
+    host = [pc.cpu().pin_memory() for pc in h["pcs"]]
+    pipe = engine.pipeline(4, 3)
+    e = pipe.run_uploading(host, h["rnd"], exact_patches=True, certify=True, rands_host=h["draws"])
+    torch.cuda.synchronize()
+    _assert_same_run(e, h["out"], k)
+    spec = importlib.util.spec_from_file_location("run_sequence", os.path.join(REPO, "cae-lo_amd", "run_sequence.py"))
+    rs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rs)
+
+    def load(i):
+        return scans(i, quantum=1e-3, scene_kind="clutter")
+    tie_log = []
+    strict = rs.run_local(engine, load, 16, 32, 500, chunk=8, dist_channels=5, batch_frames=4, tie_log=tie_log)
+    native = rs.run_local(engine, load, 16, 32, 500, chunk=8, dist_channels=5, batch_frames=4, native_ties=True)
+    assert tie_log, "the strict path found no tied frame: the comparison shows nothing"
+    for a, b in zip(strict[:4], native[:4]):
+        assert np.array_equal(a, b)
