@@ -46,6 +46,9 @@ class FrameJob(C.Structure):
 PAIR_NONE, PAIR_CHAIN, PAIR_EXPLICIT = 0, 1, 2
 EXTRACT_EXACT_VOXELS, EXTRACT_NO_DEDUP, EXTRACT_EXACT_PATCHES = 1, 2, 4   # caelo_extract / caelo_frame_job.mode bits (include/caelo.h)
 ST_TIES_LEFT = 64   # status bit of the EXTRACT_EXACT_PATCHES mode: a kd build gave up, a tie-split patch kept the canonical rule
+EXTRACT_GIVEN_KEYPTS, EXTRACT_GIVEN_ROWS = 8, 16   # the caller's key points (caelo_extract / jobs); the caller's rows (jobs only)
+ST_BAD_KEYPTS = 128   # status bit of EXTRACT_GIVEN_KEYPTS: K outside [1, 1024], or a coordinate non-finite or beyond GIVEN_KEYPTS_RANGE
+GIVEN_KEYPTS_RANGE = 16384.0   # metres, include/caelo.h CAELO_GIVEN_KEYPTS_RANGE
 ABI_VERSION = 5   # include/caelo.h CAELO_ABI_VERSION
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 

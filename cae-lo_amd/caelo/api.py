@@ -8,6 +8,8 @@ tuples / dtypes, served by the HIP engine.
     Voxel.Voxelization                    :100  Voxelization(PC)
     Voxel.GetPatchesList                  :177  GetPatchesList(Pts, AllVoxels0, AllVoxels1, AllVoxels2)
     Match.GetFeaturesFromPatches          :130  GetFeaturesFromPatches(PatchEncoder, PatchesList)
+    GetPatchesList + GetFeaturesFromPatches on a scan, fused (PoseEstimation.py:41,:106-108)
+                                                GetFeaturesAtKeyPts(PC, KeyPts, exact_patches=True)
     Match.SolveRT / RANSAC4RT             :138/:162
     Match.SolveRelativePose               :241  SolveRelativePose(PC0, F0, W0, PC1, F1, W1)
     keras.models.load_model (Match.py:313,324)  load_model(h5_path) -> object with .predict
@@ -283,6 +285,29 @@ def GetFeaturesFromPatches(PatchEncoder, PatchesList):
     """Match.py:130-135."""
     f = [PatchEncoder.predict(p) for p in PatchesList]
     return np.c_[f[0], f[1], f[2]] if _is_np(f[0]) else torch.cat(f, dim=1)
+
+
+def GetFeaturesAtKeyPts(PC, KeyPts, exact_patches=True):
+    """Voxelization(PC) -> GetPatchesList(KeyPts, ...) -> GetFeaturesFromPatches for key points of any source (PoseEstimation.py:41,
+    :106-108) in ONE fused call (caelo_extract with CAELO_EXTRACT_GIVEN_KEYPTS) -> (KeyPts, Features [K,60] f32).  PC [N,3|4] f32;
+    KeyPts [K,3], K in [1, 1024] (more: the staged functions above), carried in float32 (keysources module note), |x|, |y|, |z| <=
+    16384 m.  ``exact_patches`` (default): GetPatchesList's patches also where the 496-nearest cut splits a class of equidistant
+    voxels (CAELO_EXTRACT_EXACT_PATCHES).  ValueError for a bad key point set (a deviation: the reference would compute empty patches
+    for NaN) and the reference's errors for the scan (ValueError with fewer than 496 voxels in a scale)."""
+    from . import keysources
+    e = default_engine()
+    as_np = _is_np(KeyPts)
+    keysources.check_count(int(KeyPts.shape[0]))
+    pc = _dev(PC, torch.float32)
+    assert pc.dim() == 2 and pc.shape[1] in (3, 4), "PC: [N, 3] or [N, 4]"
+    if pc.shape[1] == 3:
+        pc = torch.cat([pc, torch.zeros_like(pc[:, :1])], dim=1).contiguous()
+    kp = _dev(KeyPts, torch.float32)
+    ff = e.extract(pc, exact_patches=exact_patches, key_pts=kp)
+    raise_status(int(ff.status[0].item()))
+    _eng.note_ties_left(e, ff.status[0:1].cpu().numpy())
+    feats = ff.features[:kp.shape[0]].contiguous()
+    return KeyPts, _out(feats, as_np)
 
 
 def SolveRT(Pairs0, Pairs1):

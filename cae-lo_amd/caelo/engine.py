@@ -24,6 +24,7 @@ MAX_K = 1024
 
 ST_COL_OOB, ST_VOXEL_OOB, ST_MAP_FULL, ST_FEW_VOXELS, ST_FEW_KEYPTS, ST_NONFINITE = 1, 2, 4, 8, 16, 32
 ST_TIES_LEFT = _ffi.ST_TIES_LEFT   # not an error: the exact_patches mode left a tie-split patch on the canonical rule
+ST_BAD_KEYPTS = _ffi.ST_BAD_KEYPTS   # given key points (extract(key_pts=...), Pipeline.run(keypts=...)) the engine cannot serve
 
 _DEFAULT_WEIGHTS = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "weights")
 RESPOND_H5 = os.path.join(_DEFAULT_WEIGHTS, "SphericalRingPCRespondLayer.h5")
@@ -40,6 +41,9 @@ def _hptr(a):
 
 def raise_status(st):
     """Map device status bits to the exception the reference would raise (SURVEY 8b 'Errors')."""
+    if st & ST_BAD_KEYPTS:   # (a deviation: the reference raises nothing there -- include/caelo.h CAELO_ST_BAD_KEYPTS)
+        raise ValueError("given key points: K must lie in [1, %d] and every coordinate must be finite with |x|, |y|, |z| <= %g m"
+                         % (MAX_K, _ffi.GIVEN_KEYPTS_RANGE))
     if st & ST_COL_OOB:
         raise IndexError("index 1800 is out of bounds for axis 1 with size 1800")  # SphericalRing.py:91
     if st & ST_VOXEL_OOB:
@@ -54,10 +58,20 @@ def raise_status(st):
         raise _ffi.CaeloError("voxel map overflow")
 
 
-def extract_mode(exact_voxels=False, dedup=True, exact_patches=False):
+def extract_mode(exact_voxels=False, dedup=True, exact_patches=False, given_keypts=False, given_rows=False):
     """The CAELO_EXTRACT_* mode word of caelo_extract / caelo_frame_job."""
+    if given_rows:
+        return _ffi.EXTRACT_GIVEN_ROWS
     return ((_ffi.EXTRACT_EXACT_VOXELS if exact_voxels else 0) | (0 if dedup else _ffi.EXTRACT_NO_DEDUP)
-            | (_ffi.EXTRACT_EXACT_PATCHES if exact_patches else 0))
+            | (_ffi.EXTRACT_EXACT_PATCHES if exact_patches else 0) | (_ffi.EXTRACT_GIVEN_KEYPTS if given_keypts else 0))
+
+
+def _given_pts(eng, key_pts):
+    """A caller's key points as a [K,3] f32 tensor on the engine's device (K is checked on the device: CAELO_ST_BAD_KEYPTS)."""
+    t = key_pts if isinstance(key_pts, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(key_pts, dtype=np.float32))
+    t = t.to(device=eng.device, dtype=torch.float32)
+    assert t.dim() == 2 and t.shape[1] == 3, "key points: [K, 3]"
+    return t
 
 
 def note_ties_left(eng, st):
@@ -266,7 +280,7 @@ class Pipeline:
         _ffi.check(self.eng.lib.caelo_pipeline_sync_encoded(self.h, int(lag)))
 
     def run(self, scans, rands=None, prev=None, dist_channels=5, exact_voxels=False, out=None, pairs=True, dedup=True, on_batch=None,
-            on_encoded=None, certify=False, rands_host=None, publish=True, exact_patches=False):
+            on_encoded=None, certify=False, rands_host=None, publish=True, exact_patches=False, keypts=None, rows_given=None):
         """scans: K device tensors [n,4] f32; rands: K device tensors of RANSAC draws ([1500,4] f64).
         Frame i is matched against frame i-1 (pose in ``result[i]``); frame 0 against ``prev``
         (FrameFeatures) when given; ``pairs=False`` extracts only (BASELINE configs[1]).  Returns a FrameBatch; the
@@ -284,20 +298,30 @@ class Pipeline:
         ``on_batch(lo, hi)`` is called right after frames [lo, hi) have been issued (with ``wait_encoded`` the device-side form of
         the same hand-over, which costs the pipeline a quarter of its rate: DESIGN.md 6).  ``exact_patches=True``: the reference's
         patches (caelo_extract's CAELO_EXTRACT_EXACT_PATCHES) -- tie-split patches are redone on the device inside the run, so the
-        descriptors, matches and RANSAC results are the reference's with no host redo; ``out.status`` may carry ST_TIES_LEFT."""
+        descriptors, matches and RANSAC results are the reference's with no host redo; ``out.status`` may carry ST_TIES_LEFT.
+        Other key point sources, per frame (a frame with neither uses the detector, so runs may mix them; the pipeline splits a batch
+        where the kind changes, pairs chain across): ``keypts[i]`` = [K,3] f32 key points of frame i (CAELO_EXTRACT_GIVEN_KEYPTS, see
+        ``Engine.extract``); ``rows_given[i]`` = [K,64] f32 rows (descriptor zero-padded to columns 0:60 | xyz 60:63 | valid 63,
+        ``keysources.rows_from_features``) that are matched as they are (CAELO_EXTRACT_GIVEN_ROWS, isLoadFeaturesFromFile): no scan
+        needed (``scans[i]`` may be None), ``out.status[i]`` / ``flags[i]`` are zero and ``key_pixels[i]`` -1."""
         eng, lib, k = self.eng, self.eng.lib, len(scans)
         out = out or FrameBatch(eng, k)
         assert out.k >= k and (not pairs or len(rands) >= k)
         stream = eng.stream
+        modes = self._given(out, k, keypts, rows_given)
         per_batch = on_batch is not None or on_encoded is not None
         # an even batch plan for runs that are not whole batches (caelo.h); with a per-batch callback: full batches, remainder last
         _ffi.check(lib.caelo_pipeline_expect(self.h, 0 if per_batch else k))
         _ffi.check(lib.caelo_pipeline_begin(self.h, stream))
-        for pc in scans:
+        for i, pc in enumerate(scans):
+            if pc is None and modes is not None and modes[i] == 2:
+                continue
             assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         _t0 = time.perf_counter()
-        jobs = self._jobs([pc.data_ptr() for pc in scans], [pc.shape[0] for pc in scans], rands, prev, out, pairs, dist_channels,
-                          exact_voxels, dedup, certify, rands_host, exact_patches)
+        jobs = self._jobs([0 if pc is None else pc.data_ptr() for pc in scans], [0 if pc is None else pc.shape[0] for pc in scans], rands,
+                          prev, out, pairs, dist_channels, exact_voxels, dedup, certify, rands_host, exact_patches)
+        if modes is not None:
+            jobs["mode"] = np.where(modes == 1, jobs["mode"] | _ffi.EXTRACT_GIVEN_KEYPTS, np.where(modes == 2, _ffi.EXTRACT_GIVEN_ROWS, jobs["mode"]))
         _t1 = time.perf_counter()
         tail = None   # a partial last batch is only issued by the flush: its callbacks come after that
         issued = []   # batches issued, not yet reported to on_encoded
@@ -336,6 +360,35 @@ class Pipeline:
             raise _ffi.CaeloError("a pair holds more than 1024 matches: no certificate")
         self.last_times = {"jobs_ms": 1e3 * (_t1 - _t0), "submit_flush_ms": 1e3 * (_t2 - _t1), "publish_ms": 1e3 * (time.perf_counter() - _t2)}
         return out
+
+    def _given(self, out, k, keypts, rows_given):
+        """Pipeline.run's other key point sources: their inputs written into ``out`` (on the current stream, which the pipeline's
+        stages wait for) -> per-frame kind [k] (0 detector, 1 given key points, 2 given rows), or None when every frame uses the detector."""
+        if keypts is None and rows_given is None:
+            return None
+        modes = np.zeros(k, dtype=np.int32)
+        counts = np.zeros(k, dtype=np.int32)
+        for i in range(k):
+            kp = keypts[i] if keypts is not None else None
+            rw = rows_given[i] if rows_given is not None else None
+            assert kp is None or rw is None, "frame %d: key points and rows given" % i
+            if kp is not None:
+                t = _given_pts(self.eng, kp)
+                out.rows[i, :min(t.shape[0], MAX_K), 60:63] = t[:MAX_K]
+                modes[i], counts[i] = 1, t.shape[0]
+            elif rw is not None:
+                t = rw if isinstance(rw, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(rw, dtype=np.float32))
+                assert t.dim() == 2 and t.shape[1] == 64 and 1 <= t.shape[0] <= MAX_K, "given rows: [K, 64] with K in [1, 1024]"
+                out.rows[i].zero_()
+                out.rows[i, :t.shape[0]] = t.to(device=self.eng.device, dtype=torch.float32)
+                out.status[i].zero_()
+                out.flags[i].zero_()
+                out.key_pixels[i].fill_(-1)
+                modes[i], counts[i] = 2, t.shape[0]
+        if modes.any():   # (one copy for all the counts; the detector's frames get theirs from the device)
+            sel = torch.from_numpy(np.nonzero(modes)[0]).to(self.eng.device)
+            out.n_key[:k].index_copy_(0, sel, torch.from_numpy(counts[modes != 0]).to(self.eng.device))
+        return modes
 
     def _publish_exact(self, out, k, certify, pairs):
         """After the flush of a certified run: the certifier thread has written every exact result (caelo_pipeline_flush waits
@@ -1060,7 +1113,7 @@ class Engine:
         return _ffi.PoseResult.from_buffer_copy(res.cpu().numpy().tobytes())
 
     # ---- fused hot path ------------------------------------------------------------------------------
-    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True, exact_patches=False):
+    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True, exact_patches=False, key_pts=None):
         """scan [N,4] f32 (device) -> FrameFeatures, ONE C-ABI call (caelo_extract), no host sync:
         project -> response CNN -> keypoints -> voxelize -> patch gather -> 3x encoder.
         dist_channels: 5 = demo calling mode (SphericalRing.py:414), 3 = batch mode
@@ -1071,7 +1124,10 @@ class Engine:
         every patch even when it is a bit-identical copy of another one of the frame (same result, more work).
         ``exact_patches=True``: GetPatchesList's patches where the 496-nearest cut splits a class of equidistant voxels too (the
         canonical rule's patches are redone on the device in the library's order before the encoder runs, flags & 4) -- what
-        ``extract`` + ``resolve_ties`` give, in the same single call.  ``status[0]`` may carry ST_TIES_LEFT (see ``note_ties_left``)."""
+        ``extract`` + ``resolve_ties`` give, in the same single call.  ``status[0]`` may carry ST_TIES_LEFT (see ``note_ties_left``).
+        ``key_pts``: [K,3] f32 key points of another source (CAELO_EXTRACT_GIVEN_KEYPTS: GetPatchesList + GetFeaturesFromPatches on
+        them, PoseEstimation.py:26-45) instead of the detector's; K in [1, 1024] and |x|, |y|, |z| <= 16384 m, checked on the device
+        (``status[0]`` & ST_BAD_KEYPTS, raised by ``raise_status`` as ValueError).  ``key_pixels`` are then -1."""
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
         vmap = vmap or self.voxmap(max(self.max_points, pc.shape[0]))
@@ -1079,11 +1135,15 @@ class Engine:
         assert rows.shape == (MAX_K, 64) and rows.is_contiguous()
         kpix = self.empty((MAX_K, 2), torch.int64)
         nkey = self.empty((1,), torch.int32)
+        if key_pts is not None:   # (more than 1024 rows: the first 1024 are copied, the count tells the device to refuse them)
+            kp = _given_pts(self, key_pts)
+            rows[:min(kp.shape[0], MAX_K), 60:63] = kp[:MAX_K]
+            nkey.fill_(kp.shape[0])
         flags = self.empty((MAX_K, 3), torch.uint8)
         status = self.empty((4,), torch.int32)
         base = rows.data_ptr()
         _ffi.check(self.lib.caelo_extract(self.ctx, vmap.h, _ptr(pc), pc.shape[0], dist_channels,
-                                          extract_mode(exact_voxels, dedup, exact_patches),
+                                          extract_mode(exact_voxels, dedup, exact_patches, key_pts is not None),
                                           C.c_void_p(base + 240), 64, C.c_void_p(base), 64, C.c_void_p(base + 252), 64,
                                           _ptr(kpix), _ptr(nkey), _ptr(flags), _ptr(status), _ptr(ws),
                                           self.stream))

@@ -148,6 +148,7 @@ int extract_check(const caelo_extract_args &a) {
     CAELO_REQUIRE(a.dist_channels == 5 || a.dist_channels == 3, "dist_channels must be 5 (demo mode) or 3 (batch mode)");
     CAELO_REQUIRE(a.kp_ld >= 3 && a.feat_ld >= 60, "bad leading dimension");
     CAELO_REQUIRE(((uintptr_t)a.status & 15u) == 0, "status must be a 16-byte aligned int32[4]");
+    CAELO_REQUIRE(!(a.mode & CAELO_EXTRACT_GIVEN_ROWS), "CAELO_EXTRACT_GIVEN_ROWS is a pipeline job mode (rows are given: nothing to extract)");
     if (a.n > a.map->max_points) {
         caelo_set_error("caelo_extract: %lld points exceed the map capacity %lld", (long long)a.n, (long long)a.map->max_points);
         return CAELO_ERR_CAPACITY;
@@ -156,6 +157,38 @@ int extract_check(const caelo_extract_args &a) {
 }
 
 int extract_front_launch(const caelo_extract_args &a, hipStream_t s) { return extract_front_set(&a, 1, s); }
+
+// CAELO_EXTRACT_GIVEN_KEYPTS: in place of the ring image -> response -> key point chain, the caller's key points are checked and the
+// columns the detector would have written are filled in.  One workgroup per frame (blockIdx.z): every thread reads *n_key before
+// thread 0 may replace an out-of-range count with 0, so that no later kernel (patches, match, RANSAC) ever sees K > 1024.
+__global__ void __launch_bounds__(256) k_given_keypts(const caelo_frame_set fs) {
+    const caelo_frame_dev &F = fs.f[blockIdx.z];
+    const int K = *F.n_key;
+    const bool k_ok = K >= 1 && K <= CAELO_MAX_KEYPTS;
+    const float lim = (float)CAELO_GIVEN_KEYPTS_RANGE;
+    bool bad = !k_ok;
+    for (int i = threadIdx.x; i < CAELO_MAX_KEYPTS; i += 256) {
+        const bool in = k_ok && i < K;
+        if (in) {
+            const float *p = F.key_pts + (size_t)F.kp_ld * i;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) bad = bad || !(fabsf(p[a]) <= lim);   // (NaN fails the comparison)
+        }
+        if (F.valid) F.valid[(size_t)F.valid_ld * i] = in ? 1.0f : 0.0f;
+        F.key_pixels[2 * i] = -1;
+        F.key_pixels[2 * i + 1] = -1;
+    }
+    if (__syncthreads_or(bad) && threadIdx.x == 0) {
+        atomicOr(F.status, CAELO_ST_BAD_KEYPTS);
+        if (!k_ok) *F.n_key = 0;
+    }
+}
+
+static int given_keypts_set(const caelo_frame_set &fs, hipStream_t s) {
+    k_given_keypts<<<dim3(1, 1, fs.n), 256, 0, s>>>(fs);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
 
 // The front halves of n frames (n <= CAELO_FB_MAX, one mode for all) with the launches of one: every kernel takes the
 // frame set and runs frame blockIdx.z.  Each frame brings its own voxel map and workspace.
@@ -166,6 +199,7 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     const bool exact_pat = (args[0].mode & CAELO_EXTRACT_EXACT_PATCHES) != 0;
     const bool exact_vox = exact_pat || (args[0].mode & CAELO_EXTRACT_EXACT_VOXELS) != 0;
     const bool dd = dedup_enabled(args[0].mode);
+    const bool given = (args[0].mode & CAELO_EXTRACT_GIVEN_KEYPTS) != 0;
     caelo_frame_set fs = {};
     fs.n = n;
     caelo_clear_list cl[CAELO_FB_MAX];
@@ -211,11 +245,15 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     else rc = vox_build_fast_set(maps, fs, sv);
     if (rc) return rc;
     if (s_vox) CAELO_HIP(hipEventRecord(ev_join, s_vox));
-    // ---- ring image, response, keypoints
-    if ((rc = ring_project_set(fs, s))) return rc;
-    // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
-    if ((rc = ring_respond_set(args[0].ctx, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52))) return rc;
-    if ((rc = ring_keypoints_set(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W, s))) return rc;
+    // ---- ring image, response, keypoints (or the caller's key points, checked)
+    if (given) {
+        if ((rc = given_keypts_set(fs, s))) return rc;
+    } else {
+        if ((rc = ring_project_set(fs, s))) return rc;
+        // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
+        if ((rc = ring_respond_set(args[0].ctx, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52))) return rc;
+        if ((rc = ring_keypoints_set(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W, s))) return rc;
+    }
     if (s_vox) CAELO_HIP(hipStreamWaitEvent(s, ev_join, 0));
     // ---- patches
     // equal patches are encoded once (dedup.hip): k_patches enters every patch into the hash table, the tables land

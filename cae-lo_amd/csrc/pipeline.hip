@@ -305,9 +305,14 @@ int issue_batch_impl(caelo_pipeline *p) {
     const uint64_t k = p->n_batches;
     const int nb = (int)(k % (uint64_t)p->n_buffers);
     const std::vector<caelo_frame_job> &jobs = p->pending;
+    // CAELO_EXTRACT_GIVEN_ROWS (a batch holds one mode): the caller's rows are the descriptors -- no front, no encoder.  The two events
+    // are still recorded (on the idle stages' streams) so that the hand-off buffer rotation and the waits of later batches hold, and the
+    // pair stage still waits for enc_done: sE is serial, so that is the encoder of the batches before -- the rows a CAELO_PAIR_CHAIN job
+    // of this batch may be matched against.
+    const bool rows_given = (jobs[0].mode & CAELO_EXTRACT_GIVEN_ROWS) != 0;
     // every argument check comes before the first launch: a rejected batch leaves no trace (n_batches, events, buffers)
     caelo_extract_args xa[CAELO_FB_MAX];
-    for (int i = 0; i < n; ++i) {
+    for (int i = 0; i < n && !rows_given; ++i) {
         const caelo_frame_job &j = jobs[i];
         xa[i] = {p->ctx, p->maps[i], j.pc, j.n, j.dist_channels, j.mode, j.rows + 60, 64, j.rows, 64, j.rows + 63, 64,
                  j.key_pixels, j.n_key, j.flags, j.status, p->ws_extract[i],
@@ -317,9 +322,11 @@ int issue_batch_impl(caelo_pipeline *p) {
     }
     p->n_batches = k + 1;
     // ---- front: the hand-off buffer is free once the encoder of batch k - n_buffers has read it
-    if (k >= (uint64_t)p->n_buffers) CAELO_HIP(hipStreamWaitEvent(p->sF, p->enc_done[nb], 0));
-    int rc = extract_front_set(xa, n, p->sF, p->sV, p->vox_fork, p->vox_join);
-    if (rc) return rc;
+    int rc = CAELO_OK;
+    if (!rows_given) {
+        if (k >= (uint64_t)p->n_buffers) CAELO_HIP(hipStreamWaitEvent(p->sF, p->enc_done[nb], 0));
+        if ((rc = extract_front_set(xa, n, p->sF, p->sV, p->vox_fork, p->vox_join))) return rc;
+    }
     CAELO_HIP(hipEventRecord(p->front_done[nb], p->sF));
     // The certificates of the batches whose pair stage has long finished go to the host half HERE: the front stage of this batch is
     // queued (what the encoder waits for next -- between the pacing wait at the end of the previous call and these launches every
@@ -331,8 +338,8 @@ int issue_batch_impl(caelo_pipeline *p) {
     }
     const int64_t t1 = now_ns();
     // ---- encoder: one launch set for the batch; only the distinct patches of each frame are encoded
-    CAELO_HIP(hipStreamWaitEvent(p->sE, p->front_done[nb], 0));
-    {
+    if (!rows_given) {
+        CAELO_HIP(hipStreamWaitEvent(p->sE, p->front_done[nb], 0));
         caelo_enc_out outs;
         outs.per_frame = FRAME_PATCHES;
         for (int i = 0; i < n; ++i) outs.base[i] = jobs[i].rows;
@@ -713,8 +720,13 @@ CAELO_API int caelo_pipeline_expect(caelo_pipeline *p, int64_t n_frames) {
 
 CAELO_API int caelo_pipeline_submit(caelo_pipeline *p, const caelo_frame_job *job) {
     CAELO_REQUIRE(p && job, "null argument");
-    CAELO_REQUIRE(job->pc && job->rows && job->key_pixels && job->n_key && job->flags && job->status, "null frame buffer");
-    CAELO_REQUIRE(job->n > 3, "PC.shape[0] > 3 (SphericalRing.py:73)");
+    if (job->mode & CAELO_EXTRACT_GIVEN_ROWS) {   // the rows are the input: no scan, nothing extracted
+        CAELO_REQUIRE(job->rows && job->n_key, "null frame buffer");
+        CAELO_REQUIRE(!(job->mode & CAELO_EXTRACT_GIVEN_KEYPTS), "CAELO_EXTRACT_GIVEN_ROWS and CAELO_EXTRACT_GIVEN_KEYPTS exclude each other");
+    } else {
+        CAELO_REQUIRE(job->pc && job->rows && job->key_pixels && job->n_key && job->flags && job->status, "null frame buffer");
+        CAELO_REQUIRE(job->n > 3, "PC.shape[0] > 3 (SphericalRing.py:73)");
+    }
     CAELO_REQUIRE(job->pair >= CAELO_PAIR_NONE && job->pair <= CAELO_PAIR_EXPLICIT, "bad pair mode");
     if (job->pair != CAELO_PAIR_NONE)
         CAELO_REQUIRE(job->rand && job->result && job->inlier_mask && job->pair_idx, "null pair buffer");
@@ -725,7 +737,7 @@ CAELO_API int caelo_pipeline_submit(caelo_pipeline *p, const caelo_frame_job *jo
         caelo_set_error("caelo_pipeline_submit: the first job has no predecessor to chain to");
         return CAELO_ERR_ARG;
     }
-    if ((job->mode & CAELO_EXTRACT_EXACT_PATCHES) && !(p->maps[0]->xo_base && p->maps[0]->xo_frames >= p->batch)) {
+    if ((job->mode & CAELO_EXTRACT_EXACT_PATCHES) && !(job->mode & CAELO_EXTRACT_GIVEN_ROWS) && !(p->maps[0]->xo_base && p->maps[0]->xo_frames >= p->batch)) {
         // the first job in this mode: kd storage + ordering scratch of every frame slot's map, before any launch of its batch
         const int rc = exact_patches_prepare(p->maps, p->batch);
         if (rc) return rc;

@@ -284,14 +284,15 @@ struct VoxIdx {
     bool ok, oob, nonfinite;
 };
 
-// int(p / d) exactly as the reference's float64 division + truncation gives it (p >= 0, quotient < 1e4), without the division
-// for all but a few points: t = p * (1 / d) is within 3e-12 of the true quotient, and so is the correctly rounded p / d, so
+// int(p / d) exactly as the reference's float64 division + truncation toward zero gives it (NumPy's int32 cast, Voxel.py:185,:193;
+// |quotient| < 2^24, either sign: a given key point may lie off the voxel grid, CAELO_GIVEN_KEYPTS_RANGE), without the division for
+// all but a few points: t = p * (1 / d) is within 2^24 x 5e-16 < 1e-8 of the true quotient, and so is the correctly rounded p / d, so
 // whenever t sits further than 1e-6 from an integer both truncate alike; only a point within a micro-voxel of a voxel face (the
 // points that make a metrically quantised scan interesting, 14 of 126 k) pays for v_div_f64's ~40 instructions.
 __device__ inline int vox_trunc_div(double p, double d, double inv_d) {
     const double t = p * inv_d;
     const int n = (int)t;
-    const double frac = t - (double)n;
+    const double frac = fabs(t - (double)n);   // (t - n lies in (-1, 0] for t < 0)
     if (frac > 1e-6 && frac < 1.0 - 1e-6) return n;
     return (int)(p / d);
 }

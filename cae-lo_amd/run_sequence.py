@@ -49,7 +49,7 @@ def _parse_poses(raw, k):
 
 
 def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-              loader_threads=4, certify=True, native_ties=False):
+              loader_threads=4, certify=True, native_ties=False, given=None):
     """Frames [lo, hi) of this rank.  Returns per-pair rows for pairs (i-1, i), i in (lo, hi) -- the pair (lo-1, lo)
     is the caller's (it needs the previous rank's last frame) -- plus the first and last frame's features.
 
@@ -60,6 +60,9 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
       * the poses and status words of chunk c come back through pinned buffers on a side stream and are parsed after chunk
         c + 1 has been issued.
     ``native_ties``: the pipeline redoes tie-split patches itself (Pipeline.run_uploading(exact_patches=True)): no host redo, no re-match.
+    ``given(i)`` -> ('keypts', [K,3] f32) | ('rows', [K,64] f32): frame i's key points or rows of another source (PoseEstimation.py:26-66,
+    caelo.keysources); the chunk then goes through Pipeline.run on resident scans (keypts= / rows_given=), with the tie-split patches
+    redone inside the pipeline unless ``strict_ties`` is off.
     """
     import queue
     import threading
@@ -172,12 +175,21 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
         # certify: the exact RANSAC (the pipeline's certifier thread runs the host half on every pair while later batches are on the
         # GPU; the call returns when this chunk's inlier sets and poses -- the reference's bits -- are in batch.result / inlier_mask)
         dn_ = draws.numpy()
-        batch = pipe.run_uploading(scans, [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels,
-                                   certify=certify, rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None,
-                                   exact_patches=native_ties)
+        if given is not None:   # other key point sources: resident scans, the sources' inputs written into the batch by Pipeline.run
+            gv = [given(c0 + j) for j in range(c1 - c0)]
+            kp = [a if kind == "keypts" else None for kind, a in gv]
+            rw = [a if kind == "rows" else None for kind, a in gv]
+            batch = pipe.run([None if rw[j] is not None else scans[j].to(eng.device, non_blocking=True) for j in range(c1 - c0)],
+                             [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels, certify=certify,
+                             rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None, exact_patches=native_ties or strict_ties,
+                             keypts=kp, rows_given=rw)
+        else:
+            batch = pipe.run_uploading(scans, [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels,
+                                       certify=certify, rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None,
+                                       exact_patches=native_ties)
         ht["pipeline"] += time.time() - t_
         t_ = time.time()
-        if strict_ties and not native_ties:
+        if strict_ties and not native_ties and given is None:
             # Frames whose 496-nearest cut (Voxel.py:195-196) splits a class of equidistant voxels: the fused path's canonical rule is
             # replaced by scikit-learn's kd-tree order (Engine.resolve_ties: ordered voxel lists, all on the device), then the pairs
             # such a frame is part of are matched again.  One synchronisation per chunk; rare (none on KITTI-shaped scans).
@@ -397,10 +409,33 @@ def main():
                                                                "(CAELO_EXTRACT_EXACT_PATCHES): no host redo and re-match; same results")
     ap.add_argument("--no-certify", action="store_true", help="the kernels' own RANSAC results (float64 fits) without the host half that makes "
                                                               "inlier sets and poses the reference's bits (csrc/certify.hip)")
+    ap.add_argument("--keypts-source", default="ae", choices=("ae", "3dfeatnet", "usip"),
+                    help="key points of the pair loop (PoseEstimation.py iKeyPtSource 0 / 1 / 2): the auto-encoder detector, or the files "
+                         "<keypts-dir>/<frame:06d>.bin of 3DFeatNet ([-1, 35] f32) or USIP ([-1, 3] f32, rotated by R90; float32 after "
+                         "the rotation); at most 1024 per frame (larger sets: the staged API)")
+    ap.add_argument("--keypts-dir", help="directory of the --keypts-source files")
+    ap.add_argument("--features-from", help="directory of <frame:06d>.bin.mat files (KeyPts / Features / Weights, isLoadFeaturesFromFile, "
+                                            "PoseEstimation.py:49-66): only the pair stage runs on them")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
 
+    given = None
+    if args.keypts_source != "ae" or args.features_from:
+        if args.keypts_source != "ae" and args.features_from:
+            ap.error("--keypts-source and --features-from exclude each other")
+        if args.keypts_source != "ae" and not args.keypts_dir:
+            ap.error("--keypts-source %s needs --keypts-dir" % args.keypts_source)
+        if args.scans and not args.python_loader:
+            ap.error("--keypts-source / --features-from run on the Python loader path (add --python-loader): the native scan loader "
+                     "(caelo_seqloader) does not read key point or feature files")
+        from caelo import keysources
+
+        def given(i):
+            if args.features_from:
+                kp, feats, _ = keysources.load_features_dir(args.features_from, i)
+                return "rows", keysources.rows_from_features(kp, feats)
+            return "keypts", keysources.load_keypts(args.keypts_source, args.keypts_dir, i)
     world, rank, local_rank = cdist.ensure_ranks(args.gpus, os.path.abspath(__file__), sys.argv[1:])
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -486,7 +521,8 @@ def main():
     else:
         rel, ok, thr, nin, first, last = run_local(eng, load, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                    args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
-                                                   loader_threads=args.loader_threads, certify=not args.no_certify, native_ties=args.native_ties)
+                                                   loader_threads=args.loader_threads, certify=not args.no_certify, native_ties=args.native_ties,
+                                                   given=given)
     if tie_log:
         print("rank %d: %d frame(s) redone in scikit-learn's tie order (%d patches): %s" % (
             rank, len(tie_log), sum(n for _, n in tie_log), [f for f, _ in tie_log][:20]), file=sys.stderr)

@@ -61,6 +61,24 @@ typedef enum {
 #define CAELO_EXTRACT_EXACT_PATCHES 4 /* caelo_extract / caelo_frame_job.mode bit: GetPatchesList's patches on every input (see caelo_extract) */
 #define CAELO_ST_TIES_LEFT 64     /* CAELO_EXTRACT_EXACT_PATCHES only: a kd-tree build gave up on its pass budget and a tie-split patch was
                                    * left on the canonical rule (flags & 2 still set) */
+#define CAELO_EXTRACT_GIVEN_KEYPTS 8 /* caelo_extract / caelo_frame_job.mode bit: the CALLER's key points instead of the detector's (key point
+                                        sources other than GetKeyPtsByAE, PoseEstimation.py:26-45): on entry key_pts rows [0, K) hold them
+                                        (f32 xyz; in the pipeline rows[:, 60:63]) and *n_key = K in [1, 1024].  The ring image, response and
+                                        key point kernels are skipped; one kernel checks K and the coordinates, writes valid (1.0 below K, 0.0
+                                        from K on) and sets key_pixels to -1.  Voxel map, patches (CAELO_EXTRACT_EXACT_PATCHES included),
+                                        dedup and encoder run as usual; rows below K keep the caller's xyz bits.  No CAELO_ST_FEW_KEYPTS: the
+                                        reference asserts K > 50 only inside its own detector (SphericalRing.py:286) */
+#define CAELO_EXTRACT_GIVEN_ROWS 16  /* caelo_frame_job.mode bit only (isLoadFeaturesFromFile, PoseEstimation.py:49-66): rows [1024][64]
+                                        (descriptor zero-padded to columns 0:60 | xyz 60:63 | valid 63) and *n_key in [1, 1024] are INPUTS;
+                                        pc may be NULL.  The batch runs no front and no encoder work, only the pair stage; key_pixels, flags
+                                        and status are not written.  Zero padding leaves the float64 descriptor distances -- and so the
+                                        match's certified argmin -- unchanged: 32-d descriptors (3DFeatNet) are matched the same way */
+#define CAELO_ST_BAD_KEYPTS 128   /* CAELO_EXTRACT_GIVEN_KEYPTS only: K outside [1, 1024] (n_key is then set to 0), or a coordinate of a row
+                                   * below K that is not finite or whose magnitude exceeds CAELO_GIVEN_KEYPTS_RANGE.  A deviation: the
+                                   * reference raises nothing there (int32(nan) is INT_MIN and gives an empty patch) */
+#define CAELO_GIVEN_KEYPTS_RANGE 16384.0 /* metres: the accepted |x|, |y|, |z| of a given key point.  Within it every key voxel and patch brick
+                                          * index fits the 20-bit packing of the voxel tables (no aliasing), so a point off the scan or off
+                                          * the voxel grid -- negative side included -- gets exactly the reference's patch (empty far away) */
 
 typedef struct caelo_ctx caelo_ctx;
 typedef struct caelo_voxmap caelo_voxmap;
