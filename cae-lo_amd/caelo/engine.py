@@ -354,10 +354,7 @@ class Pipeline:
             for lo, hi in issued:
                 on_encoded(lo, hi)
         _t2 = time.perf_counter()
-        if publish:
-            self._publish_exact(out, k, certify, pairs)
-        elif certify and certify != "device" and pairs and k > 0 and (out.exact[3][:k] == 2).any():
-            raise _ffi.CaeloError("a pair holds more than 1024 matches: no certificate")
+        self._finish_exact(out, k, certify, pairs, publish)
         self.last_times = {"jobs_ms": 1e3 * (_t1 - _t0), "submit_flush_ms": 1e3 * (_t2 - _t1), "publish_ms": 1e3 * (time.perf_counter() - _t2)}
         return out
 
@@ -390,9 +387,10 @@ class Pipeline:
             out.n_key[:k].index_copy_(0, sel, torch.from_numpy(counts[modes != 0]).to(self.eng.device))
         return modes
 
-    def _publish_exact(self, out, k, certify, pairs):
+    def _finish_exact(self, out, k, certify, pairs, publish=True):
         """After the flush of a certified run: the certifier thread has written every exact result (caelo_pipeline_flush waits
-        for it); put them into the device tensors too."""
+        for it).  Check that every pair came back exact; with ``publish``, put the results into the device tensors too (without,
+        they stay in ``out.exact``, where the caller reads them).  Host arrays only: no device read."""
         if not (certify and certify != "device" and pairs and k > 0):
             return
         res, masks, evals, status = out.exact
@@ -402,6 +400,8 @@ class Pipeline:
         if has is not None and (status[:k][has[:k]] != 0).any():   # (the flush reports it too: a job WITH a pair must come back exact)
             bad = np.flatnonzero(has[:k] & (status[:k] != 0))
             raise _ffi.CaeloError("pairs of frames %s came back without an exact result (status %s)" % (bad.tolist(), status[:k][bad].tolist()))
+        if not publish:
+            return
         ok = status[:k] == 0
         if ok.any():
             with torch.cuda.stream(torch.cuda.current_stream(self.eng.device)):
@@ -517,7 +517,7 @@ class Pipeline:
             _ffi.check(lib.caelo_pipeline_run_uploading(self.h, C.c_void_p(jobs.ctypes.data), k, nb, None, 0, C.c_void_p(dstb.ctypes.data),
                                                         C.c_void_p(srcb.ctypes.data), C.c_void_p(one_n.ctypes.data), slots, None, 0, int(ahead), copy_h, stream, tns))
             tf1_ = time.perf_counter()
-            self._publish_exact(out, k, certify, pairs)
+            self._finish_exact(out, k, certify, pairs)
             self.last_upload_times = dict(wait_arrival_ms=tns[1] / 1e6, submit_ms=tns[2] / 1e6, upload_issue_and_wait_encoded_ms=tns[3] / 1e6, native_loop_ms=1e3 * (tf1_ - tf0_),
                                           publish_ms=1e3 * (time.perf_counter() - tf1_), prepare_ms=1e3 * (tf0_ - te0_))
             return out
@@ -553,10 +553,56 @@ class Pipeline:
             lib.caelo_pipeline_set_pace(self.h, pace)
         _ffi.check(rc)
         tf1_ = time.perf_counter()
-        self._publish_exact(out, k, certify, pairs)
+        self._finish_exact(out, k, certify, pairs)
         self.last_upload_times['copy_call_us'] = [round(x) for x in up_calls[:40]]
         self.last_upload_times.update(flush_ms=1e3 * (tf1_ - tf0_), publish_ms=1e3 * (time.perf_counter() - tf1_), prepare_ms=1e3 * (te1_ - te0_), begin_ms=1e3 * (te2_ - te1_))
         return out
+
+    def run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_channels=5, dedup=True, certify=True, ahead=4, publish=True,
+                   exact_patches=False):
+        """Batches [b0, b0 + nb) of a SeqLoader through the pipeline: a batch's scans AND draws go up behind ONE copy command (the loader's
+        slot layout, mirrored on the device), the jobs are built column-wise for the whole call, and nothing here is per-frame Python.
+        Paced like ``run_uploading`` (the copies go out before the thread waits for the encoder).  ``exact_patches``: as in ``Pipeline.run``.
+        -> (FrameBatch, frames)."""
+        eng, lib, B = self.eng, self.eng.lib, self.batch
+        assert loader.batch == B and ahead >= 1 and b0 + nb <= loader.n_batches
+        k = min(loader.n - b0 * B, nb * B)
+        out = out or FrameBatch(eng, k)
+        assert out.k >= k
+        slots = ahead + 2
+        key = ("loaded", B, slots, loader.slot_bytes)
+        st = getattr(self, "_loaded", {}).get(key)
+        if st is None:
+            st = ([torch.empty((loader.slot_bytes,), dtype=torch.uint8, device=eng.device) for _ in range(slots)], torch.cuda.Stream(device=eng.device))
+            self._loaded = {key: st}
+        dslots, copy = st
+        f = np.arange(k, dtype=np.uint64)
+        lb, j = f // B, f % B                                # local batch, frame within it
+        base = np.array([d.data_ptr() for d in dslots], dtype=np.uint64)[((b0 + lb.astype(np.int64)) % slots)]
+        pcs = base + j * np.uint64(loader.cap * 16)
+        rnd = base + np.uint64(loader.scan_bytes) + j * np.uint64(6000 * 8)
+        rnd_h = np.uint64(loader.keep_h.ctypes.data) + (((b0 + lb) % np.uint64(loader.keep_n)) * np.uint64(B) + j) * np.uint64(6000 * 8)
+        if not getattr(eng, "_blas_bound", False) and certify:
+            eng.host_blas()
+            eng._blas_bound = True
+        tj0_ = time.perf_counter()
+        jobs = self._jobs(pcs, np.zeros(k, np.int64), rnd, prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None,
+                          exact_patches)
+        tj1_ = time.perf_counter()
+        stream = eng.stream
+        # the whole paced loop natively (caelo_pipeline_run_uploading: wait for a batch's arrival, submit it, queue the copy `ahead` further
+        # on, stay one batch behind the encoder) -- from Python the ~60 us between the pacing wait and the next front launches cost 20 %
+        dst = (C.c_void_p * slots)(*[d.data_ptr() for d in dslots])
+        tns = (C.c_int64 * 4)()
+        tf0_ = time.perf_counter()
+        _ffi.check(lib.caelo_pipeline_run_uploading(self.h, C.c_void_p(jobs.ctypes.data), k, nb, loader.h, int(b0), dst, None, None, slots,
+                                                    C.c_void_p(loader.ring_h.data_ptr()), loader.slot_bytes, int(ahead), C.c_void_p(copy.cuda_stream), stream, tns))
+        tw = [tns[0] / 1e9, tns[1] / 1e9, tns[2] / 1e9, tns[3] / 1e9]
+        tf1_ = time.perf_counter()
+        self._finish_exact(out, k, certify, pairs, publish)
+        self.last_loaded_times = dict(starved_s=tw[0], wait_arrival_s=tw[1], submit_s=tw[2], upload_and_pace_s=tw[3], jobs_s=tj1_ - tj0_,
+                                      flush_s=tf1_ - tf0_, publish_s=time.perf_counter() - tf1_)
+        return out, k
 
 
 class SeqLoader:
@@ -604,62 +650,6 @@ class SeqLoader:
             self.close()
         except Exception:
             pass
-
-
-def _run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_channels=5, dedup=True, certify=True, ahead=4, publish=True,
-                exact_patches=False):
-    """Batches [b0, b0 + nb) of a SeqLoader through the pipeline: a batch's scans AND draws go up behind ONE copy command (the loader's
-    slot layout, mirrored on the device), the jobs are built column-wise for the whole call, and nothing here is per-frame Python.
-    Paced like ``run_uploading`` (the copies go out before the thread waits for the encoder).  ``exact_patches``: as in ``Pipeline.run``.
-    -> (FrameBatch, frames)."""
-    eng, lib, B = self.eng, self.eng.lib, self.batch
-    assert loader.batch == B and ahead >= 1 and b0 + nb <= loader.n_batches
-    k = min(loader.n - b0 * B, nb * B)
-    out = out or FrameBatch(eng, k)
-    assert out.k >= k
-    slots = ahead + 2
-    key = ("loaded", B, slots, loader.slot_bytes)
-    st = getattr(self, "_loaded", {}).get(key)
-    if st is None:
-        st = ([torch.empty((loader.slot_bytes,), dtype=torch.uint8, device=eng.device) for _ in range(slots)], torch.cuda.Stream(device=eng.device))
-        self._loaded = {key: st}
-    dslots, copy = st
-    f = np.arange(k, dtype=np.uint64)
-    lb, j = f // B, f % B                                # local batch, frame within it
-    base = np.array([d.data_ptr() for d in dslots], dtype=np.uint64)[((b0 + lb.astype(np.int64)) % slots)]
-    pcs = base + j * np.uint64(loader.cap * 16)
-    rnd = base + np.uint64(loader.scan_bytes) + j * np.uint64(6000 * 8)
-    rnd_h = np.uint64(loader.keep_h.ctypes.data) + (((b0 + lb) % np.uint64(loader.keep_n)) * np.uint64(B) + j) * np.uint64(6000 * 8)
-    if not getattr(eng, "_blas_bound", False) and certify:
-        eng.host_blas()
-        eng._blas_bound = True
-    tj0_ = time.perf_counter()
-    jobs = self._jobs(pcs, np.zeros(k, np.int64), rnd, prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None,
-                      exact_patches)
-    tj1_ = time.perf_counter()
-    stream = eng.stream
-    # the whole paced loop natively (caelo_pipeline_run_uploading: wait for a batch's arrival, submit it, queue the copy `ahead` further
-    # on, stay one batch behind the encoder) -- from Python the ~60 us between the pacing wait and the next front launches cost 20 %
-    dst = (C.c_void_p * slots)(*[d.data_ptr() for d in dslots])
-    tns = (C.c_int64 * 4)()
-    tf0_ = time.perf_counter()
-    _ffi.check(lib.caelo_pipeline_run_uploading(self.h, C.c_void_p(jobs.ctypes.data), k, nb, loader.h, int(b0), dst, None, None, slots,
-                                                C.c_void_p(loader.ring_h.data_ptr()), loader.slot_bytes, int(ahead), C.c_void_p(copy.cuda_stream), stream, tns))
-    tw = [tns[0] / 1e9, tns[1] / 1e9, tns[2] / 1e9, tns[3] / 1e9]
-    tf1_ = time.perf_counter()
-    if publish:
-        self._publish_exact(out, k, certify, pairs)
-    elif certify and pairs and k > 0:   # (the exact results stay on the host, where the caller reads them: out.exact)
-        has = getattr(out, "_has_pair", None)
-        st_ = out.exact[3][:k]
-        if (st_ == 2).any() or (has is not None and (st_[has[:k]] != 0).any()):
-            raise _ffi.CaeloError("pairs of frames %s came back without an exact result" % np.flatnonzero(st_ != 0).tolist()[:8])
-    self.last_loaded_times = dict(starved_s=tw[0], wait_arrival_s=tw[1], submit_s=tw[2], upload_and_pace_s=tw[3], jobs_s=tj1_ - tj0_,
-                                  flush_s=tf1_ - tf0_, publish_s=time.perf_counter() - tf1_)
-    return out, k
-
-
-Pipeline.run_loaded = _run_loaded
 
 
 class Engine:
@@ -1288,6 +1278,39 @@ class Engine:
         if (status != 0).any():
             raise _ffi.CaeloError("pairs %s could not be certified (status %s)" % (np.flatnonzero(status != 0).tolist(), status[status != 0].tolist()))
         return results, masks, idxs
+
+    def redo_ties(self, batch, k, scan, draws, prev=None, certify=True):
+        """The host redo of a strict-ties run: frames 0 .. k - 1 of ``batch`` (just returned by a pipeline) whose 496-nearest cut
+        (Voxel.py:195-196) split a class of equidistant voxels are redone in scikit-learn's kd-tree order (``resolve_ties_many``), then
+        the pairs (j - 1, j) such a frame is part of are matched again -- (-1, 0) against ``prev`` when given -- with
+        ``match_pose_exact_many`` (``certify``) or ``match_pose``.  ``scan(j)`` -> frame j's scan (device tensor), asked for a tied frame
+        only; ``draws(j)`` -> pair j's RANSAC draws (device tensor, host float64 array).  The new results go wherever the run's results
+        live: ``result`` / ``inlier_mask`` / ``pair_idx`` on the device and ``batch.exact`` when the run has one.  One host read when
+        no frame is tied (the usual case: none on KITTI-shaped scans).  -> (indices of the redone frames, their tie-split patches)."""
+        if not bool((batch.flags[:k] & 2).any().item()):
+            return [], []
+        tied_frames = (batch.flags[:k] & 2).reshape(k, -1).any(dim=1).cpu().numpy()
+        tied, counts = self.resolve_ties_many([(batch.frame(j), scan(j) if tied_frames[j] else None) for j in range(k)], batch=batch)
+        redo = sorted({t for u in tied for t in (u, u + 1) if t < k and (t > 0 or prev is not None)})
+        if not redo:
+            return tied, counts
+        pairs = [(prev if j == 0 else batch.frame(j - 1), batch.frame(j)) for j in redo]
+        rands, rands_host = zip(*[draws(j) for j in redo])
+        if certify:
+            rs, ms, xs = self.match_pose_exact_many(pairs, rands, rands_host)
+            sel = torch.tensor(redo, device=self.device)
+            batch.result[sel] = torch.from_numpy(rs.view(np.uint8).reshape(len(redo), -1).copy()).to(self.device)
+            batch.inlier_mask[sel] = torch.from_numpy(ms).to(self.device)
+            for j, x in zip(redo, xs):
+                batch.pair_idx[j].copy_(x)
+            if batch.exact is not None:
+                batch.exact[0][redo] = rs
+                batch.exact[1][redo] = ms
+        else:
+            for j, (fa, fb), rand in zip(redo, pairs, rands):
+                r, m, x = self.match_pose(fa, fb, rand)
+                batch.result[j].copy_(r); batch.inlier_mask[j].copy_(m); batch.pair_idx[j].copy_(x)
+        return tied, counts
 
     def checked(self, ff, pc, dist_channels=5):
         """Synchronising status check of an extract() result: raises what the reference would raise."""

@@ -33,19 +33,95 @@ from caelo import dist as cdist  # noqa: E402
 from caelo.engine import Engine, FrameBatch, FrameFeatures, note_ties_left, raise_status, ransac_draws  # noqa: E402
 
 
-def pose_rows(batch, k):
-    """FrameBatch.result -> numpy: rel_rt [k,12], success, threshold, n_inliers (one host copy)."""
-    return _parse_poses(batch.result[:k].cpu().numpy(), k)
+def _host_times(host_times):
+    ht = host_times if host_times is not None else {}   # seconds per host activity (what a "frames/s incl. loading" figure is made of)
+    for k_ in ("load", "pin", "draws", "starved", "pipeline", "ties", "parse", "setup"):
+        ht.setdefault(k_, 0.0)
+    return ht
 
 
 def _parse_poses(raw, k):
-    out = np.zeros((k, 12), np.float32)
-    ok = np.zeros(k, bool); thr = np.zeros(k, np.float32); nin = np.zeros(k, np.int32)
-    for i in range(k):
-        r = _ffi.PoseResult.from_buffer_copy(raw[i].tobytes())
-        out[i, :9], out[i, 9:] = np.array(r.R, np.float32), np.array(r.T, np.float32)
-        ok[i], thr[i], nin[i] = bool(r.success), r.threshold, r.n_inliers
-    return out, ok, thr, nin
+    """Pose results without per-frame Python: the raw bytes viewed as the record type of caelo_pose_result -> rel_rt [k,12],
+    success, threshold, n_inliers."""
+    r = np.frombuffer(raw[:k].tobytes(), dtype=_ffi.POSE_DTYPE, count=k)
+    out = np.concatenate([r["R"].reshape(k, 9), r["T"].reshape(k, 3)], axis=1).astype(np.float32)
+    return out, r["success"] != 0, r["threshold"].astype(np.float32), r["n_inliers"].astype(np.int32)
+
+
+def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_log, certify):
+    """The chunk loop of run_local and run_local_files: frames [lo, hi) in chunks of ``chunk``.  ``submit(ci, c0, c1, prev)`` issues
+    chunk ci = frames [c0, c1) (frame c0 matched against ``prev``) -> (FrameBatch, exact_on_host, scan(j), draws(j)): with
+    ``exact_on_host`` the certified poses are read from ``batch.exact`` (Pipeline.run_loaded(publish=False)), else from the device;
+    ``scan`` and ``draws`` fetch a tied frame's scan and a pair's draws again for the host redo (Engine.redo_ties).
+    The poses and status words of chunk c come back through pinned buffers on a side stream and are parsed after chunk c + 1 has
+    been issued.  Returns what run_local returns."""
+    import gc
+    gc.collect()
+    gc.freeze()       # what exists now is never scanned again: a full collection of this process (40-90 ms) no longer lands between two batches
+    side = torch.cuda.Stream(device=eng.device)
+    ht["setup"] = time.time() - t_setup
+    rel, ok, thr, nin = [], [], [], []
+    prev, first = None, None
+    pending = None   # (k, has_prev, host poses, pinned status, event)
+    back = []
+
+    def collect(p):
+        k, has_prev, res_h, st_h, ev = p
+        ev.synchronize()
+        t_ = time.time()
+        st = st_h.numpy()[:k, 0]
+        if st.any():
+            for v in st[st != 0]:
+                raise_status(int(v))
+            note_ties_left(eng, st)
+        r, o, t, n = _parse_poses(res_h, k)
+        s = 0 if has_prev else 1                                   # slot 0 of the first chunk has no predecessor here
+        rel.append(r[s:]); ok.append(o[s:]); thr.append(t[s:]); nin.append(n[s:])
+        ht["parse"] += time.time() - t_
+
+    t_loop = time.time()
+    for ci, c0 in enumerate(range(lo, hi, chunk)):
+        c1 = min(hi, c0 + chunk)
+        k = c1 - c0
+        batch, exact_on_host, scan, draws = submit(ci, c0, c1, prev)
+        t_ = time.time()
+        if host_redo:
+            # Frames whose 496-nearest cut (Voxel.py:195-196) splits a class of equidistant voxels: the fused path's canonical rule is
+            # replaced by scikit-learn's kd-tree order, then the pairs such a frame is part of are matched again.  One synchronisation
+            # per chunk; rare (none on KITTI-shaped scans).
+            tied, n_t = eng.redo_ties(batch, k, scan, draws, prev=prev, certify=certify)
+            if tie_log is not None:
+                tie_log.extend((c0 + j, n_) for j, n_ in zip(tied, n_t))
+        ht["ties"] += time.time() - t_
+        # read this chunk's small outputs back without stalling the stream that issues the next chunk
+        done = torch.cuda.Event()
+        done.record()
+        if not back:   # pinned read-back buffers, allocated once (three: one being parsed, one in flight, one being issued)
+            for _i in range(3):
+                back.append((torch.empty((min(chunk, hi - lo),) + tuple(batch.result.shape[1:]), dtype=batch.result.dtype, pin_memory=True),
+                             torch.empty((min(chunk, hi - lo),) + tuple(batch.status.shape[1:]), dtype=batch.status.dtype, pin_memory=True)))
+        res_h, st_h = back[ci % 3]
+        with torch.cuda.stream(side):
+            side.wait_event(done)
+            if not exact_on_host:
+                res_h[:k].copy_(batch.result[:k], non_blocking=True)
+            st_h[:k].copy_(batch.status[:k], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(side)
+        if pending is not None:
+            collect(pending)
+        pending = (k, prev is not None, batch.exact[0][:k].copy() if exact_on_host else res_h.numpy(), st_h, ev)
+        if first is None:
+            first = FrameFeatures.from_rows(batch.rows[0].clone())      # (a loader may reuse the chunk's buffers)
+        prev = FrameFeatures.from_rows(batch.rows[k - 1].clone())
+        if keep is not None:
+            keep(c0, batch.view(0, k))
+        del batch, scan, draws      # (back to the caching allocator before the next chunk asks for the same sizes)
+    ht["loop"] = time.time() - t_loop
+    if pending is not None:
+        collect(pending)
+    cat = (lambda xs, d: np.concatenate(xs) if xs else np.zeros((0,) + d))
+    return cat(rel, (12,)), cat(ok, ()), cat(thr, ()), cat(nin, ()), first, prev
 
 
 def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
@@ -67,6 +143,8 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
     import queue
     import threading
     t_setup = time.time()
+    if given is not None:
+        native_ties = native_ties or strict_ties
     chunks = [(c0, min(hi, c0 + chunk)) for c0 in range(lo, hi, chunk)]
     q = queue.Queue(maxsize=2)
 
@@ -80,9 +158,7 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
                 pinned[id(a)] = t
         return t
 
-    ht = host_times if host_times is not None else {}   # seconds per host activity (what a "frames/s incl. loading" figure is made of)
-    for k_ in ("load", "pin", "draws", "starved", "pipeline", "ties", "parse", "setup"):
-        ht.setdefault(k_, 0.0)
+    ht = _host_times(host_times)
 
     # The loader works with a few threads (file reads, NumPy's Mersenne Twister and the ray caster all release the GIL for most of
     # their time) and fills pinned buffers that are allocated once: a pinned allocation per chunk cost more than the copy it serves.
@@ -140,127 +216,46 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
     threading.Thread(target=loader, daemon=True).start()
     # (the loader is already at work on the first chunks while the pipeline's buffers are allocated)
     pipe = eng.pipeline(batch_frames)
-    import gc
-    gc.collect()
-    gc.freeze()       # what exists now is never scanned again: a full collection of this process (40-90 ms) no longer lands between two batches
-    side = torch.cuda.Stream(device=eng.device)
-    ht["setup"] = time.time() - t_setup
-    rel, ok, thr, nin = [], [], [], []
-    prev, first = None, None
-    pending = None   # (k, has_prev, pinned result, pinned status, event)
-    back_ring, n_back = [], 0
 
-    def collect(p):
-        k, has_prev, res_h, st_h, ev = p
-        ev.synchronize()
-        t_ = time.time()
-        for st in st_h.numpy()[:, 0]:
-            raise_status(int(st))
-        note_ties_left(eng, st_h.numpy()[:, 0])
-        r, o, t, n = _parse_poses(res_h.numpy(), k)
-        s = 0 if has_prev else 1                                   # slot 0 of the first chunk has no predecessor here
-        rel.append(r[s:]); ok.append(o[s:]); thr.append(t[s:]); nin.append(n[s:])
-        ht["parse"] += time.time() - t_
-
-    t_loop = time.time()
-    for _ in chunks:
+    def submit(ci, c0, c1, prev):
         t_ = time.time()
         item = q.get()
         ht["starved"] += time.time() - t_
         if isinstance(item, BaseException):
             raise item
-        c0, c1, scans, draws = item
+        _, _, scans, draws = item
         t_ = time.time()
+        k = c1 - c0
         draws_d = draws.to(eng.device, non_blocking=True)
         # certify: the exact RANSAC (the pipeline's certifier thread runs the host half on every pair while later batches are on the
         # GPU; the call returns when this chunk's inlier sets and poses -- the reference's bits -- are in batch.result / inlier_mask)
-        dn_ = draws.numpy()
+        dn = draws.numpy()
+        rands = [draws_d[i] for i in range(k)]
+        rands_host = [dn[i] for i in range(k)] if certify else None
         if given is not None:   # other key point sources: resident scans, the sources' inputs written into the batch by Pipeline.run
-            gv = [given(c0 + j) for j in range(c1 - c0)]
+            gv = [given(c0 + j) for j in range(k)]
             kp = [a if kind == "keypts" else None for kind, a in gv]
             rw = [a if kind == "rows" else None for kind, a in gv]
-            batch = pipe.run([None if rw[j] is not None else scans[j].to(eng.device, non_blocking=True) for j in range(c1 - c0)],
-                             [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels, certify=certify,
-                             rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None, exact_patches=native_ties or strict_ties,
-                             keypts=kp, rows_given=rw)
+            batch = pipe.run([None if rw[j] is not None else scans[j].to(eng.device, non_blocking=True) for j in range(k)], rands, prev=prev,
+                             dist_channels=dist_channels, certify=certify, rands_host=rands_host, exact_patches=native_ties, keypts=kp, rows_given=rw)
         else:
-            batch = pipe.run_uploading(scans, [draws_d[i] for i in range(c1 - c0)], prev=prev, dist_channels=dist_channels,
-                                       certify=certify, rands_host=[dn_[i] for i in range(c1 - c0)] if certify else None,
+            batch = pipe.run_uploading(scans, rands, prev=prev, dist_channels=dist_channels, certify=certify, rands_host=rands_host,
                                        exact_patches=native_ties)
         ht["pipeline"] += time.time() - t_
-        t_ = time.time()
-        if strict_ties and not native_ties and given is None:
-            # Frames whose 496-nearest cut (Voxel.py:195-196) splits a class of equidistant voxels: the fused path's canonical rule is
-            # replaced by scikit-learn's kd-tree order (Engine.resolve_ties: ordered voxel lists, all on the device), then the pairs
-            # such a frame is part of are matched again.  One synchronisation per chunk; rare (none on KITTI-shaped scans).
-            if bool((batch.flags[:c1 - c0] & 2).any().item()):
-                items = [(batch.frame(j), scans[j].to(eng.device)) for j in range(c1 - c0)]
-                tied, n_t = eng.resolve_ties_many(items, batch=batch)         # the redos overlap on side streams
-                if tie_log is not None:
-                    tie_log.extend((c0 + j, n_) for j, n_ in zip(tied, n_t))
-                redo = sorted({t for u in tied for t in (u, u + 1) if t < c1 - c0 and (t > 0 or prev is not None)})
-                pairs_ = [(prev if j == 0 else batch.frame(j - 1), batch.frame(j)) for j in redo]
-                if certify and redo:
-                    rs_, ms_, xs_ = eng.match_pose_exact_many(pairs_, [draws_d[j] for j in redo], [dn_[j] for j in redo])
-                    sel = torch.tensor(redo, device=eng.device)
-                    batch.result[sel] = torch.from_numpy(rs_.view(np.uint8).reshape(len(redo), -1).copy()).to(eng.device)
-                    batch.inlier_mask[sel] = torch.from_numpy(ms_).to(eng.device)
-                    for j, x_ in zip(redo, xs_):
-                        batch.pair_idx[j].copy_(x_)
-                else:
-                    for j, (fa_, fb_) in zip(redo, pairs_):
-                        r_, m_, x_ = eng.match_pose(fa_, fb_, draws_d[j])
-                        batch.result[j].copy_(r_); batch.inlier_mask[j].copy_(m_); batch.pair_idx[j].copy_(x_)
-        ht["ties"] += time.time() - t_
-        # read this chunk's small outputs back without stalling the stream that issues the next chunk
-        done = torch.cuda.Event()
-        done.record()
-        if not back_ring:   # pinned read-back buffers, allocated once (three: one being parsed, one in flight, one being issued)
-            for _i in range(3):
-                back_ring.append((torch.empty((min(chunk, hi - lo),) + tuple(batch.result.shape[1:]), dtype=batch.result.dtype, pin_memory=True),
-                                  torch.empty((min(chunk, hi - lo),) + tuple(batch.status.shape[1:]), dtype=batch.status.dtype, pin_memory=True)))
-        res_h, st_h = (t[:c1 - c0] for t in back_ring[n_back % 3])
-        n_back += 1
-        with torch.cuda.stream(side):
-            side.wait_event(done)
-            res_h.copy_(batch.result[:c1 - c0], non_blocking=True)
-            st_h.copy_(batch.status[:c1 - c0], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        if pending is not None:
-            collect(pending)
-        pending = (c1 - c0, prev is not None, res_h, st_h, ev)
-        if first is None:
-            first = batch.frame(0)
-        prev = batch.frame(c1 - c0 - 1)
-        if keep is not None:
-            keep(c0, batch)
-        del batch, item, scans      # (back to the caching allocator before the next chunk asks for the same sizes)
-    ht["loop"] = time.time() - t_loop
-    if pending is not None:
-        collect(pending)
-    cat = (lambda xs, d: np.concatenate(xs) if xs else np.zeros((0,) + d))
-    return cat(rel, (12,)), cat(ok, ()), cat(thr, ()), cat(nin, ()), first, prev
+        return batch, False, lambda j: scans[j].to(eng.device), lambda j: (draws_d[j], dn[j])
 
-
-def _parse_poses_fast(raw, k):
-    """_parse_poses without per-frame Python: the pinned read-back viewed as the record type of caelo_pose_result."""
-    r = np.frombuffer(raw[:k].tobytes(), dtype=_ffi.POSE_DTYPE, count=k)
-    out = np.concatenate([r["R"].reshape(k, 9), r["T"].reshape(k, 3)], axis=1).astype(np.float32)
-    return out, r["success"] != 0, r["threshold"].astype(np.float32), r["n_inliers"].astype(np.int32)
+    return _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify)
 
 
 def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
                     loader_threads=16, certify=True, device_results=False, native_ties=False):
     """run_local for scans that are FILES (round 6): the native loader (caelo_seqloader: pread into a pinned ring + the RANSAC draws,
     csrc/seqload.hip) works ahead on its own threads, a chunk of batches goes through Pipeline.run_loaded (one copy command per batch
-    for scans and draws, jobs built column-wise), results come back through pinned buffers and are parsed as one record array.
-    Same returns as run_local; same bits (the draws are NumPy's stream, the pipeline is the same)."""
+    for scans and draws, jobs built column-wise).  Same returns as run_local; same bits (the draws are NumPy's stream, the pipeline
+    is the same)."""
     from caelo.engine import SeqLoader
     t_setup = time.time()
-    ht = host_times if host_times is not None else {}
-    for k_ in ("load", "pin", "draws", "starved", "pipeline", "ties", "parse", "setup"):
-        ht.setdefault(k_, 0.0)
+    ht = _host_times(host_times)
     B = batch_frames
     # a ring slot holds the LARGEST scan of this rank's files, not the engine's capacity: a batch goes up as one copy of the whole slot, and
     # what the copy engine moves beside the pipeline is what the upload mode costs (20.5 MB per batch at 160 000 points, 16.2 MB at 126 k)
@@ -283,104 +278,35 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
     if "error" in box:
         raise box["error"]
     loader = box["loader"]
-    import gc
-    gc.collect()
-    gc.freeze()
-    side = torch.cuda.Stream(device=eng.device)
     per_chunk = max(1, chunk // B)
     outs = [FrameBatch(eng, per_chunk * B) for _ in range(2)]
-    back = [(torch.empty((per_chunk * B,) + tuple(outs[0].result.shape[1:]), dtype=outs[0].result.dtype, pin_memory=True),
-             torch.empty((per_chunk * B,) + tuple(outs[0].status.shape[1:]), dtype=outs[0].status.dtype, pin_memory=True)) for _ in range(3)]
-    ht["setup"] = time.time() - t_setup
-    rel, ok, thr, nin = [], [], [], []
-    prev, first, pending = None, None, None
+    # certified runs: the exact results are written by the host half into host arrays (batch.exact) -- they are read THERE, not
+    # published to the device and copied back (publish=False: 51 ms of 0.40 s for 4 541 frames)
+    # (device_results -- the artefact writer reads masks and pair indices from the device tensors -- publishes them as before)
+    publish = device_results or not certify
 
-    def collect(p):
-        k, has_prev, res_h, st_h, ev = p
-        ev.synchronize()
+    def submit(ci, c0, c1, prev):
         t_ = time.time()
-        st = st_h.numpy()[:k, 0]
-        if st.any():
-            for v in st[st != 0]:
-                raise_status(int(v))
-            note_ties_left(eng, st)
-        r, o, t, n = _parse_poses_fast(res_h if isinstance(res_h, np.ndarray) else res_h.numpy(), k)
-        s_ = 0 if has_prev else 1
-        rel.append(r[s_:]); ok.append(o[s_:]); thr.append(t[s_:]); nin.append(n[s_:])
-        ht["parse"] += time.time() - t_
-
-    t_loop = time.time()
-    for ci, b0 in enumerate(range(0, loader.n_batches, per_chunk)):
-        nb = min(per_chunk, loader.n_batches - b0)
-        t_ = time.time()
-        # certified runs: the exact results are written by the host half into host arrays (batch.exact) -- they are read THERE, not
-        # published to the device and copied back (publish=False: 51 ms of 0.40 s for 4 541 frames)
-        # (device_results -- the artefact writer reads masks and pair indices from the device tensors -- publishes them as before)
-        batch, k = pipe.run_loaded(loader, b0, nb, prev=prev, out=outs[ci % 2], dist_channels=dist_channels, certify=certify,
-                                   publish=device_results or not certify, exact_patches=native_ties)
-        host_res = batch.exact[0][:k].copy().view(np.uint8).reshape(k, -1) if certify else None
+        batch, _ = pipe.run_loaded(loader, (c0 - lo) // B, (c1 - c0 + B - 1) // B, prev=prev, out=outs[ci % 2], dist_channels=dist_channels,
+                                   certify=certify, publish=publish, exact_patches=native_ties)
         ht["pipeline"] += time.time() - t_
         ht["starved"] += pipe.last_loaded_times["starved_s"]
         for k_, v_ in pipe.last_loaded_times.items():
             ht["loaded_" + k_] = ht.get("loaded_" + k_, 0.0) + v_
-        c0 = lo + b0 * B
-        t_ = time.time()
-        if strict_ties and not native_ties and bool((batch.flags[:k] & 2).any().item()):
-            # (as run_local: the tied frames' scans are read again -- rare -- and redone in scikit-learn's kd-tree order, their pairs matched again)
-            fl = (batch.flags[:k] & 2).reshape(k, -1).any(dim=1).cpu().numpy()
-            items = [(batch.frame(j), torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device) if fl[j] else None) for j in range(k)]
-            tied, n_t = eng.resolve_ties_many(items, batch=batch)
-            if tie_log is not None:
-                tie_log.extend((c0 + j, n_) for j, n_ in zip(tied, n_t))
-            redo = sorted({t for u in tied for t in (u, u + 1) if t < k and (t > 0 or prev is not None)})
-            pairs_ = [(prev if j == 0 else batch.frame(j - 1), batch.frame(j)) for j in redo]
-            if redo:
-                dn_ = [np.frombuffer(_draws_of(seed_base + c0 + j - 1)) for j in redo]
-                dd_ = [torch.from_numpy(d_).to(eng.device) for d_ in dn_]
-                if certify:
-                    rs_, ms_, xs_ = eng.match_pose_exact_many(pairs_, dd_, dn_)
-                    host_res[redo] = rs_.view(np.uint8).reshape(len(redo), -1)
-                    if device_results:
-                        sel = torch.tensor(redo, device=eng.device)
-                        batch.inlier_mask[sel] = torch.from_numpy(ms_).to(eng.device)
-                        for j, x_ in zip(redo, xs_):
-                            batch.pair_idx[j].copy_(x_)
-                else:
-                    for j, (fa_, fb_), d_ in zip(redo, pairs_, dd_):
-                        r_, m_, x_ = eng.match_pose(fa_, fb_, d_)
-                        batch.result[j].copy_(r_); batch.inlier_mask[j].copy_(m_); batch.pair_idx[j].copy_(x_)
-        ht["ties"] += time.time() - t_
-        done = torch.cuda.Event()
-        done.record()
-        res_h, st_h = back[ci % 3]
-        with torch.cuda.stream(side):
-            side.wait_event(done)
-            if not certify:
-                res_h[:k].copy_(batch.result[:k], non_blocking=True)
-            st_h[:k].copy_(batch.status[:k], non_blocking=True)
-            ev = torch.cuda.Event()
-            ev.record(side)
-        if pending is not None:
-            collect(pending)
-        pending = (k, prev is not None, host_res if certify else res_h, st_h, ev)
-        if first is None:
-            first = FrameFeatures.from_rows(batch.rows[0].clone())      # (the chunk buffers are reused two chunks later)
-        last_rows = batch.rows[k - 1].clone()
-        prev = FrameFeatures.from_rows(last_rows)
-        if keep is not None:
-            keep(c0, batch.view(0, k))
-    ht["loop"] = time.time() - t_loop
-    if pending is not None:
-        collect(pending)
+
+        def scan(j):   # (a tied frame's scan is read again: rare)
+            return torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device)
+
+        def draws(j):
+            d = ransac_draws(seed_base + c0 + j - 1)
+            return torch.from_numpy(d).to(eng.device), d
+        return batch, not publish, scan, draws
+
+    out = _run_chunks(eng, lo, hi, per_chunk * B, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify)
     ls = loader.stats()
     ht["load"], ht["draws"] = ls["read_s"], ls["draws_s"]      # (summed over the loader's threads)
     loader.close()
-    cat = (lambda xs, d: np.concatenate(xs) if xs else np.zeros((0,) + d))
-    return cat(rel, (12,)), cat(ok, ()), cat(thr, ()), cat(nin, ()), first, prev
-
-
-def _draws_of(seed):
-    return ransac_draws(seed)
+    return out
 
 
 def main():
@@ -453,7 +379,7 @@ def main():
         def load(i):
             return stageio.read_scan(files[i])
 
-        def load_into(i, slot, pin):   # the file's bytes into a pinned slot [capacity, 4]; a scan larger than the slot goes the old way
+        def load_into(i, slot, pin):   # the file's bytes into a pinned slot [capacity, 4]; a scan larger than the slot is pinned on its own
             nbytes = os.path.getsize(files[i])
             if nbytes % 16 or nbytes // 16 > slot.shape[0]:
                 return pin(stageio.read_scan(files[i]))
@@ -462,8 +388,7 @@ def main():
                 got = f.readinto(memoryview(raw)[:nbytes])
             assert got == nbytes, "short read: %s" % files[i]
             return slot[:nbytes // 16]
-        if not os.environ.get("CAELO_RUN_NO_PINNED_RING"):   # (the old path, for comparisons)
-            load.into = load_into
+        load.into = load_into
     else:
         import threading
         cache, locks, guard = {}, {}, threading.Lock()
@@ -481,16 +406,6 @@ def main():
             return cache[i]
         load.repeats = args.pool > 1
 
-        def synth_into(i, slot, pin):   # a synthesised scan copied into its pinned ring slot (a batch's scans then go up in one copy)
-            a = load(i)
-            if a.shape[0] > slot.shape[0]:
-                return pin(a)
-            slot.numpy()[:a.shape[0]] = a
-            return slot[:a.shape[0]]
-        # opt-in: synthesising the scans is what bounds a synthetic run (1.5 of 2 s for 4 541 frames), and copying each into the ring
-        # costs the loader more (+0.25 s) than the single copy command per batch saves the pipeline calls (0.88 -> 0.58 s)
-        if os.environ.get("CAELO_RUN_SYNTH_RING"):
-            load.into = synth_into
         n = args.synthetic
         files = [os.path.join(os.path.dirname(os.path.abspath(args.out)), "synthetic", "velodyne", "%06d.bin" % i) for i in range(n)]
     assert n >= 2, "need at least two scans (--synthetic N or --scans DIR)"

@@ -78,25 +78,18 @@ def test_single_call_equals_extract_then_resolve_ties(engine, scans):
 
 @pytest.fixture(scope="module")
 def host_redo(engine, scans):
-    """The host-orchestrated reference of a pipeline run over clutter frames 20..27: run + resolve_ties_many + match_pose_exact_many on
-    the pairs that touch a redone frame."""
+    """The host-orchestrated reference of a pipeline run over clutter frames 20..27: run + Engine.redo_ties (resolve_ties_many +
+    match_pose_exact_many on the pairs that touch a redone frame)."""
     import torch
     from caelo.engine import ransac_draws
     pcs = _clutter(engine, scans)
     draws = [ransac_draws(70 + i) for i in CLUTTER]
     rnd = [torch.from_numpy(d).to(engine.device) for d in draws]
     a = engine.pipeline(4, 3).run(pcs, rnd, certify=True, rands_host=draws)
-    tied, _ = engine.resolve_ties_many([(a.frame(j), pcs[j]) for j in range(len(pcs))], batch=a)
+    tied, _ = engine.redo_ties(a, len(pcs), lambda j: pcs[j], lambda j: (rnd[j], draws[j]))
     assert 3 in tied
-    redo = sorted({t for u in tied for t in (u, u + 1) if 0 < t < len(pcs)})
-    rs, ms, xs = engine.match_pose_exact_many([(a.frame(j - 1), a.frame(j)) for j in redo], [rnd[j] for j in redo], [draws[j] for j in redo])
-    sel = torch.tensor(redo, device=engine.device)
-    a.result[sel] = torch.from_numpy(rs.view(np.uint8).reshape(len(redo), -1).copy()).to(engine.device)
-    a.inlier_mask[sel] = torch.from_numpy(ms).to(engine.device)
-    for q, j in enumerate(redo):
-        a.pair_idx[j].copy_(xs[q])
     torch.cuda.synchronize()
-    return dict(pcs=pcs, draws=draws, rnd=rnd, out=a, redo=redo)
+    return dict(pcs=pcs, draws=draws, rnd=rnd, out=a)
 
 
 def _assert_same_run(got, want, k):
@@ -175,9 +168,16 @@ def test_mixed_modes_on_one_pipeline(engine, scans):
         assert torch.equal(out.rows[j], want.rows[j]) and torch.equal(out.flags[j], want.flags[j]), "frame %d" % j
 
 
+def _run_sequence():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("run_sequence", os.path.join(REPO, "cae-lo_amd", "run_sequence.py"))
+    rs = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(rs)
+    return rs
+
+
 @pytest.mark.gpu
 def test_uploading_and_run_sequence_native_ties(engine, scans, host_redo):
-    import importlib.util
     import torch
     h = host_redo
     k = len(h["pcs"])
@@ -186,9 +186,7 @@ def test_uploading_and_run_sequence_native_ties(engine, scans, host_redo):
     e = pipe.run_uploading(host, h["rnd"], exact_patches=True, certify=True, rands_host=h["draws"])
     torch.cuda.synchronize()
     _assert_same_run(e, h["out"], k)
-    spec = importlib.util.spec_from_file_location("run_sequence", os.path.join(REPO, "cae-lo_amd", "run_sequence.py"))
-    rs = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(rs)
+    rs = _run_sequence()
 
     def load(i):
         return scans(i, quantum=1e-3, scene_kind="clutter")
@@ -198,3 +196,28 @@ def test_uploading_and_run_sequence_native_ties(engine, scans, host_redo):
     assert tie_log, "the strict path found no tied frame: the comparison shows nothing"
     for a, b in zip(strict[:4], native[:4]):
         assert np.array_equal(a, b)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("certify", [True, False])
+def test_run_sequence_file_loader_equals_the_python_loader_with_ties(engine, scans, tmp_path, certify):
+    """run_local_files (the native loader, the default for --scans) against run_local reading the same files: clutter frames with
+    tie-split patches, so that the host redo and the re-match run on both paths; a chunk boundary (chunk 8) and a partial last batch
+    (14 frames in batches of 4)."""
+    from caelo import stageio
+    rs = _run_sequence()
+    files = []
+    for i in range(16, 30):
+        files.append(str(tmp_path / ("%06d.bin" % i)))
+        scans(i, quantum=1e-3, scene_kind="clutter").astype(np.float32).tofile(files[-1])
+
+    def load(i):
+        return stageio.read_scan(files[i])
+    kw = dict(chunk=8, dist_channels=5, batch_frames=4, loader_threads=4, certify=certify)
+    log_files, log_python = [], []
+    native = rs.run_local_files(engine, files, 0, len(files), 500, tie_log=log_files, **kw)
+    python = rs.run_local(engine, load, 0, len(files), 500, tie_log=log_python, **kw)
+    assert log_files, "no tied frame: the comparison shows nothing"
+    assert log_files == log_python
+    for a, b in zip(native[:4], python[:4]):
+        assert a.dtype == b.dtype and a.shape == b.shape == (len(files) - 1,) + a.shape[1:] and a.tobytes() == b.tobytes()

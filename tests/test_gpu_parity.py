@@ -1391,14 +1391,12 @@ def test_run_sequence_from_files_equals_the_synthetic_run(tmp_path):
     a, b, c = str(tmp_path / "a.txt"), str(tmp_path / "b.txt"), str(tmp_path / "c.txt")
     subprocess.run([sys.executable, script, "--scans", str(d), "--chunk", "2", "--out", a], check=True, capture_output=True, timeout=300)
     subprocess.run([sys.executable, script, "--synthetic", "11", "--out", b], check=True, capture_output=True, timeout=300)
-    env = dict(os.environ, CAELO_RUN_NO_PINNED_RING="1")
-    subprocess.run([sys.executable, script, "--scans", str(d), "--chunk", "3", "--python-loader", "--out", c], check=True, capture_output=True, timeout=300, env=env)
+    subprocess.run([sys.executable, script, "--scans", str(d), "--chunk", "3", "--python-loader", "--out", c], check=True, capture_output=True, timeout=300)
     assert open(a).read() == open(b).read() == open(c).read() and len(open(a).read().splitlines()) == 11
-    # whole batches out of one pinned block: one copy command per batch (Pipeline.run_uploading finds the pitch), files and synthetic ring
+    # whole batches of files out of one pinned block: one copy command per batch (Pipeline.run_uploading finds the pitch)
     e, f = str(tmp_path / "e.txt"), str(tmp_path / "f.txt")
     subprocess.run([sys.executable, script, "--scans", str(d), "--chunk", "16", "--out", e], check=True, capture_output=True, timeout=300)
-    subprocess.run([sys.executable, script, "--synthetic", "11", "--chunk", "16", "--out", f], check=True, capture_output=True, timeout=300,
-                   env=dict(os.environ, CAELO_RUN_SYNTH_RING="1"))
+    subprocess.run([sys.executable, script, "--synthetic", "11", "--chunk", "16", "--out", f], check=True, capture_output=True, timeout=300)
     assert open(e).read() == open(f).read() == open(a).read()
     # round 6: --scans goes through the NATIVE loader by default (caelo_seqloader: pread + NumPy's MT19937 stream on native threads,
     # Pipeline.run_loaded); round 5's Python loader threads must give the same file, whole batches out of one pinned block included
@@ -1513,7 +1511,7 @@ def test_library_reads_no_arithmetic_switch_from_the_environment():
     for fn in os.listdir(tools):
         if fn.endswith((".py", ".sh")):
             used |= set(re.findall(r"\b(CAELO_[A-Z0-9_]+)\b", open(os.path.join(tools, fn)).read()))
-    python_side = {"CAELO_LIB", "CAELO_ENC_S1", "CAELO_DIST_BACKEND", "CAELO_ALLOW_PACKED_F32", "CAELO_RUN_NO_PINNED_RING", "CAELO_SOAK_TRAJECTORY"}
+    python_side = {"CAELO_LIB", "CAELO_ENC_S1", "CAELO_DIST_BACKEND", "CAELO_ALLOW_PACKED_F32", "CAELO_SOAK_TRAJECTORY"}
     assert used <= allowed | python_side, sorted(used - allowed - python_side)
 
 

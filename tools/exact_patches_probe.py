@@ -61,10 +61,7 @@ def rates(eng, clutter, n_boxes=256, rounds=3):
 
     def host_chunk(lo, hi):
         a = pipe.run(dcl[lo:hi], crnd[lo:hi], certify=True, rands_host=cdraws[lo:hi])
-        tied, _ = eng.resolve_ties_many([(a.frame(j), dcl[lo + j]) for j in range(hi - lo)], batch=a)
-        redo = sorted({t for u in tied for t in (u, u + 1) if 0 < t < hi - lo})
-        if redo:
-            eng.match_pose_exact_many([(a.frame(j - 1), a.frame(j)) for j in redo], [crnd[lo + j] for j in redo], [cdraws[lo + j] for j in redo])
+        tied, _ = eng.redo_ties(a, hi - lo, lambda j: dcl[lo + j], lambda j: (crnd[lo + j], cdraws[lo + j]))   # (as run_sequence.py runs it)
         return len(tied)
 
     def exact_chunk(lo, hi):
