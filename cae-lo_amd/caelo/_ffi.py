@@ -49,7 +49,7 @@ ST_TIES_LEFT = 64   # status bit of the EXTRACT_EXACT_PATCHES mode: a kd build g
 EXTRACT_GIVEN_KEYPTS, EXTRACT_GIVEN_ROWS = 8, 16   # the caller's key points (caelo_extract / jobs); the caller's rows (jobs only)
 ST_BAD_KEYPTS = 128   # status bit of EXTRACT_GIVEN_KEYPTS: K outside [1, 1024], or a coordinate non-finite or beyond GIVEN_KEYPTS_RANGE
 GIVEN_KEYPTS_RANGE = 16384.0   # metres, include/caelo.h CAELO_GIVEN_KEYPTS_RANGE
-ABI_VERSION = 5   # include/caelo.h CAELO_ABI_VERSION
+ABI_VERSION = 6   # include/caelo.h CAELO_ABI_VERSION
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 
 # the same layout as a NumPy record (a run's jobs are filled column-wise and handed over in one call)
@@ -136,14 +136,12 @@ SIGNATURES = [
     ("caelo_pipeline_submit", c_int, [c_vp, C.POINTER(FrameJob)]),
     ("caelo_pipeline_submit_many", c_int, [c_vp, c_vp, c_i64]),
     ("caelo_pipeline_flush", c_int, [c_vp, c_vp]),
-    ("caelo_pipeline_wait_stream", c_int, [c_vp, c_vp]),
-    ("caelo_pipeline_release_scans", c_int, [c_vp, c_vp]),
     ("caelo_pipeline_wait_encoded", c_int, [c_vp, c_vp]),
     ("caelo_pipeline_sync_encoded", c_int, [c_vp, c_int]),
     ("caelo_pipeline_set_pace", c_int, [c_vp, c_int]),
     ("caelo_pipeline_get_pace", c_int, [c_vp]),
     ("caelo_upload_many", c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
-    ("caelo_pipeline_run_uploading", c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
+    ("caelo_pipeline_run_uploading", c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     ("caelo_host_random_sample", c_int, [C.c_uint32, c_i64, c_vp]),
     ("caelo_seqloader_slot_bytes", c_i64, [c_int, c_i64]),
     ("caelo_seqloader_create", c_int, [c_vp, c_i64, c_i64, c_int, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_int, c_vp]),

@@ -29,7 +29,7 @@
 #include <vector>
 
 namespace {
-// Events that only order work of THIS device (stage hand-offs, the voxel stream's fork / join, the scans' arrival and release):
+// Events that only order work of THIS device (stage hand-offs, the voxel stream's fork / join):
 // no system-scope fence when they are recorded -- by default hipEventRecord writes the caches back and invalidates them so that
 // the host and other devices see the data, which nobody behind these events needs (CAELO_PIPE_SYSTEM_FENCES=1 restores it).
 // The events a caller's stream or the host waits on (caelo_pipeline_flush, caelo_pipeline_wait_encoded, and enc_done, which
@@ -63,12 +63,12 @@ struct caelo_pipeline {
     void *ws_match[CAELO_FB_MAX] = {nullptr}, *ws_ransac[CAELO_FB_MAX] = {nullptr};
     hipEvent_t front_done[MAX_BUFFERS] = {nullptr}, enc_done[MAX_BUFFERS] = {nullptr};
     hipEvent_t begun = nullptr, joined[3] = {nullptr};
-    // caelo_pipeline_wait_stream / _release_scans / _wait_encoded: a ring of events each, so that an event is not recorded again
-    // while a wait on its previous record may still sit in a queue
+    // caelo_pipeline_wait_encoded: a ring of events, so that an event is not recorded again while a wait on its previous record may
+    // still sit in a queue
     static constexpr int EXT_RING = 16;
-    hipEvent_t ext_in[EXT_RING] = {nullptr}, ext_out[EXT_RING] = {nullptr}, ext_enc[EXT_RING] = {nullptr};
+    hipEvent_t ext_enc[EXT_RING] = {nullptr};
+    unsigned n_ext_enc = 0;
     std::vector<hipEvent_t> up_arrived;   // caelo_pipeline_run_uploading: a batch's scans are in device memory
-    unsigned n_ext_in = 0, n_ext_out = 0, n_ext_enc = 0;
     // host state
     std::vector<caelo_frame_job> pending;
     uint64_t n_batches = 0, submitted = 0;
@@ -332,7 +332,7 @@ int issue_batch_impl(caelo_pipeline *p) {
     // queued (what the encoder waits for next -- between the pacing wait at the end of the previous call and these launches every
     // microsecond of the issuing thread is a microsecond of the batch), the rest of the call has slack.  All but the two newest
     // issued batches: the thread waited for the encoder of the batch before the newest at the end of the previous call (a caller
-    // that paces itself -- pace -1, Pipeline.run_uploading -- waits AFTER the call: one more batch of slack).
+    // that paces itself -- pace -1, caelo_pipeline_run_uploading -- waits AFTER the call: one more batch of slack).
     if (!p->cert_issued.empty()) {
         if ((rc = cert_drain(p, p->pace >= 0 ? 1 : 2))) return rc;
     }
@@ -470,9 +470,8 @@ CAELO_API void caelo_pipeline_destroy(caelo_pipeline *p) {
     for (hipEvent_t e : p->up_arrived) (void)hipEventDestroy(e);
     for (hipEvent_t e : {p->vox_fork, p->vox_join})
         if (e) (void)hipEventDestroy(e);
-    for (int i = 0; i < caelo_pipeline::EXT_RING; ++i)
-        for (hipEvent_t e : {p->ext_in[i], p->ext_out[i], p->ext_enc[i]})
-            if (e) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->ext_enc)
+        if (e) (void)hipEventDestroy(e);
     if (p->sV) (void)hipStreamDestroy(p->sV);
     if (p->sP && p->sP != p->sF) (void)hipStreamDestroy(p->sP);
     if (p->sE && p->sE != p->sF) (void)hipStreamDestroy(p->sE);
@@ -538,11 +537,7 @@ CAELO_API int caelo_pipeline_create(caelo_ctx *c, int batch, int n_buffers, int6
         }
     }
     hip_ok(hipEventCreateWithFlags(&p->begun, local_event_flags()), "hipEventCreate");
-    for (int i = 0; i < caelo_pipeline::EXT_RING; ++i) {
-        hip_ok(hipEventCreateWithFlags(&p->ext_in[i], local_event_flags()), "hipEventCreate");
-        hip_ok(hipEventCreateWithFlags(&p->ext_out[i], local_event_flags()), "hipEventCreate");
-        hip_ok(hipEventCreateWithFlags(&p->ext_enc[i], hipEventDisableTiming), "hipEventCreate");
-    }
+    for (hipEvent_t &e : p->ext_enc) hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     for (hipEvent_t &e : p->joined) hip_ok(hipEventCreateWithFlags(&e, hipEventDisableTiming), "hipEventCreate");
     for (int i = 0; i < n_buffers; ++i) {
         hip_ok(hipEventCreateWithFlags(&p->front_done[i], local_event_flags()), "hipEventCreate");
@@ -633,15 +628,22 @@ CAELO_API int caelo_upload_many(void *const *dst, const void *const *src, const 
 // batch's scans, submit it, queue the copy of the batch `ahead` further on, wait for the encoder of the batch before -- and between
 // that wait and the next batch's front launches sat ~60 us of interpreter (event objects, slices, ctypes), every one of them a
 // microsecond of the batch (the front stream started 81 us behind the encoder's stage 1 instead of 14: 15-16 k frames/s with uploads
-// against 19.9 k resident, profiles/r06_upload_native.txt).  One copy command per batch: batch b of the call (jobs [b * batch, ...)) goes
-// from src[b] to dst[b], bytes[b] -- or, with a loader (caelo_seqloader), from its ring slot to dev_slots[(b0 + b) % n_slots], the
+// against 19.9 k resident, profiles/r06_upload_native.txt).  Batch b of the call (jobs [b * batch, ...)) is uploaded by the entries
+// [copy_first[b], copy_first[b + 1]) of the copy table dst / src / bytes (one per batch when its scans lie in one block at a fixed
+// pitch, one per frame otherwise) -- or, with a loader (caelo_seqloader), from its ring slot to dev_slots[(b0 + b) % n_slots], the
 // point counts of the batch's jobs filled in from the loader.  Between caelo_pipeline_begin and the flush, both done here.
 CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *jobs, int64_t k, int64_t nb, caelo_seqloader *loader, int64_t b0,
-                                           void *const *dst, const void *const *src, const size_t *bytes, int n_slots, const void *ring_host,
-                                           int64_t slot_bytes, int ahead, void *copy_stream, void *stream, int64_t *times_ns_host) {
+                                           void *const *dst, const void *const *src, const size_t *bytes, const int64_t *copy_first, int n_slots,
+                                           const void *ring_host, int64_t slot_bytes, int ahead, void *copy_stream, void *stream, int64_t *times_ns_host) {
     CAELO_REQUIRE(p && jobs && k > 0 && nb > 0 && dst && ahead >= 1 && copy_stream, "caelo_pipeline_run_uploading: bad argument");
-    CAELO_REQUIRE(loader ? (n_slots >= ahead + 2 && ring_host && slot_bytes > 0) : (src && bytes), "caelo_pipeline_run_uploading: bad copy description");
+    CAELO_REQUIRE(loader ? (n_slots >= ahead + 2 && ring_host && slot_bytes > 0) : (src && bytes && copy_first), "caelo_pipeline_run_uploading: bad copy description");
     CAELO_REQUIRE((k + p->batch - 1) / p->batch == nb, "caelo_pipeline_run_uploading: k frames do not make nb batches");
+    if (!loader) {
+        CAELO_REQUIRE(copy_first[0] == 0, "copy_first[0] must be 0");
+        for (int64_t b = 0; b < nb; ++b)
+            CAELO_REQUIRE(copy_first[b + 1] >= copy_first[b] && copy_first[b + 1] - copy_first[b] <= INT32_MAX,
+                          "copy_first must not decrease");
+    }
     const int B = p->batch;
     hipStream_t copy = caelo_stream(copy_stream);
     const int n_ev = ahead + 2;
@@ -652,11 +654,8 @@ CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *j
     }
     int64_t tw[4] = {0, 0, 0, 0};
     auto upload = [&](int64_t b) -> int {
-        const int64_t lo = b * B, hi = lo + B < k ? lo + B : k;
-        void *d = dst[loader ? (b0 + b) % n_slots : b];
-        const void *sp;
-        size_t nbytes;
         if (loader) {
+            const int64_t lo = b * B, hi = lo + B < k ? lo + B : k;
             int32_t slot = 0;
             int64_t npts[CAELO_FB_MAX];
             const int64_t t0 = now_ns();
@@ -664,13 +663,13 @@ CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *j
             tw[0] += now_ns() - t0;
             if (rc) return rc;
             for (int64_t i = lo; i < hi; ++i) jobs[i].n = npts[i - lo];
-            sp = (const char *)ring_host + (size_t)slot * (size_t)slot_bytes;
-            nbytes = (size_t)slot_bytes;
+            CAELO_HIP(hipMemcpyAsync(dst[(b0 + b) % n_slots], (const char *)ring_host + (size_t)slot * (size_t)slot_bytes, (size_t)slot_bytes,
+                                     hipMemcpyHostToDevice, copy));
         } else {
-            sp = src[b];
-            nbytes = bytes[b];
+            const int64_t f = copy_first[b];
+            const int rc = caelo_upload_many(dst + f, src + f, bytes + f, (int)(copy_first[b + 1] - f), copy_stream);
+            if (rc) return rc;
         }
-        if (nbytes) CAELO_HIP(hipMemcpyAsync(d, sp, nbytes, hipMemcpyHostToDevice, copy));
         CAELO_HIP(hipEventRecord(p->up_arrived[(size_t)(b % n_ev)], copy));
         return CAELO_OK;
     };
@@ -776,27 +775,7 @@ CAELO_API int caelo_pipeline_submit_many(caelo_pipeline *p, const caelo_frame_jo
     return CAELO_OK;
 }
 
-// Scans that arrive while the pipeline runs (a copy stream uploading batch b + 1 during batch b, like the producer process of
-// PoseEstimation.py:214-245): the front stage of every batch submitted from now on starts after what `stream` holds now ...
-CAELO_API int caelo_pipeline_wait_stream(caelo_pipeline *p, void *stream) {
-    CAELO_REQUIRE(p, "null argument");
-    hipEvent_t e = p->ext_in[p->n_ext_in++ % caelo_pipeline::EXT_RING];
-    CAELO_HIP(hipEventRecord(e, caelo_stream(stream)));
-    CAELO_HIP(hipStreamWaitEvent(p->sF, e, 0));   // the voxel stream forks from sF inside every batch
-    return CAELO_OK;
-}
-
-// ... and `stream` may overwrite the scan buffers of every batch ISSUED so far once their front stages (the only readers of a
-// scan: projection, ring fill, voxel map) are done.
-CAELO_API int caelo_pipeline_release_scans(caelo_pipeline *p, void *stream) {
-    CAELO_REQUIRE(p, "null argument");
-    hipEvent_t e = p->ext_out[p->n_ext_out++ % caelo_pipeline::EXT_RING];
-    CAELO_HIP(hipEventRecord(e, p->sF));
-    CAELO_HIP(hipStreamWaitEvent(caelo_stream(stream), e, 0));
-    return CAELO_OK;
-}
-
-// ... and `stream` waits for the rows of every frame of the batches issued so far (the encoder stage writes descriptors, the front
+// Results that leave while the pipeline runs: `stream` waits for the rows of every frame of the batches issued so far (the encoder stage writes descriptors, the front
 // stage before it the key points and the validity column; the pair stage only reads them).
 CAELO_API int caelo_pipeline_wait_encoded(caelo_pipeline *p, void *stream) {
     CAELO_REQUIRE(p, "null argument");

@@ -290,9 +290,10 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
         batch, _ = pipe.run_loaded(loader, (c0 - lo) // B, (c1 - c0 + B - 1) // B, prev=prev, out=outs[ci % 2], dist_channels=dist_channels,
                                    certify=certify, publish=publish, exact_patches=native_ties)
         ht["pipeline"] += time.time() - t_
-        ht["starved"] += pipe.last_loaded_times["starved_s"]
-        for k_, v_ in pipe.last_loaded_times.items():
-            ht["loaded_" + k_] = ht.get("loaded_" + k_, 0.0) + v_
+        t = pipe.last_upload_times   # (ms; this report is in seconds)
+        ht["starved"] += t["starved_ms"] / 1e3
+        for k_, v_ in t.items():
+            ht["loaded_" + k_[:-3] + "_s"] = ht.get("loaded_" + k_[:-3] + "_s", 0.0) + v_ / 1e3
 
         def scan(j):   # (a tied frame's scan is read again: rare)
             return torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device)

@@ -23,7 +23,7 @@
 extern "C" {
 #endif
 
-#define CAELO_ABI_VERSION 5   /* 5: caelo_host_unbind_blas / _blas_probe / _bound_violations, caelo_host_random_sample, caelo_seqloader_*, caelo_patches_many, caelo_pipeline_run_uploading; 4: caelo_voxmap_export never waits for the device (a count above capacity is the overflow report), caelo_voxmap_order; 3: certificates, caelo_host_* */
+#define CAELO_ABI_VERSION 6   /* 6: caelo_pipeline_run_uploading takes a copy table (copy_first: the copies of each batch); the device-side waits of the input side (wait_stream, the release of scans) are removed; 5: caelo_host_unbind_blas / _blas_probe / _bound_violations, caelo_host_random_sample, caelo_seqloader_*, caelo_patches_many, caelo_pipeline_run_uploading; 4: caelo_voxmap_export never waits for the device (a count above capacity is the overflow report), caelo_voxmap_order; 3: certificates, caelo_host_* */
 
 /* geometry fixed by the reference: SphericalRing.py:28-58, Voxel.py:15-52 */
 #define CAELO_RING_H 69
@@ -462,13 +462,6 @@ int caelo_pipeline_submit(caelo_pipeline *pipe, const caelo_frame_job *job);
  * costly foreign-call path (ctypes: ~10 us per call) hands a whole run over at once -- the odometry loop of PoseEstimation.py:241-267. */
 int caelo_pipeline_submit_many(caelo_pipeline *pipe, const caelo_frame_job *jobs, int64_t n);
 int caelo_pipeline_flush(caelo_pipeline *pipe, void *stream);
-/* Scans that arrive while the pipeline runs -- the overlap of the reference's producer process, which prepares frame i + 1 while
- * frame i is matched (PoseEstimation.py:214-245).  caelo_pipeline_wait_stream: the front stage of every batch submitted from
- * now on starts after the work `stream` holds at this moment (the uploads of those scans).  caelo_pipeline_release_scans:
- * `stream` waits until the front stages of the batches issued so far are done -- nothing else reads a scan -- before it may
- * overwrite their buffers.  Both between caelo_pipeline_begin and caelo_pipeline_flush. */
-int caelo_pipeline_wait_stream(caelo_pipeline *p, void *stream);
-int caelo_pipeline_release_scans(caelo_pipeline *p, void *stream);
 /* Results that leave while the pipeline runs -- the sharded sequence's descriptor all-gather (PoseEstimation.py:241-251 needs the
  * previous frame's features wherever that frame was extracted): `stream` waits until the rows (descriptors | key points | valid)
  * of every frame of the batches ISSUED so far are written, and of nothing later -- a collective enqueued on `stream` then moves
@@ -485,21 +478,25 @@ int caelo_pipeline_sync_encoded(caelo_pipeline *p, int lag);
 int caelo_pipeline_set_pace(caelo_pipeline *p, int lag);
 int caelo_pipeline_get_pace(const caelo_pipeline *p);   /* the pacing in effect (the library's default until set) */
 /* n host -> device copies on `stream` behind one call (the scans of a batch that live in pinned host memory, the producer side of
- * PoseEstimation.py:214-245): dst[i] <- src[i], bytes[i] each, asynchronous like hipMemcpyAsync.  The pipeline does not take part --
- * the caller orders the copies against it (caelo_pipeline_wait_stream / an event of its own / caelo_pipeline_sync_encoded). */
+ * PoseEstimation.py:214-245): dst[i] <- src[i], bytes[i] each, asynchronous like hipMemcpyAsync; a null dst[i] or src[i] is an error,
+ * a zero bytes[i] is skipped.  The pipeline does not take part -- the caller orders the copies against it (an event of its own,
+ * caelo_pipeline_sync_encoded); caelo_pipeline_run_uploading issues each batch's copies through it. */
 int caelo_upload_many(void *const *dst, const void *const *src, const size_t *bytes, int n, void *stream);
 /* A whole run of the upload mode behind ONE call: jobs [k] (in nb batches of the pipeline's batch size, the remainder last) whose
- * scans arrive by ONE copy command per batch on `copy_stream`, `ahead` batches ahead of the batch being issued; the calling thread waits
- * for a batch's arrival, submits it, queues the next copy and paces itself one batch behind the encoder -- natively: the interpreter's
- * ~60 us between that wait and the next batch's front launches were 20 % of the rate.  Includes caelo_pipeline_begin and the flush.
- * Without a loader: batch b is copied from src[b] to dst[b], bytes[b] (host arrays of nb entries).  With one (caelo_seqloader, below):
+ * scans arrive on `copy_stream`, `ahead` batches ahead of the batch being issued; the calling thread waits for a batch's arrival,
+ * submits it, queues the next batch's copies and paces itself one batch behind the encoder -- natively: the interpreter's ~60 us
+ * between that wait and the next batch's front launches were 20 % of the rate.  Includes caelo_pipeline_begin and the flush (the
+ * pipeline's pacing is off during the call and restored after it).  Without a loader: a copy table -- batch b is uploaded by the
+ * entries [copy_first[b], copy_first[b + 1]) of dst / src / bytes (caelo_upload_many), copy_first [nb + 1] non-decreasing from 0:
+ * one entry per batch when a batch's scans lie in one block at a fixed pitch (one copy command per batch: several commands per batch
+ * cost a pipeline running beside them 20 %), one per frame otherwise.  With a loader (caelo_seqloader, below; copy_first unused):
  * batch b0 + b comes from its ring slot (ring_host, slot_bytes) into dst[(b0 + b) % n_slots] (n_slots >= ahead + 2 device slots of
  * slot_bytes), and the point counts of its jobs (job.n) are filled in from the loader, which gets its slot back as soon as the copy is
  * through.  times_ns_host (nullable) [4]: waiting for the loader / for arrivals, submitting, copy issue + pacing. */
 struct caelo_seqloader;
 int caelo_pipeline_run_uploading(caelo_pipeline *pipe, caelo_frame_job *jobs, int64_t k, int64_t nb, struct caelo_seqloader *loader, int64_t b0,
-                                 void *const *dst, const void *const *src, const size_t *bytes, int n_slots, const void *ring_host,
-                                 int64_t slot_bytes, int ahead, void *copy_stream, void *stream, int64_t *times_ns_host);
+                                 void *const *dst, const void *const *src, const size_t *bytes, const int64_t *copy_first, int n_slots,
+                                 const void *ring_host, int64_t slot_bytes, int ahead, void *copy_stream, void *stream, int64_t *times_ns_host);
 
 /* ---- a sequence from files (PoseEstimation.py:173-245: the generator process that prepares frame i + 1 while frame i is matched) ----
  * caelo_host_random_sample: numpy.random.RandomState(seed).random_sample(n) bit for bit (MT19937, init_genrand seeding, 53-bit doubles):

@@ -32,7 +32,7 @@ def test_new_bits_header_ffi_engine():
     assert int(d["CAELO_EXTRACT_GIVEN_ROWS"]) == 16 == _ffi.EXTRACT_GIVEN_ROWS
     assert int(d["CAELO_ST_BAD_KEYPTS"]) == 128 == _ffi.ST_BAD_KEYPTS == engine.ST_BAD_KEYPTS
     assert float(d["CAELO_GIVEN_KEYPTS_RANGE"]) == _ffi.GIVEN_KEYPTS_RANGE >= 10000.0
-    assert int(d["CAELO_ABI_VERSION"]) == 5
+    assert int(d["CAELO_ABI_VERSION"]) == 6
     others = [int(d[k]) for k in d if k.startswith("CAELO_ST_") and k != "CAELO_ST_BAD_KEYPTS"]
     assert 128 not in others and all(o & 128 == 0 for o in others)
     assert engine.extract_mode(given_keypts=True) == 8 and engine.extract_mode(exact_patches=True, given_keypts=True) == 12

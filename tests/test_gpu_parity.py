@@ -729,24 +729,64 @@ def test_pipeline_equals_single_stream_calls(engine, scans, batch, buffers):
 def test_pipeline_with_overlapped_uploads_equals_resident_scans(engine, scans):
     """Pipeline.run_uploading (scans in pinned host memory, a copy stream uploading batch b + 4 while batch b runs, six device
     buffer sets recycled under the calling thread's pacing: caelo_pipeline_sync_encoded + an arrival event per batch) gives what
-    Pipeline.run gives on resident scans, bit for bit -- including scans of different lengths sharing a slot and a partial last
-    batch."""
+    Pipeline.run gives on resident scans, bit for bit -- for separately pinned scans (one copy per frame) and for the same scans as
+    views of one pinned block at a fixed pitch (one copy per batch), uncertified and certified (``out.exact`` too), including scans
+    of different lengths sharing a slot and a partial last batch.  The pipeline's pacing is the same afterwards; device scans and a
+    malformed copy table are refused."""
+    import ctypes
     import torch
+    from caelo import _ffi
     from caelo.engine import ransac_draws
     n = 21
     host = [torch.from_numpy(scans(i % 3, quantum=1e-3 if i % 2 else None)).pin_memory() for i in range(n)]
+    cap = max(int(h.shape[0]) for h in host)
+    block = torch.zeros((n, cap, 4), dtype=torch.float32).pin_memory()
+    for i, h in enumerate(host):
+        block[i, :h.shape[0]] = h
+    views = [block[i, :h.shape[0]] for i, h in enumerate(host)]
     dev = [h.to(engine.device) for h in host]
-    rnd = [torch.from_numpy(ransac_draws(70 + i)).to(engine.device) for i in range(n)]
+    draws = [ransac_draws(70 + i) for i in range(n)]
+    rnd = [torch.from_numpy(d).to(engine.device) for d in draws]
     prev = engine.extract(dev[2])
     pipe = engine.pipeline(4, 3)
-    want = pipe.run(dev, rnd, prev=prev)
-    torch.cuda.synchronize()
-    want = [t.clone() for t in (want.rows, want.key_pixels, want.pair_idx, want.inlier_mask, want.result, want.status)]
-    for rep in range(2):
-        got = pipe.run_uploading(host, rnd, prev=prev)
+    lib = engine.lib
+
+    def fields(b):
+        return (b.rows, b.key_pixels, b.pair_idx, b.inlier_mask, b.result, b.status)
+
+    def bits(a):
+        return np.ascontiguousarray(a[:n]).view(np.uint8)
+    for certify in (False, True):
+        kw = dict(certify=True, rands_host=draws) if certify else {}
+        ref = pipe.run(dev, rnd, prev=prev, **kw)
         torch.cuda.synchronize()
-        for a, b in zip(want, (got.rows, got.key_pixels, got.pair_idx, got.inlier_mask, got.result, got.status)):
-            assert torch.equal(a, b)
+        want = [t.clone() for t in fields(ref)]
+        want_exact = [bits(a) for a in ref.exact] if certify else None
+        pace = (pipe.pace, lib.caelo_pipeline_get_pace(pipe.h))
+        for layout in (host, host, views, views):   # (each twice: the second call reuses the device slots)
+            got = pipe.run_uploading(layout, rnd, prev=prev, **kw)
+            torch.cuda.synchronize()
+            for a, b in zip(want, fields(got)):
+                assert torch.equal(a, b)
+            if certify:
+                for a, b in zip(want_exact, got.exact):
+                    assert np.array_equal(a, bits(b))
+            assert (pipe.pace, lib.caelo_pipeline_get_pace(pipe.h)) == pace
+            if layout is views:   # one block at a fixed pitch: the device slots mirror it
+                assert pipe._slots[0] == (6, 4 * cap * 16)
+    with pytest.raises(ValueError):
+        pipe.run_uploading(dev, rnd, prev=prev)
+    # the copy table is checked before the run begins: copy_first must start at 0 and must not decrease
+    jobs = np.zeros(8, dtype=_ffi.JOB_DTYPE)
+    ptrs = np.array([h.data_ptr() for h in host[:8]], dtype=np.uint64)
+    nbytes = np.array([h.shape[0] * 16 for h in host[:8]], dtype=np.uint64)
+    copy_h = ctypes.c_void_p(torch.cuda.Stream(device=engine.device).cuda_stream)   # (not the null stream: a copy stream is required)
+    for first in ([0, 5, 4], [1, 4, 8]):
+        first = np.array(first, dtype=np.int64)
+        rc = lib.caelo_pipeline_run_uploading(pipe.h, jobs.ctypes.data, 8, 2, None, 0, ptrs.ctypes.data, ptrs.ctypes.data, nbytes.ctypes.data,
+                                              first.ctypes.data, 6, None, 0, 4, copy_h, engine.stream, None)
+        assert rc != 0 and b"copy_first" in lib.caelo_last_error()
+    assert (pipe.pace, lib.caelo_pipeline_get_pace(pipe.h)) == pace
 
 
 def test_pipeline_pacing_changes_nothing_but_the_issue(engine, scans):
