@@ -13,12 +13,16 @@ splits the steps instead); the timed region per rank is
     each rank's last frame, one collective at the end)
     ->  (ranks > 0) the pair that straddles the rank boundary (a rank's first frame against the previous rank's last
     one, taken from the gathered rows; rank 0's first frame against the last warm-up frame).
-Rank 0 prints one JSON line (contract in the task statement) including
+The frames go through the native executor (caelo_pipeline): --batch consecutive frames share ONE launch of every front kernel,
+one encoder launch set and one match / RANSAC launch; the three stages of successive batches overlap on three HIP streams
+(front(b+1) || encoder(b) || pairs(b-1)).
+
+Rank 0 prints one JSON line: `value` (frames/s over the timed steps), `ms_per_step` and what the run checked on the way (poses
+solved, status words, the exact-RANSAC counters, the collective).  A plain run does only that: set up, warm up, time the steps,
+--dump-outputs, the line.  --full adds, after the timed steps and never part of `value`:
     roofline      the dominant kernel (k_enc_stage1x, conv1+conv2 of the 3D-CAE encoder), executed MFMA
-                  FLOPs / HIP-event time measured live through caelo_encode_profile
-    The frames go through the native executor (caelo_pipeline): --batch consecutive frames share ONE launch of every
-    front kernel, one encoder launch set and one match / RANSAC launch; the three stages of successive batches overlap
-    on three HIP streams (front(b+1) || encoder(b) || pairs(b-1)).
+                  FLOPs / HIP-event time measured live through caelo_encode_profile; roofline_match likewise for the NN match
+    secondary     short legs of other configurations and scenes through the same pipeline (N == 1 only)
     cpu_baseline  the CPU oracle (oracle/, the reference restated in C/NumPy) on the host cores,
                   bounded sample, rank 0 at N == 1 only.
 """
@@ -60,6 +64,7 @@ def scan_at(index, **kw):
     """synthetic scan number `index` of the endless sequence: pose = the circuit's at index mod 600 (closed: 599 -> 0 is a pair of neighbours
     like any other), range noise / intensities seeded by the index itself (no two scans are equal)"""
     return synth.make_scan(index % synth.CIRCUIT_PERIOD, seed=index, trajectory=TRAJECTORY, **kw)
+
 
 
 CERTIFY = True  # exact RANSAC (device certificates + the host half inside the pipeline) in every leg; --no-certify turns it off
@@ -154,7 +159,8 @@ def bench_dense128(args, eng, world, rank, backend, dev):
         dt = float(tmax.item())
     if args.dump_outputs and rank == 0 and K > 0:   # the last timed step: one frame
         dump_outputs(args.dump_outputs, frame_outputs(ff.rows[None], ff.key_pixels[None], ff.n_key, ff.status[None])[0])
-    if rank == 0:
+    roofline = cpu = None
+    if rank == 0 and args.full:
         vmap = eng.voxmap(max(eng.max_points, big))
         eng.voxelize(pool[0], vmap)
         bits = eng.patches32(vmap, ff.key_pts.contiguous(), ff.n_key)
@@ -195,9 +201,9 @@ def bench_dense128(args, eng, world, rank, backend, dev):
                     "mfma_busy_pmc": pmc_busy,
                     "encoder_kernels": table, "encoder_total_ms": round(float(ms.sum()), 4),
                     "encoder_total_f32_equiv_tflops": round(float(flops.sum() / (ms.sum() * 1e-3) / 1e12), 2)}
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline_dense128()
+    if rank == 0:
         print(json.dumps({
             "metric": "frames/sec keypoint + 32^3-patch descriptor extraction, 128-beam dense scan (configs[4])",
             "value": round(world * K / dt, 2), "unit": "frames/s", "n_gpus": world, "steps": K, "warmup": W,
@@ -207,7 +213,7 @@ def bench_dense128(args, eng, world, rank, backend, dev):
                                    "coordinates; not a reference code path (PatchSize = 16 there): definition in DESIGN.md 4.5",
                        "arithmetic": "f32 in / out / accumulate; every conv / dense product as exact bf16 partial products on the bf16 "
                                      "matrix pipe (f32-grade, DESIGN.md 4.6)",
-                       "points_per_frame": int(pool[0].shape[0]), "keypoints": int(ff.n_key.item()), "patches_per_frame": int(npat),
+                       "points_per_frame": int(pool[0].shape[0]), "keypoints": int(ff.n_key.item()), "patches_per_frame": 3 * int(ff.key_pts.shape[0]),
                        "patch_voxels": 32768, "frames_per_gpu": K, "parallelism": "frames sharded x%d, no collective" % world},
             "roofline": roofline, "cpu_baseline": cpu}), flush=True)
     if world > 1:
@@ -301,12 +307,15 @@ def main():
     ap.add_argument("--steps", type=int, default=120, help="timed steps; a step = one batch of --batch frames (one launch set of "
                                                            "the pipeline) through the whole path")
     ap.add_argument("--warmup", type=int, default=6, help="untimed warm-up steps (batches)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the rocprofv3 --pmc passes that measure `roofline.traffic` and the matrix-pipe busy "
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure what the headline figure does not need: the "
+                                                        "roofline objects, the secondary legs and the CPU baseline (each can be left out "
+                                                        "with its --no-* option)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-pmc", action="store_true", help="--full without the rocprofv3 --pmc passes that measure `roofline.traffic` and the matrix-pipe busy "
                                                           "share in this run (three sub-processes, ~1 min); the committed figures are used and marked stale_possible")
     ap.add_argument("--no-certify", action="store_true", help="the kernels' own RANSAC results (float64 fits) without the host half that "
                                                               "makes inlier sets and poses the reference's bits (never the headline)")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short untimed-for-`value` legs after the timed region "
+    ap.add_argument("--no-secondary", action="store_true", help="--full without the short untimed-for-`value` legs after the timed region "
                                                                 "(configs[1], configs[4], no de-duplication, the clutter scene, upload included)")
     ap.add_argument("--batch", type=int, default=8, help="frames per launch = frames per step (1..8): the front kernels, the encoder "
                                                          "launch set and the match / RANSAC launches each cover a whole batch")
@@ -595,7 +604,12 @@ def main():
         collective["ranks_on_distinct_gpus"] = bool(torch.cuda.device_count() >= world)
 
     out = None
-    if rank == 0:
+    roofline = roofline_match = secondary = cpu = dedup_share = dedup_share_frame = streams_note = None
+    if rank == 0 and host["streams"] != 4:
+        streams_note = ("%d pipeline streams instead of 4: GPU_MAX_HW_QUEUES was %r when HIP initialised (needs >= 8 before the first "
+                        "device call; the package leaves it to the caller) or the runtime refused a stream" % (host["streams"], os.environ.get("GPU_MAX_HW_QUEUES")))
+        print("bench.py: " + streams_note, file=sys.stderr)
+    if rank == 0 and args.full:
         # ---- roofline of the encoder kernels, HIP events on the launch stream.  Two launch shapes: the one the timed region
         # issues -- `batch` frames per launch (every patch: the profiling entry point takes no de-duplication tables) -- is the
         # headline; one frame per launch (round 1's figure) is reported beside it.
@@ -723,23 +737,17 @@ def main():
                     "single_frame_launch": {"patches": 3072, "frac": one_table[names[dom]].get("pipe_frac"),
                                             "launch_ms": round(float(one_ms[dom]), 4), "encoder_kernels": one_table,
                                             "encoder_total_ms_all_patches": round(float(one_ms.sum()), 4)}}
-        streams_note = None
-        if host["streams"] != 4:
-            streams_note = ("%d pipeline streams instead of 4: GPU_MAX_HW_QUEUES was %r when HIP initialised (needs >= 8 before the first "
-                            "device call; the package leaves it to the caller) or the runtime refused a stream" % (host["streams"], os.environ.get("GPU_MAX_HW_QUEUES")))
-            print("bench.py: " + streams_note, file=sys.stderr)
         # ---- secondary legs: other configs / scenes / shortcuts through the SAME pipeline object, after the timed region, never
         # part of `value` (one driver-written record carries them all)
-        secondary = None
         if world == 1 and not args.no_secondary:
             gc.disable()      # (the legs' timed stretches are 15-250 ms long: a cycle collection inside one is a visible share of it)
             try:
                 secondary = secondary_legs(args, eng, pipe, dev, pool, rand, rand_host, Runner, frame_patches, encoder_table, host_scans, names)
             finally:
                 gc.enable()
-        cpu = None
         if world == 1 and not args.no_cpu_baseline:
             cpu = cpu_baseline()
+    if rank == 0:
         out = {
             "metric": "KITTI frames/sec end-to-end (keypts+desc+match+RANSAC)" if not args.extract_only else
                       "KITTI frames/sec keypoint+descriptor extraction only (configs[1])",
@@ -759,7 +767,8 @@ def main():
                                 "holds a scan twice); the roofline object times the encoder kernels on all 3072 patches of every frame",
                        "dedup_share": dedup_share, "dedup_share_within_frames": dedup_share_frame,
                        "value_no_dedup": (secondary or {}).get("no_dedup", {}).get("frames_per_s"),
-                       "value_no_dedup_note": "the same workload with every patch encoded (secondary.no_dedup): the rate to expect from a scene without "
+                       "value_no_dedup_note": None if dedup_share is None else
+                                              "the same workload with every patch encoded (secondary.no_dedup): the rate to expect from a scene without "
                                               "equal patches; `value` exploits that %.0f %% of this scene's patches are copies of another patch of their batch" % (100.0 * dedup_share),
                        "uploads_in_timed_region": bool(args.include_h2d),
                        "trajectory": TRAJECTORY + " (caelo.synth.sensor_pose: structure at every frame index; closed after %d frames)" % synth.CIRCUIT_PERIOD,

@@ -1,3 +1,4 @@
+# the roofline object and value of `bench.py --full` lines on stdin
 import json,sys
 for line in sys.stdin:
     line=line.strip()

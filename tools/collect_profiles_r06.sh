@@ -6,11 +6,11 @@ O=$R/gpurun_out/prof6
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 py() { timeout ${T:-300} python "$@"; }
-T=700 py $R/bench.py --steps 20 --warmup 5 > $O/bench_20steps.json 2> $O/bench_20steps.err
+T=700 py $R/bench.py --steps 20 --warmup 5 --full > $O/bench_20steps.json 2> $O/bench_20steps.err
 py $R/bench.py --steps 120 --warmup 6 --no-cpu-baseline --no-secondary --no-pmc > $O/bench_120steps.json 2>/dev/null
 py $R/bench.py --steps 120 --warmup 6 --no-cpu-baseline --no-secondary --no-pmc --no-certify > $O/bench_120steps_no_certify.json 2>/dev/null
-py $R/bench.py --steps 60 --warmup 6 --scene clutter --no-cpu-baseline --no-secondary --no-pmc > $O/bench_clutter.json 2>/dev/null
-py $R/bench.py --steps 60 --warmup 6 --include-h2d --no-cpu-baseline --no-secondary --no-pmc > $O/bench_include_h2d.json 2>/dev/null
+py $R/bench.py --steps 60 --warmup 6 --scene clutter --full --no-cpu-baseline --no-secondary --no-pmc > $O/bench_clutter.json 2>/dev/null
+py $R/bench.py --steps 60 --warmup 6 --include-h2d --full --no-cpu-baseline --no-secondary --no-pmc > $O/bench_include_h2d.json 2>/dev/null
 rm -rf /tmp/kb; timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/kb -o kb -- python $R/bench.py --steps 60 --warmup 6 --no-cpu-baseline --no-secondary --no-pmc > $O/bench_under_rocprof.json 2>/dev/null
 python $R/tools/prof_summary.py /tmp/kb/kb_results.db "rocprofv3 --kernel-trace --stats -- python bench.py --steps 60 --warmup 6 --no-cpu-baseline --no-secondary --no-pmc" > $O/kernel_stats_bench.txt 2>&1
 python $R/tools/timeline.py /tmp/kb/kb_results.db 1700 400 > $O/timeline_bench.txt 2>&1
