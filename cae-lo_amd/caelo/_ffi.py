@@ -50,6 +50,7 @@ EXTRACT_GIVEN_KEYPTS, EXTRACT_GIVEN_ROWS = 8, 16   # the caller's key points (ca
 ST_BAD_KEYPTS = 128   # status bit of EXTRACT_GIVEN_KEYPTS: K outside [1, 1024], or a coordinate non-finite or beyond GIVEN_KEYPTS_RANGE
 GIVEN_KEYPTS_RANGE = 16384.0   # metres, include/caelo.h CAELO_GIVEN_KEYPTS_RANGE
 ABI_VERSION = 6   # include/caelo.h CAELO_ABI_VERSION
+KP_NN_MAX_K, KP_NN_MAX_THRESHOLDS = 65536, 16   # include/caelo.h CAELO_KP_NN_MAX_K / CAELO_KP_NN_MAX_THRESHOLDS (caelo_kp_nn_pairs)
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 
 # the same layout as a NumPy record (a run's jobs are filled column-wise and handed over in one call)
@@ -152,6 +153,7 @@ SIGNATURES = [
     ("caelo_pipeline_stats", c_int, [c_vp, C.POINTER(c_i64)]),
     ("caelo_pipeline_expect", c_int, [c_vp, c_i64]),
     ("caelo_lane_faults", c_int, [c_vp, C.POINTER(c_i64)]),
+    ("caelo_kp_nn_pairs", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
 ]
 
 _lib = None

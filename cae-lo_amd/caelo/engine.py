@@ -751,6 +751,53 @@ class Engine:
         """Synchronising read of a caelo_icp_result."""
         return _ffi.IcpResult.from_buffer_copy(res.cpu().numpy().tobytes())
 
+    def kp_nn_pairs(self, pts, n_key, pairs, thresholds, want_dist=True):
+        """Key point repeatability on the device (caelo_kp_nn_pairs, EvaluationOnKeypts.py:68-94, :128-140).
+
+        pts [F, ld, 3] f64 world-frame key points (frame f: rows 0 .. n_key[f]-1), n_key [F] int, pairs [P, 2] int = (fit frame,
+        query frame), thresholds: 1 to 16 finite positive floats.  -> (dist [P, ld] f64 with NaN past each query frame's n_key, or
+        None; counts [P, T + 1] i64), on the device.  dist is scikit-learn's kd-tree distance to the nearest fit point, bit for bit.
+
+        Refused with ValueError before any launch (include/caelo.h): a fit set of 3 points or fewer (scikit-learn answers those by
+        brute force, with a dot-product formula and BLAS rounding), a query set of none, a non-finite coordinate (scikit-learn raises
+        there too), ld above CAELO_KP_NN_MAX_K, a pair index out of range, thresholds that are not finite and positive."""
+        pts = torch.as_tensor(pts, dtype=torch.float64, device=self.device).contiguous()
+        if pts.dim() != 3 or pts.shape[2] != 3:
+            raise ValueError("pts must be [F, ld, 3], got %s" % (tuple(pts.shape),))
+        F, ld = int(pts.shape[0]), int(pts.shape[1])
+        if ld < 1 or ld > _ffi.KP_NN_MAX_K:
+            raise ValueError("ld = %d: a key point set holds 1 to %d points here" % (ld, _ffi.KP_NN_MAX_K))
+        nk = np.asarray(n_key.cpu() if torch.is_tensor(n_key) else n_key, dtype=np.int64).reshape(-1)
+        pr = np.asarray(pairs.cpu() if torch.is_tensor(pairs) else pairs, dtype=np.int64).reshape(-1, 2)
+        thr = np.ascontiguousarray(thresholds, dtype=np.float64).reshape(-1)
+        if nk.shape[0] != F:
+            raise ValueError("n_key holds %d counts for %d frames" % (nk.shape[0], F))
+        if not 1 <= thr.size <= _ffi.KP_NN_MAX_THRESHOLDS or not (np.isfinite(thr).all() and (thr > 0).all()):
+            raise ValueError("thresholds: 1 to %d finite positive values, got %s" % (_ffi.KP_NN_MAX_THRESHOLDS, thr.tolist()))
+        if pr.size and (pr.min() < 0 or pr.max() >= F):
+            raise ValueError("a pair names a frame outside [0, %d)" % F)
+        if ((nk < 0) | (nk > ld)).any():
+            raise ValueError("n_key must lie in [0, ld = %d]" % ld)
+        if pr.size:
+            small = [int(f) for f in np.unique(pr[:, 0]) if nk[f] <= 3]
+            if small:
+                raise ValueError("fit set(s) of frame(s) %s hold 3 points or fewer: scikit-learn brute-forces those (a different "
+                                 "rounding), which this kernel does not restate" % small[:10])
+            empty = [int(f) for f in np.unique(pr[:, 1]) if nk[f] < 1]
+            if empty:
+                raise ValueError("query set(s) of frame(s) %s are empty" % empty[:10])
+        nk_d = torch.from_numpy(nk.astype(np.int32)).to(self.device)
+        inside = torch.arange(ld, device=self.device)[None, :] < nk_d[:, None]
+        if not bool(torch.isfinite(pts[inside]).all()):
+            raise ValueError("Input contains NaN, infinity or a value too large for dtype('float64').")
+        pr_d = torch.from_numpy(pr.astype(np.int32)).to(self.device).contiguous()
+        P = pr.shape[0]
+        dist = torch.full((P, ld), float("nan"), dtype=torch.float64, device=self.device) if want_dist else None
+        counts = self.empty((P, thr.size + 1), torch.int64)
+        _ffi.check(self.lib.caelo_kp_nn_pairs(self.ctx, _ptr(pts), F, ld, _ptr(nk_d), _ptr(pr_d), P, _hptr(thr), int(thr.size),
+                                              _ptr(dist), _ptr(counts), self.stream))
+        return dist, counts
+
     def voxelize(self, pc, vmap=None, status=None):
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] >= 3 and pc.is_contiguous()
         vmap = vmap or self.voxmap(max(self.max_points, pc.shape[0]))

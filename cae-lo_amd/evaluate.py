@@ -1,0 +1,72 @@
+#!/usr/bin/env python
+"""evaluate.py -- the reference's evaluation scripts on this engine's outputs (caelo.evaluate).
+
+    python evaluate.py registration --gt poses/00.txt --est poses_/00.txt --calib calib/00/calib_.txt --matchability m00.mat \\
+                                    [--gt ... --est ... --calib ... --matchability ...] [--frame-step s] [--out EvaluationResults.mat]
+    python evaluate.py keypoints --keypts-dir 00/Features --source ae --gt poses/00.txt --calib calib/00/calib_.txt \\
+                                 [--frame-step s] [--inner] --out AccuracyOfKeyPts_1_0_00.mat
+
+registration (EvaluationOnRegistration.py / EvalOnReg_KeyPts.py): one --gt / --est / --calib / --matchability per sequence, the
+sequences concatenated; prints RRE, stdRRE, RTE, stdRTE, success rate (RRE < 1 deg and RTE < 0.5 m), inlier ratio (both
+fractions) and average RANSAC trials; --out writes them as the 1 x 7 float32 EvaluationResults.
+keypoints (EvaluationOnKeypts.py): key point repeatability of one sequence; the nearest-neighbour search runs on the GPU
+(caelo_kp_nn_pairs); prints the counts and writes the reference's {'counts': ...} file.  --inner is the reference's mode 1.
+"""
+import argparse
+import os
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+from caelo import evaluate as ev  # noqa: E402
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    sub = ap.add_subparsers(dest="cmd", required=True)
+    r = sub.add_parser("registration", help="per-pair rotation / translation errors -> the 7-column row")
+    r.add_argument("--gt", action="append", required=True, help="ground truth poses [n, 12] (once per sequence)")
+    r.add_argument("--est", action="append", required=True, help="estimated poses [n, 12], e.g. run_sequence.py's output")
+    r.add_argument("--calib", action="append", required=True, help="calib_.txt (row 4 = Tr) or KITTI calib.txt")
+    r.add_argument("--matchability", action="append", required=True, help="AllProportions / AllTrialCounts .mat (run_sequence.py --matchability)")
+    r.add_argument("--frame-step", type=int, default=1, help="slice both pose files [0:n:step] (EvalOnReg_KeyPts.py:96-99)")
+    r.add_argument("--out", help="write EvaluationResults [1, 7] f32 here")
+    k = sub.add_parser("keypoints", help="key point repeatability (histogram of nearest-neighbour distances)")
+    k.add_argument("--keypts-dir", required=True, help="<frame:06d>.bin.mat (ae: KeyPts/ or Features/) or <frame:06d>.bin files")
+    k.add_argument("--source", required=True, choices=ev.SOURCES)
+    k.add_argument("--gt", required=True, help="ground truth poses [n, 12], one per key point file")
+    k.add_argument("--calib", required=True, help="calib_.txt (row 4 = Tr) or KITTI calib.txt")
+    k.add_argument("--frame-step", type=int, default=1)
+    k.add_argument("--inner", action="store_true", help="mode 1 (ComputeDispersionOfKeypoints): each frame against itself")
+    k.add_argument("--out", required=True, help="the counts file (the reference names it AccuracyOfKeyPts_<step>_<source>_<seq>.mat)")
+    a = ap.parse_args(argv)
+    if a.frame_step < 1:
+        ap.error("--frame-step must be >= 1")
+
+    if a.cmd == "registration":
+        row, ok = ev.registration(a.gt, a.est, a.calib, a.matchability, a.frame_step)
+        print("RRE %.6g  stdRRE %.6g  RTE %.6g  stdRTE %.6g  success %.6g (%d of %d)  inlier ratio %.6g  trials %.6g" % (
+            row[0], row[1], row[2], row[3], row[4], int(np.sum(ok)), ok.shape[0], row[5], row[6]))
+        if a.out:
+            ev.save_registration(a.out, row)
+        return 0
+
+    t0 = time.time()
+    poses = np.loadtxt(a.gt)
+    Tr = ev.read_tr(a.calib)
+    pts = ev.GetAllKeyPts(a.keypts_dir, a.source, poses, Tr, a.frame_step)
+    t1 = time.time()
+    _, counts = ev.device_distances(pts, a.inner)
+    t2 = time.time()
+    counts = [np.int64(c) for c in counts]
+    ev.save_repeatability(a.out, counts)
+    print("counts %s over %d frames (%s) -> %s" % ([int(c) for c in counts], len(pts), "mode 1" if a.inner else "mode 0", a.out))
+    print("seconds: reading + world transform %.3f, device pass (incl. engine start) %.3f" % (t1 - t0, t2 - t1), file=sys.stderr)
+    return 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())

@@ -48,13 +48,19 @@ def _parse_poses(raw, k):
     return out, r["success"] != 0, r["threshold"].astype(np.float32), r["n_inliers"].astype(np.int32)
 
 
-def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_log, certify):
+def _parse_records(raw, k):
+    """The RANSAC records --matchability keeps: iterations (cntIters of the last level) and n_pairs, [k] i32 each."""
+    r = np.frombuffer(raw[:k].tobytes(), dtype=_ffi.POSE_DTYPE, count=k)
+    return r["iterations"].astype(np.int32), r["n_pairs"].astype(np.int32)
+
+
+def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_log, certify, records=None):
     """The chunk loop of run_local and run_local_files: frames [lo, hi) in chunks of ``chunk``.  ``submit(ci, c0, c1, prev)`` issues
     chunk ci = frames [c0, c1) (frame c0 matched against ``prev``) -> (FrameBatch, exact_on_host, scan(j), draws(j)): with
     ``exact_on_host`` the certified poses are read from ``batch.exact`` (Pipeline.run_loaded(publish=False)), else from the device;
     ``scan`` and ``draws`` fetch a tied frame's scan and a pair's draws again for the host redo (Engine.redo_ties).
     The poses and status words of chunk c come back through pinned buffers on a side stream and are parsed after chunk c + 1 has
-    been issued.  Returns what run_local returns."""
+    been issued.  Returns what run_local returns; ``records`` (a list) receives (iterations, n_pairs) per chunk."""
     import gc
     gc.collect()
     gc.freeze()       # what exists now is never scanned again: a full collection of this process (40-90 ms) no longer lands between two batches
@@ -77,6 +83,9 @@ def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_lo
         r, o, t, n = _parse_poses(res_h, k)
         s = 0 if has_prev else 1                                   # slot 0 of the first chunk has no predecessor here
         rel.append(r[s:]); ok.append(o[s:]); thr.append(t[s:]); nin.append(n[s:])
+        if records is not None:
+            its, nps = _parse_records(res_h, k)
+            records.append((its[s:], nps[s:]))
         ht["parse"] += time.time() - t_
 
     t_loop = time.time()
@@ -125,7 +134,7 @@ def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_lo
 
 
 def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-              loader_threads=4, certify=True, native_ties=False, given=None):
+              loader_threads=4, certify=True, native_ties=False, given=None, records=None):
     """Frames [lo, hi) of this rank.  Returns per-pair rows for pairs (i-1, i), i in (lo, hi) -- the pair (lo-1, lo)
     is the caller's (it needs the previous rank's last frame) -- plus the first and last frame's features.
 
@@ -139,6 +148,7 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
     ``given(i)`` -> ('keypts', [K,3] f32) | ('rows', [K,64] f32): frame i's key points or rows of another source (PoseEstimation.py:26-66,
     caelo.keysources); the chunk then goes through Pipeline.run on resident scans (keypts= / rows_given=), with the tie-split patches
     redone inside the pipeline unless ``strict_ties`` is off.
+    ``records``: a list that receives each chunk's (iterations, n_pairs) [k] i32, the pairs in the order of the returned rows.
     """
     import queue
     import threading
@@ -244,11 +254,11 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
         ht["pipeline"] += time.time() - t_
         return batch, False, lambda j: scans[j].to(eng.device), lambda j: (draws_d[j], dn[j])
 
-    return _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify)
+    return _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify, records)
 
 
 def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-                    loader_threads=16, certify=True, device_results=False, native_ties=False):
+                    loader_threads=16, certify=True, device_results=False, native_ties=False, records=None):
     """run_local for scans that are FILES (round 6): the native loader (caelo_seqloader: pread into a pinned ring + the RANSAC draws,
     csrc/seqload.hip) works ahead on its own threads, a chunk of batches goes through Pipeline.run_loaded (one copy command per batch
     for scans and draws, jobs built column-wise).  Same returns as run_local; same bits (the draws are NumPy's stream, the pipeline
@@ -303,7 +313,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
             return torch.from_numpy(d).to(eng.device), d
         return batch, not publish, scan, draws
 
-    out = _run_chunks(eng, lo, hi, per_chunk * B, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify)
+    out = _run_chunks(eng, lo, hi, per_chunk * B, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify, records)
     ls = loader.stats()
     ht["load"], ht["draws"] = ls["read_s"], ls["draws_s"]      # (summed over the loader's threads)
     loader.close()
@@ -330,6 +340,8 @@ def main():
     ap.add_argument("--loader-threads", type=int, default=min(16, os.cpu_count() or 1), help="threads that read / synthesise scans and draw RANSAC's random numbers")
     ap.add_argument("--python-loader", action="store_true", help="--scans through round 5's Python loader threads instead of the native loader (caelo_seqloader)")
     ap.add_argument("--save-artifacts", action="store_true", help="write Features/*.mat and InliersIdx/*.mat next to the scans")
+    ap.add_argument("--matchability", help="write the per-pair RANSAC inlier proportions (n_inliers / n_pairs) and trial counts (cntIters) "
+                                           "here, in frame order: AllProportions / AllTrialCounts [1, n] (evaluate.py registration)")
     ap.add_argument("--no-strict-ties", action="store_true", help="keep the fused path's canonical rule where the 496-nearest cut splits a "
                                                                   "tie class (default: such frames are redone in scikit-learn's kd-tree order)")
     ap.add_argument("--native-ties", action="store_true", help="the pipeline redoes tie-split patches itself in scikit-learn's order "
@@ -429,16 +441,17 @@ def main():
 
     tie_log = []
     host_times = {}
+    records = [] if args.matchability else None
     if args.scans and not args.python_loader:
         rel, ok, thr, nin, first, last = run_local_files(eng, files, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                          args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
                                                          loader_threads=args.loader_threads, certify=not args.no_certify, device_results=args.save_artifacts,
-                                                         native_ties=args.native_ties)
+                                                         native_ties=args.native_ties, records=records)
     else:
         rel, ok, thr, nin, first, last = run_local(eng, load, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                    args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
                                                    loader_threads=args.loader_threads, certify=not args.no_certify, native_ties=args.native_ties,
-                                                   given=given)
+                                                   given=given, records=records)
     if tie_log:
         print("rank %d: %d frame(s) redone in scikit-learn's tie order (%d patches): %s" % (
             rank, len(tie_log), sum(n for _, n in tie_log), [f for f, _ in tie_log][:20]), file=sys.stderr)
@@ -454,14 +467,24 @@ def main():
             row = np.r_[np.array(r.R, np.float32), np.array(r.T, np.float32)][None]
             rel = np.concatenate([row, rel]); ok = np.r_[bool(r.success), ok]; thr = np.r_[np.float32(r.threshold), thr]
             nin = np.r_[np.int32(r.n_inliers), nin]
-        extra = torch.from_numpy(np.c_[rel, ok, thr, nin].astype(np.float32)).to(eng.device)
+            if records is not None:
+                records.insert(0, (np.array([r.iterations], np.int32), np.array([r.n_pairs], np.int32)))
+        cols = [rel, ok, thr, nin]
+        if records is not None:   # (two more columns: small integers, exact in float32)
+            cols += [np.concatenate([a for a, _ in records]) if records else np.zeros(0), np.concatenate([b for _, b in records]) if records else np.zeros(0)]
+        extra = torch.from_numpy(np.c_[tuple(cols)].astype(np.float32)).to(eng.device)
         allrows = cdist.gather_poses(extra, n).cpu().numpy()
         rel, ok, thr, nin = allrows[:, :12], allrows[:, 12] > 0, allrows[:, 13], allrows[:, 14].astype(np.int32)
+        if records is not None:
+            records = [(allrows[:, 15].astype(np.int32), allrows[:, 16].astype(np.int32))]
     torch.cuda.synchronize()
     dt = time.time() - t0
     if rank == 0:
         poses = stageio.chain_poses(rel, Tr)
         stageio.write_poses(args.out, poses)
+        if records is not None:
+            from caelo import evaluate as ev
+            ev.save_matchability(args.matchability, nin, np.concatenate([b for _, b in records]), np.concatenate([a for a, _ in records]))
         for i in range(len(rel) if len(rel) <= 200 else 0):
             print("%06d-%06d ok=%d thr=%.1f inliers=%4d T=[% .3f % .3f % .3f]" % (i, i + 1, ok[i], thr[i], nin[i], rel[i, 9], rel[i, 10], rel[i, 11]))
         print("%d frames, %d pairs on %d GPU(s) in %.2f s (%.1f frames/s incl. scan loading / synthesis, upload and read-back; %d of %d poses solved) -> %s" % (

@@ -397,6 +397,22 @@ int64_t caelo_icp_loop_ws_bytes(int64_t n1, int64_t m1);
 int caelo_icp(caelo_ctx *ctx, const float *pc0, int64_t n0, float *pc1, int64_t n1, const float *planar0, int64_t m0, float *planar1,
               int64_t m1, const caelo_icp_params *params, caelo_icp_result *result, void *ws, void *stream);
 
+/* ---- evaluation: key point repeatability (EvaluationOnKeypts.py, csrc/evaluate.hip) -----------------------------------------
+ * pts [n_frames][ld][3] f64 world-frame key points (device), n_key [n_frames] i32 (device): frame f holds rows 0 .. n_key[f]-1.
+ * pairs [n_pairs][2] i32 (device) = (fit frame, query frame).  For every query point: the distance to its nearest fit point, exactly
+ * as scikit-learn 0.24.2's kd-tree returns it (minimum of d = 0; d += (x - y)^2 over x, y, z, each operation rounded, then a correctly
+ * rounded sqrt) -> dist [n_pairs][ld] f64 (device, nullable; rows past the query frame's n_key are not written).  counts
+ * [n_pairs][n_thresholds + 1] i64 (device, overwritten): bin t < T counts #(dist / D_t < 1) - #(dist / D_{t-1} < 1) with an IEEE
+ * division, bin T counts #(dist / D_{T-1} >= 1) (EvaluationOnKeypts.py:128-140); a pair (f, f) gives 0 for every point, as the
+ * reference's mode 1 does.  thresholds [n_thresholds] f64 (HOST), finite and positive, 1 <= n_thresholds <= 16.
+ * The caller validates the data (caelo.Engine.kp_nn_pairs): fit sets of more than 3 points (scikit-learn brute-forces smaller ones),
+ * finite coordinates, n_key in [1, ld], pair indices in [0, n_frames).  The kernel clamps n_key to [0, ld] and skips a pair whose
+ * index is out of range, so bad data never reads out of bounds. */
+#define CAELO_KP_NN_MAX_K 65536
+#define CAELO_KP_NN_MAX_THRESHOLDS 16
+int caelo_kp_nn_pairs(caelo_ctx *ctx, const double *pts, int64_t n_frames, int ld, const int32_t *n_key, const int32_t *pairs,
+                      int64_t n_pairs, const double *thresholds, int n_thresholds, double *dist, int64_t *counts, void *stream);
+
 /* ---- frame pipeline: batches of frames behind single launches, three stages on three HIP streams ------------------
  * Replaces the reference's per-frame driver loops (BatchPreprocess.py:88-140 extract loop, Match.py:296-353 /
  * PoseEstimation.py pair loop) for throughput.  `batch` consecutive frames share ONE launch of every kernel of the
