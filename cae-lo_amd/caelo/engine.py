@@ -207,6 +207,13 @@ class Pipeline:
         return {"jobs": int(out[0]), "issue_us_per_frame": out[1] / n / 1e3, "batches": int(out[2]), "batch": int(out[3]),
                 "buffers": int(out[4]), "streams": int(out[5])}
 
+    def streams(self):
+        """caelo_pipeline_streams: the HIP stream handles (ints) of the stages -> {"front", "encoder", "pair", "voxel"}; stages that
+        share a stream report the same handle, "voxel" is None when the voxel maps are built on the front stream."""
+        out = (C.c_void_p * 4)()
+        _ffi.check(self.eng.lib.caelo_pipeline_streams(self.h, out))
+        return dict(zip(("front", "encoder", "pair", "voxel"), (out[i] for i in range(4))))
+
     def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None, exact_patches=False):
         """The run's jobs as one record array, filled column-wise, handed over in ONE foreign call (a ctypes call per frame
         costs ~10 us: 380 us for a 20-frame run, most of it before the first launch)."""
@@ -433,8 +440,10 @@ class Pipeline:
         frame i + 1 while frame i is matched (PoseEstimation.py:214-245).  The loop runs natively (caelo_pipeline_run_uploading) and
         paces the hand-overs from the calling thread, not by waits in the device queues: per batch it waits for the arrival of the
         batch's scans (an event on the copy stream), issues the launches, then the copies of the batch ``ahead`` further on, then waits
-        for the encoder of the batch before (caelo_pipeline_sync_encoded: the GPU keeps one batch queued; the buffers the next copies
-        overwrite were read by a front stage at least two batches back).  ``ahead``: 13.5 / 15.3 / 15.9 / 16.1 k frames/s for
+        for the encoder of the batch before (caelo_pipeline_sync_encoded: the GPU keeps one batch queued).  The slot the next copy
+        overwrites held batch b - 2, whose scans only its front stage read: the wait for the encoder of b - 2 (one iteration earlier)
+        covers it; the first ``ahead`` copies of a call wait on the device for the previous call's work (the copy stream waits the
+        call's begin, once).  ``ahead``: 13.5 / 15.3 / 15.9 / 16.1 k frames/s for
         1 / 2 / 3 / 4 (18.6 k resident; an arrival is late by up to 0.3 ms now and then, and a batch of scans is 17 MB of device
         memory).  Device-side waits for the same hand-overs cost 8 - 15 % of the resident rate EACH, however rarely they were issued
         (DESIGN.md 5).  Scans of a batch that are views of ONE pinned block at a fixed pitch go up behind one copy command per batch,
@@ -484,7 +493,11 @@ class Pipeline:
                    exact_patches=False):
         """Batches [b0, b0 + nb) of a SeqLoader through the pipeline: a batch's scans AND draws go up behind ONE copy command (the loader's
         slot layout, mirrored on the device), the jobs are built column-wise for the whole call, and nothing here is per-frame Python.
-        The loop of ``run_uploading``, fed by the loader.  ``exact_patches``: as in ``Pipeline.run``.  -> (FrameBatch, frames)."""
+        The loop of ``run_uploading``, fed by the loader.  A device slot here also holds the batch's draws, which its PAIR stage reads:
+        before the copy that overwrites the slot of batch b - 2 the calling thread waits for an event recorded on the pair stream after
+        that batch's pairs (the encoder wait of ``run_uploading`` does not cover them).  With ``certify`` the certifier reads the draws
+        from the loader's keep ring, which must hold ring + 7 batches (caelo_pipeline::CERT_RING + 1 beyond the loader's ring; refused
+        otherwise).  ``exact_patches``: as in ``Pipeline.run``.  -> (FrameBatch, frames)."""
         B = self.batch
         assert loader.batch == B and ahead >= 1 and b0 + nb <= loader.n_batches
         k = min(loader.n - b0 * B, nb * B)

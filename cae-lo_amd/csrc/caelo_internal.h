@@ -123,6 +123,8 @@ struct caelo_voxmap {
 };
 
 void kd_destroy(caelo_voxmap *m);
+// seqload.hip: the loader's ring of slots and its ring of kept draws (0: none), for the pipeline's checks
+void seqloader_rings(const caelo_seqloader *L, int *ring_batches, int *keep_batches);
 int kd_store_lists(caelo_voxmap *m, const int16_t *const lists[3], const int64_t ns[3], hipStream_t s);
 int kd_begin_device_lists(caelo_voxmap *m, int16_t *vox_out[3], int32_t **n_out, hipStream_t s);
 int kd_resolve(const caelo_voxmap *m, const float *pts, int pts_ld, int64_t k_max, const int32_t *n_key, uint64_t *bits, uint8_t *flags,

@@ -69,6 +69,7 @@ struct caelo_pipeline {
     hipEvent_t ext_enc[EXT_RING] = {nullptr};
     unsigned n_ext_enc = 0;
     std::vector<hipEvent_t> up_arrived;   // caelo_pipeline_run_uploading: a batch's scans are in device memory
+    std::vector<hipEvent_t> pair_read;    // ... with a loader: a batch's pair stage is through (the draws in its device slot are read)
     // host state
     std::vector<caelo_frame_job> pending;
     uint64_t n_batches = 0, submitted = 0;
@@ -468,6 +469,7 @@ CAELO_API void caelo_pipeline_destroy(caelo_pipeline *p) {
     for (hipEvent_t e : p->joined)
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->up_arrived) (void)hipEventDestroy(e);
+    for (hipEvent_t e : p->pair_read) (void)hipEventDestroy(e);
     for (hipEvent_t e : {p->vox_fork, p->vox_join})
         if (e) (void)hipEventDestroy(e);
     for (hipEvent_t e : p->ext_enc)
@@ -581,6 +583,17 @@ CAELO_API int caelo_pipeline_stats(caelo_pipeline *p, int64_t *out_host) {
     return CAELO_OK;
 }
 
+// the streams the stages run on: out_host[4] = front, encoder, pair, voxel maps (a stage that shares a stream reports that stream;
+// null: no voxel stream, the maps are built on the front stream)
+CAELO_API int caelo_pipeline_streams(const caelo_pipeline *p, void **out_host) {
+    CAELO_REQUIRE(p && out_host, "null argument");
+    out_host[0] = (void *)p->sF;
+    out_host[1] = (void *)p->sE;
+    out_host[2] = (void *)p->sP;
+    out_host[3] = (void *)p->sV;
+    return CAELO_OK;
+}
+
 CAELO_API int caelo_pipeline_cert_stats(caelo_pipeline *p, int64_t *out_host) {
     CAELO_REQUIRE(p && out_host, "null argument");
     std::lock_guard<std::mutex> lk(p->cert_mu);
@@ -644,6 +657,17 @@ CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *j
             CAELO_REQUIRE(copy_first[b + 1] >= copy_first[b] && copy_first[b + 1] - copy_first[b] <= INT32_MAX,
                           "copy_first must not decrease");
     }
+    if (loader) {   // the certifier reads a batch's draws from the loader's keep ring: the ring must outlast the certifier's lag
+        int ring = 0, keep = 0;
+        seqloader_rings(loader, &ring, &keep);
+        bool host_draws = false;
+        for (int64_t i = 0; i < k && !host_draws; ++i) host_draws = jobs[i].result_host && jobs[i].rand_host;
+        // Batch b's draws are read by the certifier until its task is free; the task of batch b + CERT_RING cannot be had before, so
+        // the issuing thread is at most in batch b + CERT_RING, has released the loader's slots up to it, and the loader may have
+        // filled batches up to b + CERT_RING + ring_batches -- all of them in keep entries other than b's only with this many:
+        CAELO_REQUIRE(!host_draws || keep == 0 || keep >= ring + caelo_pipeline::CERT_RING + 1,
+                      "caelo_pipeline_run_uploading: a certified run needs the loader's keep_batches >= ring_batches + 7");
+    }
     const int B = p->batch;
     hipStream_t copy = caelo_stream(copy_stream);
     const int n_ev = ahead + 2;
@@ -651,6 +675,11 @@ CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *j
         hipEvent_t e;
         CAELO_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         p->up_arrived.push_back(e);
+    }
+    while (loader && (int)p->pair_read.size() < n_slots) {
+        hipEvent_t e;
+        CAELO_HIP(hipEventCreateWithFlags(&e, local_event_flags()));
+        p->pair_read.push_back(e);
     }
     int64_t tw[4] = {0, 0, 0, 0};
     auto upload = [&](int64_t b) -> int {
@@ -688,8 +717,22 @@ CAELO_API int caelo_pipeline_run_uploading(caelo_pipeline *p, caelo_frame_job *j
         int64_t t1 = now_ns();
         tw[1] += t1 - t0;
         if ((rc = caelo_pipeline_submit_many(p, jobs + lo, hi - lo))) break;
+        // With a loader, a device slot holds the batch's draws too, which the pair stage reads (k_ransac_hyp / _hyp_up / _finish): the
+        // slot is overwritten only once that stage is through.  The issuing thread waits for it (no device-side wait: DESIGN.md 6);
+        // the batch is two behind the one just issued, its pair stage has normally long finished.
+        if (loader && hi - lo == B && hipEventRecord(p->pair_read[(size_t)(b % n_slots)], p->sP) != hipSuccess) {
+            caelo_set_error("caelo_pipeline_run_uploading: hipEventRecord failed");
+            rc = CAELO_ERR_HIP;
+            break;
+        }
         t0 = now_ns();
         tw[2] += t0 - t1;
+        if (loader && b + ahead < nb && b + ahead >= n_slots &&
+            hipEventSynchronize(p->pair_read[(size_t)((b + ahead - n_slots) % n_slots)]) != hipSuccess) {
+            caelo_set_error("caelo_pipeline_run_uploading: a pair stage failed");
+            rc = CAELO_ERR_HIP;
+            break;
+        }
         if (b + ahead < nb && (rc = upload(b + ahead))) break;
         if (hi - lo == B && (rc = caelo_pipeline_sync_encoded(p, 1))) break;   // (a partial last batch is only issued by the flush)
         tw[3] += now_ns() - t0;

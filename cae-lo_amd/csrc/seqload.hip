@@ -156,7 +156,7 @@ void seq_worker(caelo_seqloader *L) {
         // the draws of pair (frame - 1, frame): RandomState(seed_base + frame - 1).random_sample(CAELO_SEQ_DRAWS)
         const int64_t seed = L->seed_base + L->first_frame + i - 1;
         double *dr = (double *)(sbase + (size_t)L->batch * (size_t)L->cap * 16) + (size_t)j * CAELO_SEQ_DRAWS;
-        random_sample((uint32_t)(seed > 0 ? seed : 0), CAELO_SEQ_DRAWS, dr);
+        random_sample((uint32_t)(seed > 0 ? seed : 0), CAELO_SEQ_DRAWS, dr);   // (in range for every frame with a pair: checked at create)
         if (L->keep) memcpy(L->keep + ((size_t)(b % L->keep_ring) * L->batch + j) * CAELO_SEQ_DRAWS, dr, sizeof(double) * CAELO_SEQ_DRAWS);
         t_read += t1 - t0;
         t_draw += now_ns_() - t1;
@@ -188,6 +188,11 @@ CAELO_API int caelo_seqloader_create(const char *const *paths, int64_t n, int64_
                                      void *ring_host, double *draws_keep_host, int keep_batches, int64_t seed_base, int threads, caelo_seqloader **out) {
     CAELO_REQUIRE(paths && out && ring_host && n > 0 && batch >= 1 && batch <= CAELO_FB_MAX && ring_batches >= 2 && cap_points > 0 &&
                   threads >= 1 && threads <= 256 && (!draws_keep_host || keep_batches >= ring_batches), "caelo_seqloader_create: bad argument");
+    {   // pair (frame - 1, frame) draws RandomState(seed_base + frame - 1), which takes seeds in [0, 2^32) only; frame 0 has no pair
+        const __int128 f_lo = first_frame > 1 ? first_frame : 1, f_hi = (__int128)first_frame + n - 1;
+        CAELO_REQUIRE(f_hi < f_lo || (seed_base + f_lo - 1 >= 0 && seed_base + f_hi - 1 <= (__int128)UINT32_MAX),
+                      "caelo_seqloader_create: seed_base + frame - 1 must lie in [0, 2^32) for every frame with a pair (RandomState's seeds)");
+    }
     caelo_seqloader *L = new caelo_seqloader();
     L->paths.assign(paths, paths + n);
     L->n = n; L->batch = batch; L->ring = ring_batches; L->cap = cap_points;
@@ -203,6 +208,11 @@ CAELO_API int caelo_seqloader_create(const char *const *paths, int64_t n, int64_
     for (int t = 0; t < threads; ++t) L->workers.emplace_back(seq_worker, L);
     *out = L;
     return CAELO_OK;
+}
+
+void seqloader_rings(const caelo_seqloader *L, int *ring_batches, int *keep_batches) {
+    *ring_batches = L->ring;
+    *keep_batches = L->keep ? L->keep_ring : 0;
 }
 
 // blocks until batch b is in its ring slot: -> the slot, the point counts of its frames (n_points_host [batch]; frames past the end: 0)

@@ -358,6 +358,11 @@ def main():
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
+    # pair (i - 1, i) draws RandomState(seed_base + i - 1), which takes seeds in [0, 2^32): both loaders refuse a base that leaves it
+    # for any frame with a pair (frame 0 has none) -- before any device work, the same way whichever loader would run
+    n_frames = len(glob.glob(os.path.join(args.scans, "*.bin"))) if args.scans else args.synthetic
+    if n_frames >= 2 and not (0 <= args.seed_base and args.seed_base + n_frames - 2 < 2 ** 32):
+        ap.error("--seed-base %d: the seeds seed_base + i - 1 of pairs i = 1 .. %d must lie in [0, 2^32)" % (args.seed_base, n_frames - 1))
 
     given = None
     if args.keypts_source != "ae" or args.features_from:

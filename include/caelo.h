@@ -493,6 +493,9 @@ int caelo_pipeline_sync_encoded(caelo_pipeline *p, int lag);
  * a 20-batch run.  A caller that paces itself (caelo_pipeline_sync_encoded between its own work) turns this off. */
 int caelo_pipeline_set_pace(caelo_pipeline *p, int lag);
 int caelo_pipeline_get_pace(const caelo_pipeline *p);   /* the pacing in effect (the library's default until set) */
+/* The HIP streams of the stages: out_host[4] = front, encoder, pair, voxel maps.  Stages that share a stream report the same handle;
+ * out_host[3] is null when the voxel maps are built on the front stream.  (Tests hold one stage back to check the hand-offs.) */
+int caelo_pipeline_streams(const caelo_pipeline *p, void **out_host);
 /* n host -> device copies on `stream` behind one call (the scans of a batch that live in pinned host memory, the producer side of
  * PoseEstimation.py:214-245): dst[i] <- src[i], bytes[i] each, asynchronous like hipMemcpyAsync; a null dst[i] or src[i] is an error,
  * a zero bytes[i] is skipped.  The pipeline does not take part -- the caller orders the copies against it (an event of its own,
@@ -508,7 +511,11 @@ int caelo_upload_many(void *const *dst, const void *const *src, const size_t *by
  * cost a pipeline running beside them 20 %), one per frame otherwise.  With a loader (caelo_seqloader, below; copy_first unused):
  * batch b0 + b comes from its ring slot (ring_host, slot_bytes) into dst[(b0 + b) % n_slots] (n_slots >= ahead + 2 device slots of
  * slot_bytes), and the point counts of its jobs (job.n) are filled in from the loader, which gets its slot back as soon as the copy is
- * through.  times_ns_host (nullable) [4]: waiting for the loader / for arrivals, submitting, copy issue + pacing. */
+ * through.  A device slot is overwritten only after the previous batch in it is through its pair stage, which reads the draws there
+ * (the calling thread waits for an event on the pair stream; without a loader only the front stage reads a slot, and the wait for the
+ * encoder covers it).  Jobs that take their host draws from the loader's keep ring (rand_host, certified) need keep_batches >=
+ * ring_batches + 7: the certifier may still read a batch's draws while the loader refills up to ring_batches + 6 batches later.
+ * times_ns_host (nullable) [4]: waiting for the loader / for arrivals, submitting, copy issue + pacing. */
 struct caelo_seqloader;
 int caelo_pipeline_run_uploading(caelo_pipeline *pipe, caelo_frame_job *jobs, int64_t k, int64_t nb, struct caelo_seqloader *loader, int64_t b0,
                                  void *const *dst, const void *const *src, const size_t *bytes, const int64_t *copy_first, int n_slots,
@@ -523,7 +530,8 @@ int caelo_pipeline_run_uploading(caelo_pipeline *pipe, caelo_frame_job *jobs, in
  * that one copy command moves a batch to a device slot of the same layout; draws_keep_host (nullable) [keep_batches][batch][CAELO_SEQ_DRAWS]
  * keeps batch b's draws at b % keep_batches for the host half (caelo_frame_job::rand_host).  _wait blocks until batch b (files b * batch ..)
  * sits in slot b % ring_batches and reports the point counts; _release hands the slot back (in order).  A file that is missing, not a
- * multiple of 16 bytes or larger than a slot fails the wait with an error naming it.  Host code only. */
+ * multiple of 16 bytes or larger than a slot fails the wait with an error naming it.  RandomState takes seeds in [0, 2^32): a
+ * seed_base that gives a frame WITH a pair (global frame index >= 1) a seed outside that range is refused.  Host code only. */
 #define CAELO_SEQ_DRAWS (CAELO_RANSAC_LEVELS * CAELO_RANSAC_MAX_TRIALS * 4)
 typedef struct caelo_seqloader caelo_seqloader;
 int caelo_host_random_sample(uint32_t seed, int64_t n, double *out_host);

@@ -218,3 +218,84 @@ def test_seqloader_reads_files_and_draws(tmp_path):
     bad.write_bytes(b"\0" * 24)
     with pytest.raises(_ffi.CaeloError, match="bad.bin"):
         run(paths[:5] + [str(bad).encode()] + paths[5:])
+
+
+def _seqloader_draws(lib, paths, first, seed_base, batch=2, cap=16):
+    """caelo_seqloader over `paths` (one batch after another) -> the draws of every file [n][6000]; raises CaeloError if refused."""
+    import ctypes as C
+    from caelo import _ffi
+    n = len(paths)
+    arr = (C.c_char_p * n)(*paths)
+    ring_h = np.zeros((2, int(lib.caelo_seqloader_slot_bytes(batch, cap))), np.uint8)
+    h = C.c_void_p()
+    _ffi.check(lib.caelo_seqloader_create(arr, n, first, batch, 2, cap, C.c_void_p(ring_h.ctypes.data), None, 0, seed_base, 2, C.byref(h)))
+    out = np.zeros((n, 6000), np.float64)
+    try:
+        slot, npts = C.c_int32(-1), (C.c_int64 * batch)()
+        for b in range((n + batch - 1) // batch):
+            _ffi.check(lib.caelo_seqloader_wait(h, b, C.byref(slot), npts))
+            dr = ring_h[slot.value, batch * cap * 16:].view(np.float64).reshape(batch, 6000)
+            out[b * batch:min(n, b * batch + batch)] = dr[:min(batch, n - b * batch)]
+            _ffi.check(lib.caelo_seqloader_release(h, b))
+    finally:
+        lib.caelo_seqloader_destroy(h)
+    return out
+
+
+def test_seqloader_seeds_span_randomstates_range_and_no_further(tmp_path):
+    """Pair (frame - 1, frame) draws RandomState(seed_base + frame - 1), whose seeds are [0, 2^32): the loader's draws equal NumPy's
+    at both ends of that range, and a seed_base that puts any frame WITH a pair outside it is refused (it used to be clamped to 0 or
+    truncated to 32 bits in silence).  Frame 0 has no pair: its seed may be -1."""
+    import ctypes as C
+    from caelo import _ffi
+    lib = _ffi.load()
+    paths = []
+    for i in range(5):
+        p = tmp_path / ("%06d.bin" % i)
+        np.zeros((3, 4), np.float32).tofile(str(p))
+        paths.append(str(p).encode())
+    top = 2 ** 32 - 1
+    for seed in (0, 1, top - 1, top):
+        one = np.empty(6000, np.float64)
+        assert lib.caelo_host_random_sample(C.c_uint32(seed), 6000, C.c_void_p(one.ctypes.data)) == 0
+        assert np.array_equal(one, np.random.RandomState(seed).random_sample(6000)), seed
+    # frames 1 .. 4 at the top of the range: seeds 2^32 - 4 .. 2^32 - 1
+    got = _seqloader_draws(lib, paths, 0, top - 3)
+    for f in range(1, 5):
+        assert np.array_equal(got[f], np.random.RandomState(top - 3 + f - 1).random_sample(6000)), f
+    # frame 0 at seed_base 0 (its seed -1 is never used), frames 1 .. 4 from seed 0
+    got = _seqloader_draws(lib, paths, 0, 0)
+    for f in range(1, 5):
+        assert np.array_equal(got[f], np.random.RandomState(f - 1).random_sample(6000)), f
+    # a later window of a sequence: frames 7 .. 11 all have pairs
+    got = _seqloader_draws(lib, paths, 7, top - 10)
+    assert np.array_equal(got[4], np.random.RandomState(top).random_sample(6000))
+    for first, base in ((0, top - 2),          # frame 4: seed 2^32
+                        (0, -1),               # frame 1: seed -1
+                        (7, top - 9),          # frame 11: seed 2^32
+                        (3, -3),               # frame 3: seed -1
+                        (0, 2 ** 62)):
+        with pytest.raises(_ffi.CaeloError, match="seed"):
+            _seqloader_draws(lib, paths, first, base)
+        with pytest.raises(ValueError):        # what the reference's generator says to the largest seed of the run
+            np.random.RandomState(base + first + len(paths) - 2 if base > 0 else base + max(first, 1) - 1)
+
+
+def test_run_sequence_loaders_refuse_the_same_seed_bases(tmp_path):
+    """run_sequence.py --scans with the native loader and with --python-loader reject the same --seed-base, with the same message and
+    before any device work: -1 (pair 1 would draw RandomState(-1)) and a base whose last pair would draw RandomState(2^32)."""
+    import subprocess
+    import sys
+    d = tmp_path / "velodyne"
+    d.mkdir()
+    for i in range(4):
+        np.zeros((8, 4), np.float32).tofile(str(d / ("%06d.bin" % i)))
+    script = os.path.join(REPO, "cae-lo_amd", "run_sequence.py")
+    for base in (-1, 2 ** 32 - 2):
+        errs = []
+        for extra in ([], ["--python-loader"]):
+            r = subprocess.run([sys.executable, script, "--scans", str(d), "--seed-base", str(base), "--out", str(tmp_path / "p.txt")] + extra,
+                               capture_output=True, text=True, timeout=300)
+            assert r.returncode == 2 and "must lie in [0, 2^32)" in r.stderr, (base, extra, r.returncode, r.stderr[-2000:])
+            errs.append(r.stderr.strip().splitlines()[-1])
+        assert errs[0] == errs[1]
