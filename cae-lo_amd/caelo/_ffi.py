@@ -49,6 +49,7 @@ ST_TIES_LEFT = 64   # status bit of the EXTRACT_EXACT_PATCHES mode: a kd build g
 EXTRACT_GIVEN_KEYPTS, EXTRACT_GIVEN_ROWS = 8, 16   # the caller's key points (caelo_extract / jobs); the caller's rows (jobs only)
 ST_BAD_KEYPTS = 128   # status bit of EXTRACT_GIVEN_KEYPTS: K outside [1, 1024], or a coordinate non-finite or beyond GIVEN_KEYPTS_RANGE
 GIVEN_KEYPTS_RANGE = 16384.0   # metres, include/caelo.h CAELO_GIVEN_KEYPTS_RANGE
+EXTRACT_CORRECT_PC = 32   # the scan is rotated by the context's calibration angle first (caelo_set_calib_angle; CorrectPC)
 ABI_VERSION = 6   # include/caelo.h CAELO_ABI_VERSION
 KP_NN_MAX_K, KP_NN_MAX_THRESHOLDS = 65536, 16   # include/caelo.h CAELO_KP_NN_MAX_K / CAELO_KP_NN_MAX_THRESHOLDS (caelo_kp_nn_pairs)
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
@@ -79,6 +80,9 @@ SIGNATURES = [
     ("caelo_set_respond_weights", c_int, [c_vp] + [c_vp] * 4),
     ("caelo_set_encoder_weights", c_int, [c_vp] + [c_vp] * 10),
     ("caelo_set_encoder_reference", c_int, [c_vp, c_int]),
+    ("caelo_correct_pc", c_int, [c_vp, c_vp, c_i64, c_int, C.c_double, c_vp, c_vp]),
+    ("caelo_set_calib_angle", c_int, [c_vp, C.c_double]),
+    ("caelo_get_calib_angle", C.c_double, [c_vp]),
     ("caelo_project", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_respond", c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_vp]),
     ("caelo_keypoints_ws_bytes", c_i64, []),

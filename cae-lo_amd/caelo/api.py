@@ -13,6 +13,7 @@ tuples / dtypes, served by the HIP engine.
     Match.SolveRT / RANSAC4RT             :138/:162
     Match.SolveRelativePose               :241  SolveRelativePose(PC0, F0, W0, PC1, F1, W1)
     keras.models.load_model (Match.py:313,324)  load_model(h5_path) -> object with .predict
+    Transformations.CorrectPC             :28   CorrectPC(PC, CalibAngle)
 
 Arguments may be NumPy arrays (results come back as NumPy, like the reference) or torch tensors on
 the GPU (results stay on the GPU).  Every array-level function runs on the GPU; there is no CPU
@@ -51,6 +52,18 @@ def _out(t, as_np):
 
 
 # ---------------------------------------------------------------------------------------------
+def CorrectPC(PC, CalibAngle):
+    """Transformations.py:28-39 -> PC_ [N,3] f32 (NumPy): every point rotated by ``CalibAngle`` degrees about p x z^ on the device
+    (caelo_correct_pc), in the reference's float32 arithmetic under NumPy >= 2 (caelo/correct.py).  PC: a float32
+    NumPy array [N,3]; anything else, or a non-finite angle, is a ValueError.  Points with x = y = 0 come back NaN, as there."""
+    from . import correct
+    correct.check_args(PC, CalibAngle)
+    if PC.shape[0] == 0:
+        return PC.copy()
+    e = default_engine()
+    return e.correct_pc(torch.from_numpy(np.ascontiguousarray(PC)).to(e.device), CalibAngle).cpu().numpy()
+
+
 def ProjectPC2SphericalRing(PC):
     """SphericalRing.py:72-94 -> (Image_float [69,1800,5] f32, GridCounter [69,1800] i32)."""
     assert PC.shape[0] > 3 and PC.shape[1] == 4

@@ -58,12 +58,13 @@ def raise_status(st):
         raise _ffi.CaeloError("voxel map overflow")
 
 
-def extract_mode(exact_voxels=False, dedup=True, exact_patches=False, given_keypts=False, given_rows=False):
+def extract_mode(exact_voxels=False, dedup=True, exact_patches=False, given_keypts=False, given_rows=False, correct_pc=False):
     """The CAELO_EXTRACT_* mode word of caelo_extract / caelo_frame_job."""
     if given_rows:
         return _ffi.EXTRACT_GIVEN_ROWS
     return ((_ffi.EXTRACT_EXACT_VOXELS if exact_voxels else 0) | (0 if dedup else _ffi.EXTRACT_NO_DEDUP)
-            | (_ffi.EXTRACT_EXACT_PATCHES if exact_patches else 0) | (_ffi.EXTRACT_GIVEN_KEYPTS if given_keypts else 0))
+            | (_ffi.EXTRACT_EXACT_PATCHES if exact_patches else 0) | (_ffi.EXTRACT_GIVEN_KEYPTS if given_keypts else 0)
+            | (_ffi.EXTRACT_CORRECT_PC if correct_pc else 0))
 
 
 def _given_pts(eng, key_pts):
@@ -214,7 +215,8 @@ class Pipeline:
         _ffi.check(self.eng.lib.caelo_pipeline_streams(self.h, out))
         return dict(zip(("front", "encoder", "pair", "voxel"), (out[i] for i in range(4))))
 
-    def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None, exact_patches=False):
+    def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None, exact_patches=False,
+              calib_angle=None):
         """The run's jobs as one record array, filled column-wise, handed over in ONE foreign call (a ctypes call per frame
         costs ~10 us: 380 us for a 20-frame run, most of it before the first launch)."""
         k = len(ptrs)
@@ -222,6 +224,8 @@ class Pipeline:
         idx = np.arange(k, dtype=np.uint64)
         jobs["pc"], jobs["n"] = ptrs, counts
         jobs["dist_channels"], jobs["mode"] = int(dist_channels), extract_mode(exact_voxels, dedup, exact_patches)
+        if calib_angle is not None:   # the scans are corrected on the device first (CAELO_EXTRACT_CORRECT_PC, the context's angle)
+            jobs["mode"] |= np.where(self.eng._calib_frames(calib_angle, k), _ffi.EXTRACT_CORRECT_PC, 0).astype(np.int32)
         jobs["rows"] = out.rows.data_ptr() + idx * (MAX_K * 256)
         jobs["key_pixels"] = out.key_pixels.data_ptr() + idx * (MAX_K * 16)
         jobs["n_key"] = out.n_key.data_ptr() + idx * 4
@@ -287,7 +291,7 @@ class Pipeline:
         _ffi.check(self.eng.lib.caelo_pipeline_sync_encoded(self.h, int(lag)))
 
     def run(self, scans, rands=None, prev=None, dist_channels=5, exact_voxels=False, out=None, pairs=True, dedup=True, on_batch=None,
-            on_encoded=None, certify=False, rands_host=None, publish=True, exact_patches=False, keypts=None, rows_given=None):
+            on_encoded=None, certify=False, rands_host=None, publish=True, exact_patches=False, keypts=None, rows_given=None, calib_angle=None):
         """scans: K device tensors [n,4] f32; rands: K device tensors of RANSAC draws ([1500,4] f64).
         Frame i is matched against frame i-1 (pose in ``result[i]``); frame 0 against ``prev``
         (FrameFeatures) when given; ``pairs=False`` extracts only (BASELINE configs[1]).  Returns a FrameBatch; the
@@ -310,7 +314,11 @@ class Pipeline:
         where the kind changes, pairs chain across): ``keypts[i]`` = [K,3] f32 key points of frame i (CAELO_EXTRACT_GIVEN_KEYPTS, see
         ``Engine.extract``); ``rows_given[i]`` = [K,64] f32 rows (descriptor zero-padded to columns 0:60 | xyz 60:63 | valid 63,
         ``keysources.rows_from_features``) that are matched as they are (CAELO_EXTRACT_GIVEN_ROWS, isLoadFeaturesFromFile): no scan
-        needed (``scans[i]`` may be None), ``out.status[i]`` / ``flags[i]`` are zero and ``key_pixels[i]`` -1."""
+        needed (``scans[i]`` may be None), ``out.status[i]`` / ``flags[i]`` are zero and ``key_pixels[i]`` -1.
+        ``calib_angle``: degrees; every scan is first corrected by the reference's CorrectPC on the device (``Engine.extract``), one
+        launch per batch at the head of the front stage; the caller's scans are not written.  A sequence with one entry per frame
+        (the angle, or None for a frame that is not corrected) mixes both kinds: a batch is split where the kind changes.  Given key
+        points and given rows are never corrected (the reference corrects scans only)."""
         eng, lib, k = self.eng, self.eng.lib, len(scans)
         out = out or FrameBatch(eng, k)
         assert out.k >= k and (not pairs or len(rands) >= k)
@@ -326,7 +334,7 @@ class Pipeline:
             assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         _t0 = time.perf_counter()
         jobs = self._jobs([0 if pc is None else pc.data_ptr() for pc in scans], [0 if pc is None else pc.shape[0] for pc in scans], rands,
-                          prev, out, pairs, dist_channels, exact_voxels, dedup, certify, rands_host, exact_patches)
+                          prev, out, pairs, dist_channels, exact_voxels, dedup, certify, rands_host, exact_patches, calib_angle)
         if modes is not None:
             jobs["mode"] = np.where(modes == 1, jobs["mode"] | _ffi.EXTRACT_GIVEN_KEYPTS, np.where(modes == 2, _ffi.EXTRACT_GIVEN_ROWS, jobs["mode"]))
         _t1 = time.perf_counter()
@@ -434,7 +442,7 @@ class Pipeline:
         self.pace = int(lag)
 
     def run_uploading(self, host_scans, rands=None, prev=None, dist_channels=5, out=None, pairs=True, dedup=True, ahead=4, certify=False,
-                      rands_host=None, exact_patches=False):
+                      rands_host=None, exact_patches=False, calib_angle=None):
         """``run`` for scans that live in (pinned) HOST memory: a copy stream uploads batch b + ``ahead`` while the pipeline works on
         batch b, into ``ahead + 2`` sets of device buffers -- the overlap of the reference's producer process, which prepares
         frame i + 1 while frame i is matched (PoseEstimation.py:214-245).  The loop runs natively (caelo_pipeline_run_uploading) and
@@ -448,7 +456,8 @@ class Pipeline:
         memory).  Device-side waits for the same hand-overs cost 8 - 15 % of the resident rate EACH, however rarely they were issued
         (DESIGN.md 5).  Scans of a batch that are views of ONE pinned block at a fixed pitch go up behind one copy command per batch,
         other scans behind one per frame.  Device tensors are refused (ValueError): copying them with hipMemcpyDefault would change
-        the copy of the measured one-block path, and ``run`` takes them as they are.  ``exact_patches``: as in ``run``."""
+        the copy of the measured one-block path, and ``run`` takes them as they are.  ``exact_patches``, ``calib_angle``: as in ``run`` (the
+        correction runs on the device slot's copy, after it has landed)."""
         k, B = len(host_scans), self.batch
         out = out or FrameBatch(self.eng, k)
         assert out.k >= k and (not pairs or len(rands) >= k) and ahead >= 1
@@ -483,21 +492,22 @@ class Pipeline:
 
         def build(fb):
             pcs = fb + (np.arange(k, dtype=np.uint64) % np.uint64(B)) * np.uint64(stride)
-            jobs = self._jobs(pcs, nbytes // np.uint64(16), rands, prev, out, pairs, dist_channels, False, dedup, certify, rands_host, exact_patches)
+            jobs = self._jobs(pcs, nbytes // np.uint64(16), rands, prev, out, pairs, dist_channels, False, dedup, certify, rands_host, exact_patches,
+                              calib_angle)
             if pitch:   # one copy per batch: first frame's slot, first frame's source, bytes up to the end of the last frame
                 return jobs, (pcs[first], src[first], src[last] + nbytes[last] - src[first], np.arange(len(first) + 1))
             return jobs, (pcs, src, nbytes, np.r_[first, k])   # one copy per frame
         return self._upload_run(k, ahead, B * stride, build, out, certify, pairs)
 
     def run_loaded(self, loader, b0, nb, prev=None, out=None, pairs=True, dist_channels=5, dedup=True, certify=True, ahead=4, publish=True,
-                   exact_patches=False):
+                   exact_patches=False, calib_angle=None):
         """Batches [b0, b0 + nb) of a SeqLoader through the pipeline: a batch's scans AND draws go up behind ONE copy command (the loader's
         slot layout, mirrored on the device), the jobs are built column-wise for the whole call, and nothing here is per-frame Python.
         The loop of ``run_uploading``, fed by the loader.  A device slot here also holds the batch's draws, which its PAIR stage reads:
         before the copy that overwrites the slot of batch b - 2 the calling thread waits for an event recorded on the pair stream after
         that batch's pairs (the encoder wait of ``run_uploading`` does not cover them).  With ``certify`` the certifier reads the draws
         from the loader's keep ring, which must hold ring + 7 batches (caelo_pipeline::CERT_RING + 1 beyond the loader's ring; refused
-        otherwise).  ``exact_patches``: as in ``Pipeline.run``.  -> (FrameBatch, frames)."""
+        otherwise).  ``exact_patches``, ``calib_angle``: as in ``Pipeline.run``.  -> (FrameBatch, frames)."""
         B = self.batch
         assert loader.batch == B and ahead >= 1 and b0 + nb <= loader.n_batches
         k = min(loader.n - b0 * B, nb * B)
@@ -509,7 +519,7 @@ class Pipeline:
 
         def build(fb):   # a slot: the batch's scans at the loader's capacity, then its draws
             return self._jobs(fb + j * np.uint64(loader.cap * 16), np.zeros(k, np.int64), fb + np.uint64(loader.scan_bytes) + j * np.uint64(6000 * 8),
-                              prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None, exact_patches), None
+                              prev, out, pairs, dist_channels, False, dedup, certify, rnd_h if certify else None, exact_patches, calib_angle), None
         return self._upload_run(k, ahead, loader.slot_bytes, build, out, certify, pairs, publish, loader, b0), k
 
     def _upload_run(self, k, ahead, slot_bytes, build, out, certify, pairs, publish=True, loader=None, b0=0):
@@ -653,6 +663,45 @@ class Engine:
     def set_encoder_reference(self, on=True):
         """caelo_set_encoder_reference: stage 1 of this engine's encoder = the exact-f32 kernel (precision reference; slower)."""
         _ffi.check(self.lib.caelo_set_encoder_reference(self.ctx, 1 if on else 0))
+
+    def set_calib_angle(self, deg):
+        """caelo_set_calib_angle: the angle (degrees) the CAELO_EXTRACT_CORRECT_PC mode rotates scans by; a context setting like the
+        weights (0 until set).  ValueError for a non-finite angle."""
+        deg = float(deg)
+        if not np.isfinite(deg):
+            raise ValueError("the calibration angle must be a finite number of degrees (got %r)" % (deg,))
+        _ffi.check(self.lib.caelo_set_calib_angle(self.ctx, deg))
+
+    def get_calib_angle(self):
+        return float(self.lib.caelo_get_calib_angle(self.ctx))
+
+    def _calib_frames(self, calib_angle, k):
+        """``calib_angle=`` of the pipeline's job builder: a number (every frame) or one entry per frame (the angle, or None for a frame
+        that is not corrected; the context holds ONE angle, so the entries that are not None must agree).  Sets the context's angle ->
+        bool [k], the frames that get the mode bit."""
+        if np.isscalar(calib_angle):
+            on, angles = np.ones(k, dtype=bool), {float(calib_angle)}
+        else:
+            assert len(calib_angle) == k, "calib_angle: a number, or one entry per frame"
+            on = np.array([a is not None for a in calib_angle], dtype=bool)
+            angles = {float(a) for a in calib_angle if a is not None}
+        if len(angles) > 1:
+            raise ValueError("one calibration angle per run (got %s): the angle is a context setting" % sorted(angles))
+        if angles:
+            self.set_calib_angle(angles.pop())
+        return on
+
+    def correct_pc(self, pc, angle):
+        """caelo_correct_pc (CorrectPC, Transformations.py:28-39): pc [N,3] or [N,4] f32 (device) rotated point by point by ``angle``
+        degrees about p x z^ -> a new tensor of the same shape; column 3 (intensity) is copied bit for bit.  No host sync.  A point with
+        x = y = 0 becomes NaN, as in the Python reference."""
+        assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] in (3, 4) and pc.is_contiguous()
+        angle = float(angle)
+        if not np.isfinite(angle):
+            raise ValueError("the calibration angle must be a finite number of degrees (got %r)" % (angle,))
+        out = torch.empty_like(pc)
+        _ffi.check(self.lib.caelo_correct_pc(self.ctx, _ptr(pc), pc.shape[0], pc.shape[1], angle, _ptr(out), self.stream))
+        return out
 
     def lane_faults(self):
         """caelo_lane_faults: wavefronts of the pose kernels whose lanes disagreed on a hypothesis they all derive from the
@@ -1091,7 +1140,8 @@ class Engine:
         return _ffi.PoseResult.from_buffer_copy(res.cpu().numpy().tobytes())
 
     # ---- fused hot path ------------------------------------------------------------------------------
-    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True, exact_patches=False, key_pts=None):
+    def extract(self, pc, dist_channels=5, vmap=None, rows=None, exact_voxels=False, dedup=True, exact_patches=False, key_pts=None,
+                calib_angle=None):
         """scan [N,4] f32 (device) -> FrameFeatures, ONE C-ABI call (caelo_extract), no host sync:
         project -> response CNN -> keypoints -> voxelize -> patch gather -> 3x encoder.
         dist_channels: 5 = demo calling mode (SphericalRing.py:414), 3 = batch mode
@@ -1105,10 +1155,16 @@ class Engine:
         ``extract`` + ``resolve_ties`` give, in the same single call.  ``status[0]`` may carry ST_TIES_LEFT (see ``note_ties_left``).
         ``key_pts``: [K,3] f32 key points of another source (CAELO_EXTRACT_GIVEN_KEYPTS: GetPatchesList + GetFeaturesFromPatches on
         them, PoseEstimation.py:26-45) instead of the detector's; K in [1, 1024] and |x|, |y|, |z| <= 16384 m, checked on the device
-        (``status[0]`` & ST_BAD_KEYPTS, raised by ``raise_status`` as ValueError).  ``key_pixels`` are then -1."""
+        (``status[0]`` & ST_BAD_KEYPTS, raised by ``raise_status`` as ValueError).  ``key_pixels`` are then -1.
+        ``calib_angle``: degrees; the scan is first corrected by the reference's CorrectPC (CAELO_EXTRACT_CORRECT_PC: sets the
+        context's angle and the mode bit) into storage of the voxel map, inside the same call -- ``extract(correct_pc(pc, a))`` bit
+        for bit; ``pc`` is not written and given key points are not corrected.  A scan with a point on the z axis then reports
+        ST_NONFINITE (the reference's NaN)."""
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] == 4 and pc.is_contiguous()
         ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
         vmap = vmap or self.voxmap(max(self.max_points, pc.shape[0]))
+        if calib_angle is not None:
+            self.set_calib_angle(calib_angle)
         rows = self.empty((MAX_K, 64), torch.float32) if rows is None else rows
         assert rows.shape == (MAX_K, 64) and rows.is_contiguous()
         kpix = self.empty((MAX_K, 2), torch.int64)
@@ -1121,7 +1177,7 @@ class Engine:
         status = self.empty((4,), torch.int32)
         base = rows.data_ptr()
         _ffi.check(self.lib.caelo_extract(self.ctx, vmap.h, _ptr(pc), pc.shape[0], dist_channels,
-                                          extract_mode(exact_voxels, dedup, exact_patches, key_pts is not None),
+                                          extract_mode(exact_voxels, dedup, exact_patches, key_pts is not None, correct_pc=calib_angle is not None),
                                           C.c_void_p(base + 240), 64, C.c_void_p(base), 64, C.c_void_p(base + 252), 64,
                                           _ptr(kpix), _ptr(nkey), _ptr(flags), _ptr(status), _ptr(ws),
                                           self.stream))

@@ -65,6 +65,7 @@ struct caelo_ctx {
     bool has_enc;
     bool enc_reference;   // caelo_set_encoder_reference: stage 1 = the exact-f32 k_enc_stage1 (precision reference)
     int32_t *faults;  // device counter of the pair kernels' lane-agreement checks (match.hip); 0 on healthy hardware
+    double calib_angle;  // caelo_set_calib_angle: degrees, what CAELO_EXTRACT_CORRECT_PC rotates a scan by (correct.hip); 0 until set
 };
 
 // ---- voxel map ---------------------------------------------------------------------------------
@@ -120,6 +121,9 @@ struct caelo_voxmap {
     char *xo_base;
     size_t xo_bytes;
     int xo_frames;
+    // CAELO_EXTRACT_CORRECT_PC (correct.hip): the corrected scan [max_points][4] f32 the front kernels read instead of the caller's;
+    // allocated by correct_prepare on the first use of the mode, null until then
+    float *corr;
 };
 
 void kd_destroy(caelo_voxmap *m);
@@ -351,6 +355,11 @@ int extract_encode_launch(const caelo_extract_args &a, hipStream_t s);  // the f
 int exact_patches_prepare(caelo_voxmap *const *maps, int n_frames);
 void exact_patches_clear_item(caelo_voxmap *m, caelo_clear_list &list);
 int exact_patches_redo(caelo_voxmap *const *maps, const caelo_frame_set &fs, const caelo_extract_args *args, int n, hipStream_t s);
+
+// CAELO_EXTRACT_CORRECT_PC (correct.hip).  prepare: the maps' corrected-scan storage (host only, before any launch of the batch).
+// set: the scans of the set rotated by the context's calibration angle into that storage, one launch (blockIdx.y = frame).
+int correct_prepare(caelo_voxmap *const *maps, int n);
+int correct_set(const caelo_extract_args *args, int n, hipStream_t s);
 
 #define CAELO_KP_HIST_BINS 2048
 

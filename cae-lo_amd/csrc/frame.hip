@@ -200,6 +200,7 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     const bool exact_vox = exact_pat || (args[0].mode & CAELO_EXTRACT_EXACT_VOXELS) != 0;
     const bool dd = dedup_enabled(args[0].mode);
     const bool given = (args[0].mode & CAELO_EXTRACT_GIVEN_KEYPTS) != 0;
+    const bool correct = (args[0].mode & CAELO_EXTRACT_CORRECT_PC) != 0;   // the scans rotated into the maps' storage first (correct.hip)
     caelo_frame_set fs = {};
     fs.n = n;
     caelo_clear_list cl[CAELO_FB_MAX];
@@ -210,12 +211,13 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     }
     int rc = CAELO_OK;
     if (exact_pat && (rc = exact_patches_prepare(maps, n))) return rc;   // (allocates once, before the set's first launch)
+    if (correct && ((rc = correct_prepare(maps, n)) || (rc = correct_set(args, n, s)))) return rc;   // (the same; then the head of the chain)
     for (int i = 0; i < n; ++i) {
         const caelo_extract_args &a = args[i];
         char *ws = (char *)a.ws;
         caelo_frame_dev &d = fs.f[i];
         frame_dev_set_map(d, a.map);
-        d.pc = a.pc; d.n = a.n; d.pc_stride = 4; d.dist_c = a.dist_channels;
+        d.pc = correct ? a.map->corr : a.pc; d.n = a.n; d.pc_stride = 4; d.dist_c = a.dist_channels;
         d.ring = (float *)(ws + L.ring); d.counter = nullptr; d.winner = (int32_t *)(ws + L.winner);  // (occupied = has a winner)
         d.resp = (float *)(ws + L.resp); d.cand = (unsigned long long *)(ws + L.cand); d.cand_count = (int32_t *)(ws + L.cand_count);
         d.key_pixels = a.key_pixels; d.key_pts = a.key_pts; d.kp_ld = a.kp_ld; d.valid = a.valid; d.valid_ld = a.valid_ld;

@@ -765,6 +765,7 @@ CAELO_API int caelo_pipeline_submit(caelo_pipeline *p, const caelo_frame_job *jo
     if (job->mode & CAELO_EXTRACT_GIVEN_ROWS) {   // the rows are the input: no scan, nothing extracted
         CAELO_REQUIRE(job->rows && job->n_key, "null frame buffer");
         CAELO_REQUIRE(!(job->mode & CAELO_EXTRACT_GIVEN_KEYPTS), "CAELO_EXTRACT_GIVEN_ROWS and CAELO_EXTRACT_GIVEN_KEYPTS exclude each other");
+        CAELO_REQUIRE(!(job->mode & CAELO_EXTRACT_CORRECT_PC), "CAELO_EXTRACT_GIVEN_ROWS reads no scan: nothing for CAELO_EXTRACT_CORRECT_PC to correct");
     } else {
         CAELO_REQUIRE(job->pc && job->rows && job->key_pixels && job->n_key && job->flags && job->status, "null frame buffer");
         CAELO_REQUIRE(job->n > 3, "PC.shape[0] > 3 (SphericalRing.py:73)");
@@ -782,6 +783,11 @@ CAELO_API int caelo_pipeline_submit(caelo_pipeline *p, const caelo_frame_job *jo
     if ((job->mode & CAELO_EXTRACT_EXACT_PATCHES) && !(job->mode & CAELO_EXTRACT_GIVEN_ROWS) && !(p->maps[0]->xo_base && p->maps[0]->xo_frames >= p->batch)) {
         // the first job in this mode: kd storage + ordering scratch of every frame slot's map, before any launch of its batch
         const int rc = exact_patches_prepare(p->maps, p->batch);
+        if (rc) return rc;
+    }
+    if ((job->mode & CAELO_EXTRACT_CORRECT_PC) && !(job->mode & CAELO_EXTRACT_GIVEN_ROWS)) {
+        // (the first job in this mode allocates every frame slot's corrected-scan buffer, before any launch of its batch)
+        const int rc = correct_prepare(p->maps, p->batch);
         if (rc) return rc;
     }
     if (!p->pending.empty() && (p->pending[0].mode != job->mode)) {  // the frames of a launch share one mode

@@ -97,6 +97,7 @@ CAELO_API void caelo_voxmap_destroy(caelo_voxmap *m) {
     kd_destroy(m);
     if (m->base) (void)hipFree(m->base);
     if (m->scratch) (void)hipFree(m->scratch);
+    if (m->corr) (void)hipFree(m->corr);
     delete m;
 }
 

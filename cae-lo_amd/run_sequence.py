@@ -4,6 +4,7 @@
 
     python run_sequence.py --synthetic 20 --out poses_/00.txt
     python run_sequence.py --scans <seq>/velodyne --calib <calib>/00/calib_.txt --out poses_/00.txt --save-artifacts
+    python run_sequence.py --scans <raw KITTI seq>/velodyne --calib-angle 0.22 --out poses_/00.txt   # CorrectPC on the fly
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_sequence.py --synthetic 800 ...
 
 Frames are sharded contiguously over the ranks (one process per GPU); every rank runs its frames through the
@@ -133,8 +134,13 @@ def _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, host_redo, tie_lo
     return cat(rel, (12,)), cat(ok, ()), cat(thr, ()), cat(nin, ()), first, prev
 
 
+def _corrected(eng, scan, calib_angle):
+    """A tied frame's scan for the host redo (Engine.redo_ties): corrected like the pipeline corrected it."""
+    return scan if calib_angle is None else eng.correct_pc(scan, calib_angle)
+
+
 def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-              loader_threads=4, certify=True, native_ties=False, given=None, records=None):
+              loader_threads=4, certify=True, native_ties=False, given=None, records=None, calib_angle=None):
     """Frames [lo, hi) of this rank.  Returns per-pair rows for pairs (i-1, i), i in (lo, hi) -- the pair (lo-1, lo)
     is the caller's (it needs the previous rank's last frame) -- plus the first and last frame's features.
 
@@ -149,6 +155,8 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
     caelo.keysources); the chunk then goes through Pipeline.run on resident scans (keypts= / rows_given=), with the tie-split patches
     redone inside the pipeline unless ``strict_ties`` is off.
     ``records``: a list that receives each chunk's (iterations, n_pairs) [k] i32, the pairs in the order of the returned rows.
+    ``calib_angle``: degrees; every scan is corrected on the device inside its batch (Pipeline.run(calib_angle=...)); given key points
+    and rows are not.
     """
     import queue
     import threading
@@ -247,22 +255,23 @@ def run_local(eng, load, lo, hi, seed_base, chunk, dist_channels, batch_frames, 
             kp = [a if kind == "keypts" else None for kind, a in gv]
             rw = [a if kind == "rows" else None for kind, a in gv]
             batch = pipe.run([None if rw[j] is not None else scans[j].to(eng.device, non_blocking=True) for j in range(k)], rands, prev=prev,
-                             dist_channels=dist_channels, certify=certify, rands_host=rands_host, exact_patches=native_ties, keypts=kp, rows_given=rw)
+                             dist_channels=dist_channels, certify=certify, rands_host=rands_host, exact_patches=native_ties, keypts=kp, rows_given=rw,
+                             calib_angle=calib_angle)
         else:
             batch = pipe.run_uploading(scans, rands, prev=prev, dist_channels=dist_channels, certify=certify, rands_host=rands_host,
-                                       exact_patches=native_ties)
+                                       exact_patches=native_ties, calib_angle=calib_angle)
         ht["pipeline"] += time.time() - t_
-        return batch, False, lambda j: scans[j].to(eng.device), lambda j: (draws_d[j], dn[j])
+        return batch, False, lambda j: _corrected(eng, scans[j].to(eng.device), calib_angle), lambda j: (draws_d[j], dn[j])
 
     return _run_chunks(eng, lo, hi, chunk, submit, ht, t_setup, keep, strict_ties and not native_ties, tie_log, certify, records)
 
 
 def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_frames, keep=None, strict_ties=True, tie_log=None, host_times=None,
-                    loader_threads=16, certify=True, device_results=False, native_ties=False, records=None):
+                    loader_threads=16, certify=True, device_results=False, native_ties=False, records=None, calib_angle=None):
     """run_local for scans that are FILES (round 6): the native loader (caelo_seqloader: pread into a pinned ring + the RANSAC draws,
     csrc/seqload.hip) works ahead on its own threads, a chunk of batches goes through Pipeline.run_loaded (one copy command per batch
     for scans and draws, jobs built column-wise).  Same returns as run_local; same bits (the draws are NumPy's stream, the pipeline
-    is the same)."""
+    is the same).  ``calib_angle``: as in run_local (the correction runs on the device slot, after the batch's copy has landed)."""
     from caelo.engine import SeqLoader
     t_setup = time.time()
     ht = _host_times(host_times)
@@ -298,7 +307,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
     def submit(ci, c0, c1, prev):
         t_ = time.time()
         batch, _ = pipe.run_loaded(loader, (c0 - lo) // B, (c1 - c0 + B - 1) // B, prev=prev, out=outs[ci % 2], dist_channels=dist_channels,
-                                   certify=certify, publish=publish, exact_patches=native_ties)
+                                   certify=certify, publish=publish, exact_patches=native_ties, calib_angle=calib_angle)
         ht["pipeline"] += time.time() - t_
         t = pipe.last_upload_times   # (ms; this report is in seconds)
         ht["starved"] += t["starved_ms"] / 1e3
@@ -306,7 +315,7 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
             ht["loaded_" + k_[:-3] + "_s"] = ht.get("loaded_" + k_[:-3] + "_s", 0.0) + v_ / 1e3
 
         def scan(j):   # (a tied frame's scan is read again: rare)
-            return torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device)
+            return _corrected(eng, torch.from_numpy(stageio.read_scan(files[c0 + j])).to(eng.device), calib_angle)
 
         def draws(j):
             d = ransac_draws(seed_base + c0 + j - 1)
@@ -355,6 +364,11 @@ def main():
     ap.add_argument("--keypts-dir", help="directory of the --keypts-source files")
     ap.add_argument("--features-from", help="directory of <frame:06d>.bin.mat files (KeyPts / Features / Weights, isLoadFeaturesFromFile, "
                                             "PoseEstimation.py:49-66): only the pair stage runs on them")
+    ap.add_argument("--calib-angle", type=float, default=None, metavar="DEG",
+                    help="correct every scan by the reference's CorrectPC (Transformations.py:28-39: each point rotated by DEG degrees about "
+                         "p x z, the HDL-64E's vertical-angle calibration; raw KITTI scans: 0.22) on the device, inside the batch launch, before "
+                         "anything else reads it -- no corrected copy of the data set on disk.  Default: no correction.  Only scans are "
+                         "corrected, as in the reference: key points given by --keypts-source / --features-from are used as they are")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
@@ -364,6 +378,8 @@ def main():
     if n_frames >= 2 and not (0 <= args.seed_base and args.seed_base + n_frames - 2 < 2 ** 32):
         ap.error("--seed-base %d: the seeds seed_base + i - 1 of pairs i = 1 .. %d must lie in [0, 2^32)" % (args.seed_base, n_frames - 1))
 
+    if args.calib_angle is not None and not np.isfinite(args.calib_angle):
+        ap.error("--calib-angle must be a finite number of degrees")
     given = None
     if args.keypts_source != "ae" or args.features_from:
         if args.keypts_source != "ae" and args.features_from:
@@ -451,12 +467,12 @@ def main():
         rel, ok, thr, nin, first, last = run_local_files(eng, files, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                          args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
                                                          loader_threads=args.loader_threads, certify=not args.no_certify, device_results=args.save_artifacts,
-                                                         native_ties=args.native_ties, records=records)
+                                                         native_ties=args.native_ties, records=records, calib_angle=args.calib_angle)
     else:
         rel, ok, thr, nin, first, last = run_local(eng, load, lo, hi, args.seed_base, args.chunk, args.dist_channels,
                                                    args.batch, keep, strict_ties=not args.no_strict_ties, tie_log=tie_log, host_times=host_times,
                                                    loader_threads=args.loader_threads, certify=not args.no_certify, native_ties=args.native_ties,
-                                                   given=given, records=records)
+                                                   given=given, records=records, calib_angle=args.calib_angle)
     if tie_log:
         print("rank %d: %d frame(s) redone in scikit-learn's tie order (%d patches): %s" % (
             rank, len(tie_log), sum(n for _, n in tie_log), [f for f, _ in tie_log][:20]), file=sys.stderr)

@@ -80,6 +80,14 @@ typedef enum {
                                           * index fits the 20-bit packing of the voxel tables (no aliasing), so a point off the scan or off
                                           * the voxel grid -- negative side included -- gets exactly the reference's patch (empty far away) */
 
+#define CAELO_EXTRACT_CORRECT_PC 32   /* caelo_extract / caelo_frame_job.mode bit: the scan is first rotated by the context's calibration angle
+                                        (caelo_set_calib_angle; CorrectPC, Transformations.py:28-39) into storage the library owns -- the voxel
+                                        map's (caelo_extract) or the frame slot's (pipeline), max_points x 16 B, allocated by the first call in
+                                        this mode -- and ring image and voxel map are built from that copy: the results of
+                                        caelo_correct_pc + the same call without the bit, bit for bit.  The caller's pc is never written.  In the
+                                        pipeline: one launch per batch at the head of the front stage.  A point on the z axis becomes NaN, as in
+                                        the Python reference, and the frame reports CAELO_ST_NONFINITE.  Not with CAELO_EXTRACT_GIVEN_ROWS */
+
 typedef struct caelo_ctx caelo_ctx;
 typedef struct caelo_voxmap caelo_voxmap;
 
@@ -113,6 +121,18 @@ int caelo_set_encoder_weights(caelo_ctx *ctx, const float *w1_host /*[27][1][8]*
  * An explicit, per-context choice: the library reads NO environment variable that changes arithmetic (no reference counterpart:
  * PatchEncoder.predict, Match.py:131-133, has one arithmetic). */
 int caelo_set_encoder_reference(caelo_ctx *ctx, int on);
+
+/* CorrectPC  (Transformations.py:28-39; BatchPreprocess.py:70-88 BatchCorrectPC): every point rotated by calib_angle_deg about the
+ * axis p x z^, the HDL-64E's vertical-angle calibration of the KITTI scans.  pc, out [n][stride] f32 (device), stride 3 or 4; with
+ * stride 4 the fourth column (intensity) is copied bit for bit.  out may not overlap pc; n = 0 does nothing; a non-finite angle is
+ * refused.  Arithmetic: the reference's float32 operations under NumPy >= 2 (NEP 50) one by one up to the rotation matrix (its
+ * bits); the final product is p'_i = (R_i0 x + R_i1 y) + R_i2 z without contraction, where the reference calls its BLAS (DESIGN.md
+ * 5.8).  A point with x = y = 0 gives NaN, as there.
+ * caelo_set_calib_angle: the angle (degrees, finite; 0 until set) that CAELO_EXTRACT_CORRECT_PC applies -- a context setting like
+ * the weights, read when a call or a pipeline batch is launched. */
+int caelo_correct_pc(caelo_ctx *ctx, const float *pc, int64_t n, int stride, double calib_angle_deg, float *out, void *stream);
+int caelo_set_calib_angle(caelo_ctx *ctx, double deg);
+double caelo_get_calib_angle(caelo_ctx *ctx);
 
 /* ProjectPC2SphericalRing  (SphericalRing.py:72-94)
  * pc [n][4] f32 -> ring [69][1800][5] f32, counter [69][1800] i32.  workspace: winner [69*1800] i32. */
