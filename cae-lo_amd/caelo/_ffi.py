@@ -159,6 +159,8 @@ SIGNATURES = [
     ("caelo_pipeline_expect", c_int, [c_vp, c_i64]),
     ("caelo_lane_faults", c_int, [c_vp, C.POINTER(c_i64)]),
     ("caelo_kp_nn_pairs", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
+    ("caelo_register_pairs_ws_bytes", c_i64, [c_i64]),
+    ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 ]
 
 _lib = None

@@ -400,3 +400,22 @@ def SolveRelativePose(OriPC0, OriCodes0, Weights0, OriPC1, OriCodes1, Weights1, 
     if as_np:
         return R, T, bool(r.success), i0.cpu().numpy(), i1.cpu().numpy(), thr
     return torch.from_numpy(R).to(e.device), torch.from_numpy(T).to(e.device), bool(r.success), i0, i1, thr
+
+
+def SolveRelativePoses(rows, pairs, seeds):
+    """The batched counterpart of SolveRelativePose: ``rows`` [F,1024,64] f32 (a pipeline's frame rows: descriptor 0:60 | xyz 60:63 |
+    valid 63; device tensor or array), ``pairs`` [P,2] (frame 0, frame 1), ``seeds`` one RandomState seed per pair (or [P,6000]
+    draws).  All pairs go through ONE call (Engine.register_pairs with the host half: the reference's bits, as SolveRelativePose gives them).
+    -> a list of (R, T, isSuccess, inliersIdx0, inliersIdx1, residualThreshold), one per pair, as NumPy arrays."""
+    e = default_engine()
+    rows = _dev(rows, torch.float32)
+    n_key = rows[:, :, 63].sum(dim=1).round().to(torch.int32).contiguous()
+    out = e.register_pairs(rows, n_key, pairs, seeds, certify=True)
+    idx = out.pair_idx.cpu().numpy()
+    res = []
+    for q, r in enumerate(out.results):
+        i1 = np.flatnonzero(out.masks[q])
+        thr = {0: 0.4, 1: 0.8, 2: 1.6}[int(round(np.log2(float(r["threshold"]) / 0.4)))]
+        res.append((np.array(r["R"], dtype=np.float32).reshape(3, 3), np.array(r["T"], dtype=np.float32).reshape(3, 1), bool(r["success"]),
+                    idx[q][i1], i1, thr))
+    return res

@@ -7,6 +7,7 @@ pose) that run without any host synchronisation until the caller reads a result.
 
 PyTorch is used for device memory and streams only.
 """
+import collections
 import ctypes as C
 import os
 import threading
@@ -1356,6 +1357,55 @@ class Engine:
                 batch.result[j].copy_(r); batch.inlier_mask[j].copy_(m); batch.pair_idx[j].copy_(x)
         return tied, counts
 
+    def register_pairs(self, rows, n_key, pairs, seeds, certify=True):
+        """The pipeline's pair stage over a table of frame pairs of resident rows, ONE call (caelo_register_pairs): ``rows``
+        [F,1024,64] f32 and ``n_key`` [F] i32 on the device (a FrameBatch's), ``pairs`` [P,2] (frame 0, frame 1) -- any two frames,
+        (f, f) included -- ``seeds`` one integer per pair (the pair draws ``ransac_draws(seed)``, as the pipeline's pair with that
+        seed does) or a float64 array [P,6000] of draws.  ``certify=True``: the kernels leave certificates and the host half runs
+        over them as for a pipeline batch (the reference's inlier sets, R_star / T_star and refits, bit for bit); without it the
+        kernels' own float64 fits are returned.  -> RegisteredPairs(results [P] (_ffi.POSE_DTYPE: R, T, R_ransac, T_ransac,
+        threshold, success, iterations, n_inliers, ...), masks [P,1024] u8 (host), pair_idx [P,1024] i64 (device), evals [P],
+        status [P]) in the table's order.  Raises before any launch for a frame index outside [0, F) or a frame of the table whose
+        n_key lies outside [1, 1024].  Synchronises."""
+        assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
+        assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
+        pr = np.ascontiguousarray(pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
+        if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
+            raise _ffi.CaeloError("register_pairs: a frame index does not fit 32 bits")
+        P = int(pr.shape[0])
+        if isinstance(seeds, np.ndarray) and seeds.dtype == np.float64:
+            draws = np.ascontiguousarray(seeds).reshape(P, -1)
+        else:
+            assert len(seeds) == P, "one seed per pair"
+            draws = np.stack([ransac_draws(int(s_)) for s_ in seeds]) if P else np.zeros((0, 6000))
+        assert draws.shape[1] == 6000, "[P,6000] draws: 3 levels x 500 trials x 4"
+        pr_d = torch.from_numpy(pr.astype(np.int32)).to(self.device)
+        rand_d = torch.from_numpy(draws).to(self.device)
+        idx = self.zeros((P, MAX_K), torch.int64)
+        ws = self._ws("register_pairs", int(self.lib.caelo_register_pairs_ws_bytes(P)))
+        if certify:
+            self.host_blas()
+            cert = self.new_cert(P)
+            res_d = mask_d = None
+        else:
+            cert = None
+            res_d = self.zeros((P, C.sizeof(_ffi.PoseResult)), torch.uint8)
+            mask_d = self.zeros((P, MAX_K), torch.uint8)
+        _ffi.check(self.lib.caelo_register_pairs(self.ctx, _ptr(rows), rows.shape[0], _ptr(n_key), _ptr(pr_d), P, _ptr(rand_d), _ptr(idx),
+                                                 _ptr(res_d), _ptr(mask_d), _ptr(cert), _ptr(ws), self.stream))
+        if P == 0:
+            return RegisteredPairs(np.zeros(0, dtype=_ffi.POSE_DTYPE), np.zeros((0, MAX_K), dtype=np.uint8), idx, np.zeros(0, np.int32), np.zeros(0, np.int32))
+        if certify:
+            results, masks, evals, status = self.certify(cert, list(draws))
+            if (status != 0).any():
+                raise _ffi.CaeloError("pairs %s could not be certified (status %s)" % (np.flatnonzero(status != 0).tolist(), status[status != 0].tolist()))
+            results, masks = results.copy(), masks.copy()
+        else:
+            results = np.frombuffer(res_d.cpu().numpy().tobytes(), dtype=_ffi.POSE_DTYPE).copy()
+            masks = mask_d.cpu().numpy()
+            evals, status = np.zeros(P, np.int32), np.zeros(P, np.int32)
+        return RegisteredPairs(results, masks, idx, evals, status)
+
     def checked(self, ff, pc, dist_channels=5):
         """Synchronising status check of an extract() result: raises what the reference would raise."""
         raise_status(int(ff.status[0].item()))
@@ -1386,6 +1436,8 @@ class Engine:
             raise _ffi.CaeloError("pair could not be certified (status %d)" % status[0])
         return results[0], masks[0], idx
 
+
+RegisteredPairs = collections.namedtuple("RegisteredPairs", "results masks pair_idx evals status")   # Engine.register_pairs
 
 _default = None
 

@@ -895,8 +895,9 @@ __device__ __forceinline__ void four_hypotheses(const float *sP0, const float *s
         counts[trial0 + lane] = lane == 0 ? cnt[0] : (lane == 1 ? cnt[1] : (lane == 2 ? cnt[2] : cnt[3]));
 }
 
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) {
-    const caelo_pair_dev &P = ps.p[blockIdx.z];
+template <class PS>
+static __device__ __forceinline__ void ransac_hyp_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
+    const auto &P = pair_of(ps, blockIdx.z);
     const float *__restrict__ pc0 = P.pc0, *__restrict__ pc1 = P.pc1;
     const int64_t *__restrict__ pair_idx = P.pair_idx;
     RansacWs *ws = (RansacWs *)P.ws_ransac;
@@ -947,6 +948,9 @@ __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_s
     if (cert) four_hypotheses<true>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts, sN, cert, 0);
     else four_hypotheses<false>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts);
 }
+__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body(ps, ld0, ld1, k1_max); }
+__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body(pt, ld0, ld1, k1_max); }
+
 
 // Round 6: certificates for the 0.8 m and 1.6 m levels (Match.py:207-214).  A pair escalates when no hypothesis of a level reaches
 // leastInliers; without bounds for the next level the host half evaluates all of its (up to 500) hypotheses like the reference's loop --
@@ -957,8 +961,9 @@ __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_s
 // (0.8 m, 1.6 m: both, the second is wasted when the first succeeds, and escalations are rare) gets its `hi_up` / `idx_up` exactly as
 // the first level got `hi` / `idx`.  The inlier counts of these levels are not kept (scratch): the host half derives them.
 #define RU_BLOCKS 32   // (8 workgroups per level were tried for the sake of the launches that only look and leave: those took as long as before, 43 us on the pair stream, and a batch with a failing pair 4 x longer -- the failing_pairs leg fell from 17.5 k to 9.9 k frames/s)
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) {
-    const caelo_pair_dev &P = ps.p[blockIdx.z];
+template <class PS>
+static __device__ __forceinline__ void ransac_hyp_up_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
+    const auto &P = pair_of(ps, blockIdx.z);
     caelo_ransac_cert *cert = P.cert;
     if (!cert) return;
     RansacWs *ws = (RansacWs *)P.ws_ransac;
@@ -992,10 +997,14 @@ __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pai
         four_hypotheses<true>(sP0, sP1, N, P.rand + (size_t)level * CAELO_RANSAC_MAX_TRIALS * 4, trial0, 0.4f * (float)(1 << level), lane, ps.faults,
                               s_scratch, sN, cert, level);
 }
+__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body(ps, ld0, ld1, k1_max); }
+__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body(pt, ld0, ld1, k1_max); }
+
 
 #define RF_WAVES 8   // the accept rules, the mask and the refit use four of them; all eight evaluate a next level's hypotheses
-__global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) {
-    const caelo_pair_dev &P = ps.p[blockIdx.z];
+template <class PS>
+static __device__ __forceinline__ void ransac_finish_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
+    const auto &P = pair_of(ps, blockIdx.z);
     if (P.cert && P.cert_only) return;   // (a mixed set: this pair's result comes from the host half)
     const float *__restrict__ pc0 = P.pc0, *__restrict__ pc1 = P.pc1;
     const int64_t *__restrict__ pair_idx = P.pair_idx;
@@ -1154,6 +1163,9 @@ __global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish(const caelo_
         for (int q = 0; q < 3; ++q) res->T[q] = T[q];
     }
 }
+__global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_finish_body(ps, ld0, ld1, k1_max); }
+__global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_finish_body(pt, ld0, ld1, k1_max); }
+
 
 CAELO_API int caelo_ransac(caelo_ctx *c, const float *pc0, int ld0, const float *pc1, int ld1, const int64_t *pair_idx,
                            int64_t k1_max, const int32_t *n1, const double *rnd, caelo_pose_result *result,
@@ -1184,6 +1196,34 @@ int ransac_set(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, hipSt
     }
     if (all_cert_only) return CAELO_OK;   // the host half decides every pair of the set: no finishing kernel
     k_ransac_finish<<<dim3(1, 1, ps.n), 64 * RF_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
+// The pair stage's launches over one slice of a pair table (caelo_register_pairs): the shapes of match_set / ransac_set for the
+// pipeline's rows (ld 64, 1024 rows, descriptor width 60, 16-byte aligned rows: the vector loads), the kernels' table instantiations.
+int match_table(const caelo_pair_table &pt, hipStream_t s) {
+    CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
+    CAELO_REQUIRE((((uintptr_t)pt.rows) & 15u) == 0, "rows not 16-byte aligned");
+    const int64_t kpad = ms_pad16(CAELO_MAX_KEYPTS);
+    k_match_prep_tab<<<dim3((unsigned)((kpad / 16 + 3) / 4), 1, pt.n), 256, 0, s>>>(pt, 64, CAELO_MAX_KEYPTS, 60, kpad, 1);
+    CAELO_LAUNCH_CHECK();
+    k_match_screen_tab<<<dim3((unsigned)((CAELO_MAX_KEYPTS + 16 * MS_CT - 1) / (16 * MS_CT)), 1, pt.n), 64 * MS_NW, 0, s>>>(pt, 64, CAELO_MAX_KEYPTS, 64,
+                                                                                                                     CAELO_MAX_KEYPTS, 60, kpad, 1);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
+int ransac_table(const caelo_pair_table &pt, hipStream_t s) {
+    CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
+    k_ransac_hyp_tab<<<dim3((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * RH_PER_WAVE - 1) / (RE_WAVES * RH_PER_WAVE), 1, pt.n), 64 * RE_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
+    CAELO_LAUNCH_CHECK();
+    if (pt.cert) {   // bounds for the 0.8 / 1.6 m levels of the pairs whose first level failed
+        k_ransac_hyp_up_tab<<<dim3(RU_BLOCKS, 2, pt.n), 64 * RE_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
+        CAELO_LAUNCH_CHECK();
+    }
+    if (pt.cert && pt.cert_only) return CAELO_OK;   // the host half decides every pair: no finishing kernel
+    k_ransac_finish_tab<<<dim3(1, 1, pt.n), 64 * RF_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
 }

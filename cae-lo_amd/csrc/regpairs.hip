@@ -1,0 +1,85 @@
+// regpairs.hip -- caelo_register_pairs: the pipeline's pair stage (NN match, RANSAC hypotheses, certificates, refit) over a TABLE of
+// frame pairs whose rows are already resident, e.g. the frame steps 2, 5, 10 of a sequence after ONE extraction pass.
+//
+// Nothing is computed here that the consecutive path does not compute: match_table / ransac_table (match.hip) launch the pair
+// stage's kernel bodies instantiated for a device pair table instead of a caelo_pair_set, so a pair gives the bits it gives in
+// a pipeline batch or through caelo_match + caelo_ransac.  What this file adds is the host side: the argument checks (the table
+// and the key point counts are read back once, before any launch), the slice order and the walk over the slices.
+//
+// Slice order: the table entries are sorted (stably) by (frame 0, frame 1) on the host while they are being checked, and a launch
+// covers CAELO_FB_MAX consecutive entries of that order.  Pairs that share their frame 0 -- steps 1, 5 and 10 from one anchor --
+// then sit in one launch, and the chain (a, a + s), (a + s, a + 2 s) has its shared frame in neighbouring slots: the second fetch
+// of a frame's rows (262 KB) hits L2.  Outputs are indexed by the table entry, so the caller sees its own order.
+// Host cost per call: ONE wait for the stream (the read-back of the table and of n_key, 8 B per pair + 4 B per frame), the sort, and
+// three host vectors; nothing goes up -- a slice's order is part of its launches' arguments.
+#include "caelo_internal.h"
+
+#include <algorithm>
+#include <vector>
+
+namespace {
+constexpr int64_t RP_ALIGN = 256;
+inline int64_t rp_up(int64_t b) { return (b + RP_ALIGN - 1) / RP_ALIGN * RP_ALIGN; }
+inline int64_t rp_match_stride() { return rp_up(caelo_match_ws_bytes(CAELO_MAX_KEYPTS)); }
+inline int64_t rp_ransac_stride() { return rp_up(caelo_ransac_ws_bytes()); }
+}  // namespace
+
+// CAELO_FB_MAX slots of match + RANSAC workspace, whatever the table's length (the slices reuse them)
+CAELO_API int64_t caelo_register_pairs_ws_bytes(int64_t n_pairs) {
+    if (n_pairs < 0) return 0;
+    return CAELO_FB_MAX * (rp_match_stride() + rp_ransac_stride());
+}
+
+CAELO_API int caelo_register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                                   const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                                   caelo_ransac_cert *certs_out, void *ws, void *stream) {
+    CAELO_REQUIRE(pairs, "null pair table");
+    CAELO_REQUIRE(n_frames >= 1 && n_frames < (1LL << 31), "n_frames must lie in [1, 2^31)");
+    CAELO_REQUIRE(n_pairs >= 0 && n_pairs < (1LL << 31), "n_pairs must lie in [0, 2^31)");
+    CAELO_REQUIRE(c && rows && n_key && rand && pair_idx_out && ws, "null argument");
+    CAELO_REQUIRE((results_out && masks_out) || (certs_out && !results_out && !masks_out),
+                  "results_out and masks_out go together; without them certs_out must take the pairs' certificates");
+    CAELO_REQUIRE((((uintptr_t)rows) & 15u) == 0 && (((uintptr_t)certs_out) & 15u) == 0 && (((uintptr_t)masks_out) & 3u) == 0 &&
+                      (((uintptr_t)ws) & 15u) == 0,
+                  "rows, certs_out and ws must be 16-byte aligned, masks_out 4-byte aligned");
+    if (n_pairs == 0) return CAELO_OK;
+    hipStream_t s = caelo_stream(stream);
+    // ---- the table and the counts as the device holds them once `stream` has reached this call: read back, checked, ordered
+    std::vector<int32_t> tab((size_t)n_pairs * 2), nk((size_t)n_frames), order((size_t)n_pairs);
+    CAELO_HIP(hipMemcpyAsync(tab.data(), pairs, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CAELO_HIP(hipMemcpyAsync(nk.data(), n_key, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CAELO_HIP(hipStreamSynchronize(s));
+    for (int64_t q = 0; q < n_pairs; ++q)
+        for (int side = 0; side < 2; ++side) {
+            const int64_t f = tab[(size_t)(2 * q + side)];
+            if (f < 0 || f >= n_frames) {
+                caelo_set_error("caelo_register_pairs: pair %lld names frame %lld, outside [0, %lld)", (long long)q, (long long)f, (long long)n_frames);
+                return CAELO_ERR_ARG;
+            }
+            if (nk[(size_t)f] < 1 || nk[(size_t)f] > CAELO_MAX_KEYPTS) {
+                caelo_set_error("caelo_register_pairs: frame %lld of pair %lld has n_key %d, outside [1, %d]", (long long)f, (long long)q,
+                                (int)nk[(size_t)f], CAELO_MAX_KEYPTS);
+                return CAELO_ERR_ARG;
+            }
+        }
+    for (int64_t q = 0; q < n_pairs; ++q) order[(size_t)q] = (int32_t)q;
+    std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+        return tab[2 * (size_t)a] != tab[2 * (size_t)b] ? tab[2 * (size_t)a] < tab[2 * (size_t)b] : tab[2 * (size_t)a + 1] < tab[2 * (size_t)b + 1];
+    });
+    caelo_pair_table pt = {};
+    pt.rows = rows; pt.n_key = n_key; pt.pairs = pairs;
+    pt.pair_idx = pair_idx_out; pt.rand = rand; pt.result = results_out; pt.mask = masks_out; pt.cert = certs_out;
+    pt.cert_only = results_out ? 0 : 1;
+    pt.ws_match_stride = rp_match_stride(); pt.ws_ransac_stride = rp_ransac_stride();
+    pt.ws_match = (char *)ws;
+    pt.ws_ransac = pt.ws_match + CAELO_FB_MAX * pt.ws_match_stride;
+    pt.faults = c->faults;
+    for (int64_t q0 = 0; q0 < n_pairs; q0 += CAELO_FB_MAX) {   // the slot workspaces are reused slice after slice: the stream orders them
+        pt.n = (int32_t)std::min<int64_t>(CAELO_FB_MAX, n_pairs - q0);
+        for (int z = 0; z < pt.n; ++z) pt.order[z] = order[(size_t)(q0 + z)];   // (a slice's order travels in the kernel arguments)
+        int rc = match_table(pt, s);
+        if (rc == CAELO_OK) rc = ransac_table(pt, s);
+        if (rc) return rc;
+    }
+    return CAELO_OK;
+}

@@ -5,6 +5,7 @@
     python run_sequence.py --synthetic 20 --out poses_/00.txt
     python run_sequence.py --scans <seq>/velodyne --calib <calib>/00/calib_.txt --out poses_/00.txt --save-artifacts
     python run_sequence.py --scans <raw KITTI seq>/velodyne --calib-angle 0.22 --out poses_/00.txt   # CorrectPC on the fly
+    python run_sequence.py --scans <seq>/velodyne --frame-steps 1,5,10 --out poses_/00.txt   # + poses_/5_00.txt, poses_/10_00.txt, one extraction pass
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_sequence.py --synthetic 800 ...
 
 Frames are sharded contiguously over the ranks (one process per GPU); every rank runs its frames through the
@@ -27,7 +28,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
-from caelo import _ffi, stageio, synth  # noqa: E402
+from caelo import _ffi, framesteps, stageio, synth  # noqa: E402
 import caelo  # noqa: E402
 caelo.configure_runtime()  # this script owns its process: before HIP starts (the queue count is left to the caller)
 from caelo import dist as cdist  # noqa: E402
@@ -369,6 +370,17 @@ def main():
                          "p x z, the HDL-64E's vertical-angle calibration; raw KITTI scans: 0.22) on the device, inside the batch launch, before "
                          "anything else reads it -- no corrected copy of the data set on disk.  Default: no correction.  Only scans are "
                          "corrected, as in the reference: key points given by --keypts-source / --features-from are used as they are")
+    ap.add_argument("--frame-steps", default="1", metavar="S[,S...]",
+                    help="also register the sequence at these frame steps, from the rows of the ONE extraction pass: step s pairs scan k*s with "
+                         "scan (k+1)*s (the reference's GenerateTrajactory.m:124-126), pair k drawing RandomState(seed_base + k) -- what a plain "
+                         "run over every s-th scan computes.  Step 1 is the pipeline's run and is always written to --out; every other step s "
+                         "is registered with Engine.register_pairs on the chunk's resident rows (the last max(S) frames' rows are carried "
+                         "from chunk to chunk) and written to --out with '<s>_' in front of its file name: one row per input frame, the "
+                         "multiples of s holding the pose chained through Tr, the frames in between repeating the preceding multiple's row.  "
+                         "(The reference's MATLAB writer cannot be run here: the in-between rows are this project's choice; evaluate.py "
+                         "--frame-step s reads the multiples only.)  --matchability M gets the same prefix per step.  With --gpus > 1 a rank "
+                         "registers the step pairs whose frame 0 it owns: its halo is the next rank's first max(S) frames' rows (one more "
+                         "all-gather), and every rank needs at least max(S) frames")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
@@ -378,6 +390,13 @@ def main():
     if n_frames >= 2 and not (0 <= args.seed_base and args.seed_base + n_frames - 2 < 2 ** 32):
         ap.error("--seed-base %d: the seeds seed_base + i - 1 of pairs i = 1 .. %d must lie in [0, 2^32)" % (args.seed_base, n_frames - 1))
 
+    try:
+        steps = framesteps.parse_steps(args.frame_steps)
+    except ValueError as e:
+        ap.error("--frame-steps: %s" % e)
+    if n_frames and framesteps.carry_frames(steps) and n_frames // max(1, args.gpus) < framesteps.carry_frames(steps):
+        ap.error("--frame-steps %s on %d GPUs: every rank needs at least max(steps) = %d of the %d frames (its first frames are the halo "
+                 "of the rank before it)" % (args.frame_steps, args.gpus, framesteps.carry_frames(steps), n_frames))
     if args.calib_angle is not None and not np.isfinite(args.calib_angle):
         ap.error("--calib-angle must be a finite number of degrees")
     given = None
@@ -448,7 +467,11 @@ def main():
     lo, hi = cdist.shard_frames(n, rank, world)
     t0 = time.time()
 
+    stepper = framesteps.StepRegistrar(eng, steps, args.seed_base, not args.no_certify, lo) if any(s_ != 1 for s_ in steps) else None
+
     def keep(c0, batch):
+        if stepper is not None:   # (after the host redo of tied frames: the rows are final)
+            stepper.keep(c0, batch)
         if not args.save_artifacts:
             return
         rows = batch.rows.cpu().numpy(); nk = batch.n_key.cpu().numpy()
@@ -498,6 +521,14 @@ def main():
         rel, ok, thr, nin = allrows[:, :12], allrows[:, 12] > 0, allrows[:, 13], allrows[:, 14].astype(np.int32)
         if records is not None:
             records = [(allrows[:, 15].astype(np.int32), allrows[:, 16].astype(np.int32))]
+    if stepper is not None and world > 1:   # the step pairs that straddle a rank boundary: frame 0's owner registers them on the next rank's head
+        heads = cdist.all_gather_boundary(stepper.head_rows())
+        if rank < world - 1:
+            stepper.boundary(heads[rank + 1], hi, n)
+        exports = [None] * world
+        dist.all_gather_object(exports, stepper.export())
+        if rank == 0:
+            stepper.merge(exports)
     torch.cuda.synchronize()
     dt = time.time() - t0
     if rank == 0:
@@ -506,6 +537,14 @@ def main():
         if records is not None:
             from caelo import evaluate as ev
             ev.save_matchability(args.matchability, nin, np.concatenate([b for _, b in records]), np.concatenate([a for a, _ in records]))
+        for s_ in (stepper.steps if stepper is not None else []):
+            rel_s, ok_s, nin_s, np_s, it_s = stepper.step_results(s_)
+            assert len(rel_s) == len(framesteps.step_pairs(n, s_)), "step %d: %d pairs registered, %d scheduled" % (s_, len(rel_s), len(framesteps.step_pairs(n, s_)))
+            stageio.write_poses(framesteps.step_path(args.out, s_), framesteps.expand_rows(stageio.chain_poses(rel_s, Tr), n, s_))
+            if args.matchability:
+                from caelo import evaluate as ev
+                ev.save_matchability(framesteps.step_path(args.matchability, s_), nin_s, np_s, it_s)
+            print("step %d: %d pairs (%d solved) -> %s" % (s_, len(rel_s), int(np.sum(ok_s)), framesteps.step_path(args.out, s_)))
         for i in range(len(rel) if len(rel) <= 200 else 0):
             print("%06d-%06d ok=%d thr=%.1f inliers=%4d T=[% .3f % .3f % .3f]" % (i, i + 1, ok[i], thr[i], nin[i], rel[i, 9], rel[i, 10], rel[i, 11]))
         print("%d frames, %d pairs on %d GPU(s) in %.2f s (%.1f frames/s incl. scan loading / synthesis, upload and read-back; %d of %d poses solved) -> %s" % (

@@ -571,6 +571,31 @@ void caelo_seqloader_destroy(caelo_seqloader *loader);
 int caelo_pipeline_expect(caelo_pipeline *pipe, int64_t n_frames);
 int caelo_pipeline_stats(caelo_pipeline *pipe, int64_t *out_host);
 
+/* ---- pair tables: the pipeline's pair stage over ANY frame pairs of resident rows (additive; the ABI version stays 6) -------------
+ * The pipeline registers frame i against frame i + 1.  caelo_register_pairs registers a table pairs [n_pairs][2] i32 of
+ * (frame 0, frame 1) indices into rows [n_frames][1024][64] f32 (a pipeline's rows: descriptor 0:60 | xyz 60:63 | valid 63,
+ * 16-byte aligned) with n_key [n_frames] i32 -- all DEVICE memory, as written by work queued on `stream` before the call.  The
+ * kernels are the pair stage's own (NN match with the float64 certification of the argmin, the 500 hypotheses of the 0.4 m level,
+ * the bounds of the 0.8 / 1.6 m levels, the refit) taking their pairs from the table: a pair gives the bits it gives in a pipeline
+ * batch and through caelo_match + caelo_ransac.  Pair q draws from rand + q * 6000 ([n_pairs][3 * 500][4] f64, device) and writes
+ *   pair_idx_out [n_pairs][1024] i64, and
+ *   results_out [n_pairs] + masks_out [n_pairs][1024] u8: the kernels' float64 fits and inlier masks, and / or
+ *   certs_out [n_pairs] (16-byte aligned): the certificates, which caelo_host_certify takes unchanged once copied to the host.
+ * results_out and masks_out go together; both null with certs_out given: certificates only, the host half produces the results
+ * (the finishing kernel is not launched, as in a pipeline job with result_host).
+ * A launch of every kernel covers up to 8 pairs; larger tables are walked in such slices, ordered by (frame 0, frame 1) so that
+ * pairs sharing a frame sit in one launch (outputs stay in the table's order).  ws: caelo_register_pairs_ws_bytes(n_pairs) bytes (eight slots of match + RANSAC workspace),
+ * 16-byte aligned, no initialisation, one per call in flight; no other device memory is allocated.
+ * Refused before any launch (CAELO_ERR_ARG, caelo_last_error): a null table, a frame index outside [0, n_frames), a frame of the
+ * table whose n_key lies outside [1, 1024].  The call waits for `stream` once (it reads the table and the counts back to check
+ * them: one hipStreamSynchronize, nothing is uploaded); the results are complete when `stream` has passed the call.  A pair (f, f) is
+ * legal: every point matches the FIRST point with its descriptor (itself unless descriptors repeat, Match.py:258) and the pose is the
+ * identity to float32 rounding. */
+int64_t caelo_register_pairs_ws_bytes(int64_t n_pairs);
+int caelo_register_pairs(caelo_ctx *ctx, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                         const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                         caelo_ransac_cert *certs_out, void *ws, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
