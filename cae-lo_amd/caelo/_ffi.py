@@ -110,6 +110,7 @@ SIGNATURES = [
     ("caelo_encode32", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp]),
     ("caelo_encode32_profile", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_vp, c_vp, c_vp]),
     ("caelo_match_ws_bytes", c_i64, [c_i64]),
+    ("caelo_match_ws_bytes_dim", c_i64, [c_i64, c_int]),
     ("caelo_match", c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
     ("caelo_match_profile", c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_vp]),
     ("caelo_solve_rt", c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),
@@ -161,6 +162,8 @@ SIGNATURES = [
     ("caelo_kp_nn_pairs", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes", c_i64, [c_i64]),
     ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_register_pairs_ws_bytes_dim", c_i64, [c_i64, c_int]),
+    ("caelo_register_pairs_desc", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int]),
 ]
 
 _lib = None

@@ -383,8 +383,14 @@ def RANSAC4RT(Pairs0, Pairs1, Weights0=None, Weights1=None, rng=None):
     return torch.from_numpy(R).to(e.device), torch.from_numpy(T).to(e.device), bool(r.success), m, thr
 
 
+MAX_DESC_DIM = 256   # the widest descriptor caelo_match takes (include/caelo.h)
+
+
 def SolveRelativePose(OriPC0, OriCodes0, Weights0, OriPC1, OriCodes1, Weights1, rng=None):
     """Match.py:241-283 -> (R, T, isSuccess, inliersIdx0, inliersIdx1, residualThreshold)."""
+    s0, s1 = tuple(np.shape(OriCodes0) if _is_np(OriCodes0) else OriCodes0.shape), tuple(np.shape(OriCodes1) if _is_np(OriCodes1) else OriCodes1.shape)
+    if len(s0) != 2 or len(s1) != 2 or s0[1] != s1[1] or not 1 <= s0[1] <= MAX_DESC_DIM:   # (before anything is uploaded or launched)
+        raise ValueError("SolveRelativePose: descriptors [K, D] of one width D <= %d, got %s and %s" % (MAX_DESC_DIM, s0, s1))
     e = default_engine()
     as_np = _is_np(OriPC0)
     pc0, pc1 = _dev(OriPC0, torch.float32), _dev(OriPC1, torch.float32)
@@ -402,15 +408,21 @@ def SolveRelativePose(OriPC0, OriCodes0, Weights0, OriPC1, OriCodes1, Weights1, 
     return torch.from_numpy(R).to(e.device), torch.from_numpy(T).to(e.device), bool(r.success), i0, i1, thr
 
 
-def SolveRelativePoses(rows, pairs, seeds):
+def SolveRelativePoses(rows, pairs, seeds, desc=None):
     """The batched counterpart of SolveRelativePose: ``rows`` [F,1024,64] f32 (a pipeline's frame rows: descriptor 0:60 | xyz 60:63 |
     valid 63; device tensor or array), ``pairs`` [P,2] (frame 0, frame 1), ``seeds`` one RandomState seed per pair (or [P,6000]
     draws).  All pairs go through ONE call (Engine.register_pairs with the host half: the reference's bits, as SolveRelativePose gives them).
+    ``desc`` [F,1024,D <= 256] f32: descriptors of the caller's to match on instead of the rows' columns 0:60 (the rows still give
+    xyz and the counts).
     -> a list of (R, T, isSuccess, inliersIdx0, inliersIdx1, residualThreshold), one per pair, as NumPy arrays."""
     e = default_engine()
     rows = _dev(rows, torch.float32)
+    if desc is not None:
+        desc = _dev(desc, torch.float32)
+        if desc.dim() != 3 or not 1 <= desc.shape[2] <= MAX_DESC_DIM:
+            raise ValueError("SolveRelativePoses: desc [F,1024,D <= %d], got %s" % (MAX_DESC_DIM, tuple(desc.shape)))
     n_key = rows[:, :, 63].sum(dim=1).round().to(torch.int32).contiguous()
-    out = e.register_pairs(rows, n_key, pairs, seeds, certify=True)
+    out = e.register_pairs(rows, n_key, pairs, seeds, certify=True, desc=desc)
     idx = out.pair_idx.cpu().numpy()
     res = []
     for q, r in enumerate(out.results):

@@ -1039,8 +1039,11 @@ class Engine:
     def match(self, f0, f1, n0=None, n1=None):
         """f0 [k0,dim], f1 [k1,dim] (row-strided views allowed) -> pair_idx [k1] int64."""
         idx = self.zeros((f1.shape[0],), torch.int64)
-        kmax = max(int(f0.shape[0]), int(f1.shape[0]))
-        ws = self._ws("match%d" % kmax, int(self.lib.caelo_match_ws_bytes(kmax)))   # sized by the larger frame (caelo.h)
+        kmax, dim = max(int(f0.shape[0]), int(f1.shape[0])), int(f0.shape[1])
+        if dim > 64:   # the screen over several K = 64 blocks: one more operand image per block (caelo_match_ws_bytes_dim)
+            ws = self._ws("match%d_%d" % (kmax, dim), int(self.lib.caelo_match_ws_bytes_dim(kmax, dim)))
+        else:
+            ws = self._ws("match%d" % kmax, int(self.lib.caelo_match_ws_bytes(kmax)))   # sized by the larger frame (caelo.h)
         _ffi.check(self.lib.caelo_match(self.ctx, _ptr(f0), self._ld(f0), f0.shape[0], _ptr(n0), _ptr(f1), self._ld(f1),
                                         f1.shape[0], _ptr(n1), f0.shape[1], _ptr(idx), _ptr(ws), self.stream))
         return idx
@@ -1357,7 +1360,7 @@ class Engine:
                 batch.result[j].copy_(r); batch.inlier_mask[j].copy_(m); batch.pair_idx[j].copy_(x)
         return tied, counts
 
-    def register_pairs(self, rows, n_key, pairs, seeds, certify=True):
+    def register_pairs(self, rows, n_key, pairs, seeds, certify=True, desc=None):
         """The pipeline's pair stage over a table of frame pairs of resident rows, ONE call (caelo_register_pairs): ``rows``
         [F,1024,64] f32 and ``n_key`` [F] i32 on the device (a FrameBatch's), ``pairs`` [P,2] (frame 0, frame 1) -- any two frames,
         (f, f) included -- ``seeds`` one integer per pair (the pair draws ``ransac_draws(seed)``, as the pipeline's pair with that
@@ -1366,8 +1369,15 @@ class Engine:
         kernels' own float64 fits are returned.  -> RegisteredPairs(results [P] (_ffi.POSE_DTYPE: R, T, R_ransac, T_ransac,
         threshold, success, iterations, n_inliers, ...), masks [P,1024] u8 (host), pair_idx [P,1024] i64 (device), evals [P],
         status [P]) in the table's order.  Raises before any launch for a frame index outside [0, F) or a frame of the table whose
-        n_key lies outside [1, 1024].  Synchronises."""
+        n_key lies outside [1, 1024].  Synchronises.
+        ``desc`` [F,1024,D] f32 on the device (D <= 256; contiguous or row-strided, i.e. a column slice of a wider block): the NN
+        match runs on these descriptors instead of the rows' columns 0:60 (caelo_register_pairs_desc); the rows still give xyz."""
         assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
+        if desc is not None:
+            if desc.dtype != torch.float32 or desc.dim() != 3 or tuple(desc.shape[:2]) != (rows.shape[0], MAX_K) or not 1 <= desc.shape[2] <= 256:
+                raise ValueError("desc [F=%d,%d,D<=256] f32, got %s %s" % (rows.shape[0], MAX_K, tuple(desc.shape), desc.dtype))
+            if desc.stride(2) != 1 or desc.stride(0) != MAX_K * desc.stride(1) or desc.stride(1) < desc.shape[2]:
+                raise ValueError("desc must be contiguous or a column slice of a contiguous [F,%d,ld] block, got strides %s" % (MAX_K, tuple(desc.stride())))
         assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
         pr = np.ascontiguousarray(pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
         if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
@@ -1382,7 +1392,10 @@ class Engine:
         pr_d = torch.from_numpy(pr.astype(np.int32)).to(self.device)
         rand_d = torch.from_numpy(draws).to(self.device)
         idx = self.zeros((P, MAX_K), torch.int64)
-        ws = self._ws("register_pairs", int(self.lib.caelo_register_pairs_ws_bytes(P)))
+        if desc is None:
+            ws = self._ws("register_pairs", int(self.lib.caelo_register_pairs_ws_bytes(P)))
+        else:
+            ws = self._ws("register_pairs_d%d" % desc.shape[2], int(self.lib.caelo_register_pairs_ws_bytes_dim(P, int(desc.shape[2]))))
         if certify:
             self.host_blas()
             cert = self.new_cert(P)
@@ -1391,8 +1404,13 @@ class Engine:
             cert = None
             res_d = self.zeros((P, C.sizeof(_ffi.PoseResult)), torch.uint8)
             mask_d = self.zeros((P, MAX_K), torch.uint8)
-        _ffi.check(self.lib.caelo_register_pairs(self.ctx, _ptr(rows), rows.shape[0], _ptr(n_key), _ptr(pr_d), P, _ptr(rand_d), _ptr(idx),
-                                                 _ptr(res_d), _ptr(mask_d), _ptr(cert), _ptr(ws), self.stream))
+        if desc is None:
+            _ffi.check(self.lib.caelo_register_pairs(self.ctx, _ptr(rows), rows.shape[0], _ptr(n_key), _ptr(pr_d), P, _ptr(rand_d), _ptr(idx),
+                                                     _ptr(res_d), _ptr(mask_d), _ptr(cert), _ptr(ws), self.stream))
+        else:
+            _ffi.check(self.lib.caelo_register_pairs_desc(self.ctx, _ptr(rows), rows.shape[0], _ptr(n_key), _ptr(pr_d), P, _ptr(rand_d), _ptr(idx),
+                                                          _ptr(res_d), _ptr(mask_d), _ptr(cert), _ptr(ws), self.stream,
+                                                          _ptr(desc), int(desc.stride(1)), int(desc.shape[2])))
         if P == 0:
             return RegisteredPairs(np.zeros(0, dtype=_ffi.POSE_DTYPE), np.zeros((0, MAX_K), dtype=np.uint8), idx, np.zeros(0, np.int32), np.zeros(0, np.int32))
         if certify:

@@ -150,12 +150,17 @@ class StepRegistrar:
 
     def step_results(self, s):
         """-> (rel [p, 12] f32 (R | T), success [p], n_inliers [p], n_pairs [p], iterations [p]) of step s, in pair order."""
-        from . import _ffi
-        ks = np.concatenate([k_ for k_, _ in self.results[s]]) if self.results[s] else np.zeros(0, dtype=np.int64)
-        r = np.concatenate([r_ for _, r_ in self.results[s]]) if self.results[s] else np.zeros(0, dtype=_ffi.POSE_DTYPE)
-        order = np.argsort(ks, kind="stable")
-        assert np.array_equal(ks[order], np.arange(len(ks))), "step %d: pairs %s registered" % (s, ks[order].tolist())
-        r = r[order]
-        p = len(r)
-        rel = np.concatenate([r["R"].reshape(p, 9), r["T"].reshape(p, 3)], axis=1).astype(np.float32)
-        return rel, r["success"] != 0, r["n_inliers"].astype(np.int32), r["n_pairs"].astype(np.int32), r["iterations"].astype(np.int32)
+        return pack_results(self.results[s], s)
+
+
+def pack_results(entries, s):
+    """entries [(pair numbers k, record array (_ffi.POSE_DTYPE))] of step s, in any order -> what StepRegistrar.step_results returns."""
+    from . import _ffi
+    ks = np.concatenate([k_ for k_, _ in entries]) if entries else np.zeros(0, dtype=np.int64)
+    r = np.concatenate([r_ for _, r_ in entries]) if entries else np.zeros(0, dtype=_ffi.POSE_DTYPE)
+    order = np.argsort(ks, kind="stable")
+    assert np.array_equal(ks[order], np.arange(len(ks))), "step %d: pairs %s registered" % (s, ks[order].tolist())
+    r = r[order]
+    p = len(r)
+    rel = np.concatenate([r["R"].reshape(p, 9), r["T"].reshape(p, 3)], axis=1).astype(np.float32)
+    return rel, r["success"] != 0, r["n_inliers"].astype(np.int32), r["n_pairs"].astype(np.int32), r["iterations"].astype(np.int32)

@@ -122,12 +122,89 @@ def rows_from_features(KeyPts, Features):
     Features = np.asarray(Features)
     k = check_count(KeyPts.shape[0], "features set")
     if Features.shape[0] != k or Features.ndim != 2 or Features.shape[1] > 60:
-        raise ValueError("Features [K, D <= 60] for K = %d key points, got %s" % (k, Features.shape))
+        raise ValueError("Features [K, D <= 60] for K = %d key points, got %s (descriptors wider than the rows' 60 columns go beside "
+                         "the rows: Engine.register_pairs(..., desc=) / api.SolveRelativePoses(..., desc=))" % (k, Features.shape))
     rows = np.zeros((k, 64), np.float32)
     rows[:, 0:Features.shape[1]] = Features
     rows[:, 60:63] = KeyPts[:, 0:3]
     rows[:, 63] = 1.0
     return rows
+
+
+def desc_path(desc_dir, frame):
+    """<dir>/<frame:06d>.bin, the naming of the published comparison's descriptor folders (Scripts/GenerateTrajactory.m:193)."""
+    return os.path.join(desc_dir, str(int(frame)).zfill(6) + ".bin")
+
+
+def read_descriptors(path, dim):
+    """A descriptor .bin of the published comparison (Scripts/GenerateTrajactory.m:193-197): [-1, dim] f32 -> [K, dim] f32."""
+    dim = int(dim)
+    if dim < 1:
+        raise ValueError("%s: descriptor width %d, expected >= 1" % (path, dim))
+    if not os.path.isfile(path):
+        raise FileNotFoundError("descriptor file %s does not exist (expected <desc-dir>/<frame:06d>.bin)" % path)
+    nbytes = os.path.getsize(path)
+    if nbytes % (4 * dim):
+        raise ValueError("%s: %d bytes do not make rows of %d float32 (%d bytes each)" % (path, nbytes, dim, 4 * dim))
+    a = np.fromfile(path, dtype=np.float32, count=-1).reshape([-1, dim])
+    check_count(a.shape[0], path)
+    return a
+
+
+def write_descriptors(path, desc):
+    """The layout read_descriptors reads: the rows of ``desc`` [K, dim] as f32, nothing else."""
+    desc = np.asarray(desc)
+    if desc.ndim != 2 or desc.shape[1] < 1:
+        raise ValueError("%s: descriptors [K, dim >= 1], got %s" % (path, desc.shape))
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.ascontiguousarray(desc, dtype=np.float32).tofile(path)
+    return path
+
+
+class DescSource:
+    """run_sequence.py --desc-dir: descriptors of another method (<desc_dir>/<frame:06d>.bin, [-1, desc_dim] f32) on key points that
+    come from ``keypts_source`` ('3dfeatnet' | 'usip') + ``keypts_dir`` or from the KeyPts of ``features_from`` files (whose Features
+    are ignored).  No scan is read.  Everything that is wrong with the arguments or with a frame's files is a ValueError that names
+    the frame."""
+    MAX_DIM = 256
+
+    def __init__(self, desc_dir, desc_dim, keypts_source="ae", keypts_dir=None, features_from=None):
+        if desc_dim is None:
+            raise ValueError("--desc-dir needs --desc-dim, the descriptors' width: frame 0's file %s cannot be cut into rows without it" % desc_path(desc_dir, 0))
+        if not 1 <= int(desc_dim) <= self.MAX_DIM:
+            raise ValueError("--desc-dim %s: the match takes widths 1 .. %d (frame 0: %s)" % (desc_dim, self.MAX_DIM, desc_path(desc_dir, 0)))
+        if keypts_source != "ae" and features_from:
+            raise ValueError("--keypts-source and --features-from exclude each other (frame 0's key points: one source)")
+        if keypts_source == "ae" and not features_from:
+            raise ValueError("--desc-dir reads no scans: the key points of frame 0 and every other frame must come from --keypts-source "
+                             "3dfeatnet|usip with --keypts-dir, or from the KeyPts of --features-from files")
+        if keypts_source != "ae" and not keypts_dir:
+            raise ValueError("--keypts-source %s needs --keypts-dir (frame 0: <keypts-dir>/000000.bin)" % keypts_source)
+        self.desc_dir, self.dim = desc_dir, int(desc_dim)
+        self.keypts_source, self.keypts_dir, self.features_from = keypts_source, keypts_dir, features_from
+
+    def n_frames(self):
+        """Frames 0 .. n - 1: the run of consecutive <frame:06d>.bin files from 000000.bin on."""
+        n = 0
+        while os.path.isfile(desc_path(self.desc_dir, n)):
+            n += 1
+        return n
+
+    def frame(self, i):
+        """-> (key points [K,3] f32, descriptors [K,dim] f32) of frame i."""
+        if self.features_from:
+            pts = np.ascontiguousarray(np.asarray(load_features_dir(self.features_from, i)[0])[:, 0:3], dtype=np.float32)
+            check_count(pts.shape[0], "frame %d's features file" % i)
+        else:
+            pts = load_keypts(self.keypts_source, self.keypts_dir, i)
+        try:
+            d = read_descriptors(desc_path(self.desc_dir, i), self.dim)
+        except ValueError as e:
+            raise ValueError("frame %d: %s" % (i, e))
+        if d.shape[0] != pts.shape[0]:
+            raise ValueError("frame %d: %d key points but %d descriptors of width %d in %s" % (i, pts.shape[0], d.shape[0], self.dim,
+                                                                                             desc_path(self.desc_dir, i)))
+        return pts, d
 
 
 def load_features(raw_file, folder="Features"):

@@ -66,6 +66,13 @@ CAELO_API int64_t caelo_match_ws_bytes(int64_t k_max) {
     // both frames (match_screen.inc); k_max = the larger of the two frames' row capacities
     return ms_ws_bytes(k_max > 0 ? k_max : 1);
 }
+static inline int64_t msw_ws_bytes(int64_t kmax, int nb);
+__host__ __device__ inline int msw_nb(int dim);
+CAELO_API int64_t caelo_match_ws_bytes_dim(int64_t k_max, int dim) {
+    // descriptors wider than 64: nb = ceil((dim + 2) / 64) operand images per 16-row tile of frame 0 (match_screen_wide.inc)
+    if (dim <= MT_MAXDIM) return caelo_match_ws_bytes(k_max);
+    return msw_ws_bytes(k_max > 0 ? k_max : 1, msw_nb(dim));
+}
 
 __device__ inline double exact_dist(const float *a, const float *b, int dim) {
     double acc = 0.0;
@@ -333,6 +340,7 @@ __global__ void __launch_bounds__(64 * MM_WAVES) k_match_mfma(const caelo_pair_s
 }
 
 #include "match_screen.inc"
+#include "match_screen_wide.inc"
 
 CAELO_API int caelo_match(caelo_ctx *c, const float *f0, int ld0, int64_t k0_max, const int32_t *n0, const float *f1,
                           int ld1, int64_t k1_max, const int32_t *n1, int dim, int64_t *pair_idx, void *ws, void *stream) {
@@ -385,11 +393,13 @@ CAELO_API int caelo_match_profile(caelo_ctx *c, const float *const *rows, int n_
 
 int match_set(const caelo_pair_set &ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, hipStream_t s) {
     CAELO_REQUIRE(ps.n >= 1 && ps.n <= CAELO_FB_MAX, "bad pair count");
-    CAELO_REQUIRE(dim > 0 && dim <= MT_MAXDIM && ld0 >= dim && ld1 >= dim && k0_max > 0 && k1_max > 0, "bad shape");
+    CAELO_REQUIRE(dim > 0 && dim <= MSW_MAXDIM && ld0 >= dim && ld1 >= dim && k0_max > 0 && k1_max > 0, "bad shape");
     CAELO_REQUIRE(k0_max + 16 * MM_STEP_TILES < MM_IDX_MASK, "too many frame-0 rows (the row index travels in 21 key bits)");
     // the f16 screen + exact certification (match_screen.inc) for every descriptor width that leaves room for the two norm slots in
     // K = 64 (the reference's descriptors are 60 wide); wider ones: the all-f64 kernel.  Same pair_idx bit for bit
-    // (tests/test_gpu_parity.py::test_match_shape_sweep_vs_oracle covers both).
+    // (tests/test_gpu_parity.py::test_match_shape_sweep_vs_oracle covers both).  Past 64 the screen again, over several K = 64
+    // blocks (match_screen_wide.inc; the workspace is caelo_match_ws_bytes_dim's).
+    if (dim > MT_MAXDIM) return match_set_wide(ps, ld0, k0_max, ld1, k1_max, dim, s);
     if (dim <= 62) {
         const int64_t kpad = ms_pad16(k0_max > k1_max ? k0_max : k1_max);
         bool v4 = (dim % 4 == 0) && (ld0 % 4 == 0) && (ld1 % 4 == 0);

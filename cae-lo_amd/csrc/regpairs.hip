@@ -12,6 +12,8 @@
 // of a frame's rows (262 KB) hits L2.  Outputs are indexed by the table entry, so the caller sees its own order.
 // Host cost per call: ONE wait for the stream (the read-back of the table and of n_key, 8 B per pair + 4 B per frame), the sort, and
 // three host vectors; nothing goes up -- a slice's order is part of its launches' arguments.
+// caelo_register_pairs_desc: the same walk with the NN match on descriptors of the caller's ([n_frames][1024][ld_desc], up to 256
+// wide) instead of the rows' columns 0:60; xyz and the counts still come from the rows.
 #include "caelo_internal.h"
 
 #include <algorithm>
@@ -20,7 +22,7 @@
 namespace {
 constexpr int64_t RP_ALIGN = 256;
 inline int64_t rp_up(int64_t b) { return (b + RP_ALIGN - 1) / RP_ALIGN * RP_ALIGN; }
-inline int64_t rp_match_stride() { return rp_up(caelo_match_ws_bytes(CAELO_MAX_KEYPTS)); }
+inline int64_t rp_match_stride(int dim = 60) { return rp_up(caelo_match_ws_bytes_dim(CAELO_MAX_KEYPTS, dim)); }
 inline int64_t rp_ransac_stride() { return rp_up(caelo_ransac_ws_bytes()); }
 }  // namespace
 
@@ -30,9 +32,17 @@ CAELO_API int64_t caelo_register_pairs_ws_bytes(int64_t n_pairs) {
     return CAELO_FB_MAX * (rp_match_stride() + rp_ransac_stride());
 }
 
-CAELO_API int caelo_register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
-                                   const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
-                                   caelo_ransac_cert *certs_out, void *ws, void *stream) {
+CAELO_API int64_t caelo_register_pairs_ws_bytes_dim(int64_t n_pairs, int dim) {
+    if (n_pairs < 0) return 0;
+    return CAELO_FB_MAX * (rp_match_stride(dim) + rp_ransac_stride());
+}
+
+// desc == nullptr: the rows' own descriptors through match_table.  Otherwise the slice's pairs as a caelo_pair_set the host fills
+// from the table it has read back anyway (pair_of's other argument: the set travels in the kernel arguments like a slice's order)
+// and match_set, i.e. whichever match kernels `dim` selects; RANSAC never reads a descriptor and stays ransac_table.
+static int register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                          const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                          caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim) {
     CAELO_REQUIRE(pairs, "null pair table");
     CAELO_REQUIRE(n_frames >= 1 && n_frames < (1LL << 31), "n_frames must lie in [1, 2^31)");
     CAELO_REQUIRE(n_pairs >= 0 && n_pairs < (1LL << 31), "n_pairs must lie in [0, 2^31)");
@@ -70,16 +80,45 @@ CAELO_API int caelo_register_pairs(caelo_ctx *c, const float *rows, int64_t n_fr
     pt.rows = rows; pt.n_key = n_key; pt.pairs = pairs;
     pt.pair_idx = pair_idx_out; pt.rand = rand; pt.result = results_out; pt.mask = masks_out; pt.cert = certs_out;
     pt.cert_only = results_out ? 0 : 1;
-    pt.ws_match_stride = rp_match_stride(); pt.ws_ransac_stride = rp_ransac_stride();
+    pt.ws_match_stride = rp_match_stride(desc ? dim : 60); pt.ws_ransac_stride = rp_ransac_stride();
     pt.ws_match = (char *)ws;
     pt.ws_ransac = pt.ws_match + CAELO_FB_MAX * pt.ws_match_stride;
     pt.faults = c->faults;
     for (int64_t q0 = 0; q0 < n_pairs; q0 += CAELO_FB_MAX) {   // the slot workspaces are reused slice after slice: the stream orders them
         pt.n = (int32_t)std::min<int64_t>(CAELO_FB_MAX, n_pairs - q0);
         for (int z = 0; z < pt.n; ++z) pt.order[z] = order[(size_t)(q0 + z)];   // (a slice's order travels in the kernel arguments)
-        int rc = match_table(pt, s);
+        int rc;
+        if (desc) {
+            caelo_pair_set ps = {};
+            ps.n = pt.n;
+            for (int z = 0; z < pt.n; ++z) {
+                const int64_t q = pt.order[z], a = tab[(size_t)(2 * q)], b = tab[(size_t)(2 * q + 1)];
+                caelo_pair_dev &d = ps.p[z];
+                d.f0 = desc + a * (CAELO_MAX_KEYPTS * ld_desc); d.f1 = desc + b * (CAELO_MAX_KEYPTS * ld_desc);
+                d.n0 = n_key + a; d.n1 = n_key + b;
+                d.pair_idx = pair_idx_out + q * CAELO_MAX_KEYPTS;
+                d.ws_match = pt.ws_match + (int64_t)z * pt.ws_match_stride;
+            }
+            rc = match_set(ps, (int)ld_desc, CAELO_MAX_KEYPTS, (int)ld_desc, CAELO_MAX_KEYPTS, dim, s);
+        } else {
+            rc = match_table(pt, s);
+        }
         if (rc == CAELO_OK) rc = ransac_table(pt, s);
         if (rc) return rc;
     }
     return CAELO_OK;
+}
+
+CAELO_API int caelo_register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                                   const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                                   caelo_ransac_cert *certs_out, void *ws, void *stream) {
+    return register_pairs(c, rows, n_frames, n_key, pairs, n_pairs, rand, pair_idx_out, results_out, masks_out, certs_out, ws, stream, nullptr, 64, 60);
+}
+
+CAELO_API int caelo_register_pairs_desc(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                                        const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                                        caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim) {
+    CAELO_REQUIRE(desc, "null descriptors");
+    CAELO_REQUIRE(dim >= 1 && dim <= 256 && ld_desc >= dim && ld_desc < (1LL << 31), "dim must lie in [1, 256] and ld_desc in [dim, 2^31)");
+    return register_pairs(c, rows, n_frames, n_key, pairs, n_pairs, rand, pair_idx_out, results_out, masks_out, certs_out, ws, stream, desc, ld_desc, dim);
 }

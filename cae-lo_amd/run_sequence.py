@@ -6,6 +6,7 @@
     python run_sequence.py --scans <seq>/velodyne --calib <calib>/00/calib_.txt --out poses_/00.txt --save-artifacts
     python run_sequence.py --scans <raw KITTI seq>/velodyne --calib-angle 0.22 --out poses_/00.txt   # CorrectPC on the fly
     python run_sequence.py --scans <seq>/velodyne --frame-steps 1,5,10 --out poses_/00.txt   # + poses_/5_00.txt, poses_/10_00.txt, one extraction pass
+    python run_sequence.py --desc-dir <usip desc>/00 --desc-dim 128 --keypts-source usip --keypts-dir <usip keypts>/00 --out poses_/00.txt
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_sequence.py --synthetic 800 ...
 
 Frames are sharded contiguously over the ranks (one process per GPU); every rank runs its frames through the
@@ -330,6 +331,77 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
     return out
 
 
+def run_desc(eng, src, n, seed_base, chunk, steps, certify):
+    """--desc-dir: the pair stage alone on descriptors of another method (caelo.keysources.DescSource; no scan is read, nothing is
+    extracted).  Frames [0, n) chunk by chunk: a chunk's key points and descriptors become rows [k,1024,64] (xyz 60:63 | valid 63,
+    columns 0:60 zero and unread) and desc [k,1024,D]; ONE Engine.register_pairs(..., desc=) call registers the consecutive pairs
+    (i - 1, i) whose frame i the chunk holds and the pairs of every other step whose frame 1 it holds (framesteps.chunk_pairs), the
+    last max(steps) frames being carried from chunk to chunk.  Pair k of a step draws RandomState(seed_base + k), as in every other
+    run.  -> {step: framesteps.pack_results(...)}."""
+    others = [s for s in steps if s != 1]
+    m = max(1, framesteps.carry_frames(steps))
+    results = {s: [] for s in [1] + others}
+    carried, base = None, 0
+    for c0 in range(0, n, chunk):
+        c1 = min(n, c0 + chunk)
+        rows = np.zeros((c1 - c0, 1024, 64), np.float32)
+        desc = np.zeros((c1 - c0, 1024, src.dim), np.float32)
+        nk = np.zeros(c1 - c0, np.int32)
+        for j in range(c1 - c0):
+            pts, d = src.frame(c0 + j)
+            k = pts.shape[0]
+            if k < 1:
+                raise ValueError("frame %d has no key points" % (c0 + j))
+            rows[j, :k, 60:63], rows[j, :k, 63], desc[j, :k], nk[j] = pts, 1.0, d, k
+        rows, desc, nk = (torch.from_numpy(a).to(eng.device) for a in (rows, desc, nk))
+        if carried is not None:
+            rows, desc, nk = torch.cat([carried[0], rows]), torch.cat([carried[1], desc]), torch.cat([carried[2], nk])
+        else:
+            base = c0
+        todo = [(1, i - 1, i - 1, i) for i in range(max(c0, 1), c1)] + [(s, k, a, b) for s in others for k, a, b in framesteps.chunk_pairs(c0, c1, s, 0)]
+        if todo:
+            out = eng.register_pairs(rows, nk, [(a - base, b - base) for _, _, a, b in todo], [seed_base + k for _, k, _, _ in todo],
+                                     certify=certify, desc=desc)
+            for s in results:
+                sel = [i for i, t in enumerate(todo) if t[0] == s]
+                if sel:
+                    results[s].append((np.array([todo[i][1] for i in sel], dtype=np.int64), out.results[sel]))
+        keep_n = min(m, rows.shape[0])
+        base = c1 - keep_n
+        carried = (rows[rows.shape[0] - keep_n:].clone(), desc[desc.shape[0] - keep_n:].clone(), nk[nk.shape[0] - keep_n:].clone())
+    return {s: framesteps.pack_results(results[s], s) for s in results}
+
+
+def main_desc(args, ap, steps):
+    """The --desc-dir run (one GPU): the files every other run writes, under the same names."""
+    from caelo import keysources
+    if args.gpus > 1:
+        ap.error("--desc-dir runs on one GPU (--gpus %d): a pair table of a whole sequence takes seconds; sharding it is not implemented" % args.gpus)
+    if args.scans or args.synthetic or args.save_artifacts or args.calib_angle is not None:
+        ap.error("--desc-dir reads no scans: --scans, --synthetic, --save-artifacts and --calib-angle do not go with it")
+    src = keysources.DescSource(args.desc_dir, args.desc_dim, args.keypts_source, args.keypts_dir, args.features_from)
+    n = src.n_frames()
+    if n < 2:
+        raise ValueError("--desc-dir %s: need at least frames 0 and 1 (%s, %s)" % (args.desc_dir, keysources.desc_path(args.desc_dir, 0), keysources.desc_path(args.desc_dir, 1)))
+    if not (0 <= args.seed_base and args.seed_base + n - 2 < 2 ** 32):
+        ap.error("--seed-base %d: the seeds seed_base + i - 1 of pairs i = 1 .. %d must lie in [0, 2^32)" % (args.seed_base, n - 1))
+    if framesteps.carry_frames(steps) > n:
+        ap.error("--frame-steps %s: the largest step exceeds the %d frames" % (args.frame_steps, n))
+    eng = Engine(device=0)
+    Tr = stageio.read_calib_tr(args.calib) if args.calib else None
+    t0 = time.time()
+    res = run_desc(eng, src, n, args.seed_base, args.chunk, steps, not args.no_certify)
+    dt = time.time() - t0
+    for s_, (rel, ok, nin, npairs, its) in res.items():
+        assert len(rel) == len(framesteps.step_pairs(n, s_))
+        stageio.write_poses(framesteps.step_path(args.out, s_), stageio.chain_poses(rel, Tr) if s_ == 1 else framesteps.expand_rows(stageio.chain_poses(rel, Tr), n, s_))
+        if args.matchability:
+            from caelo import evaluate as ev
+            ev.save_matchability(framesteps.step_path(args.matchability, s_), nin, npairs, its)
+        print("step %d: %d pairs (%d solved) on %d-d descriptors -> %s" % (s_, len(rel), int(np.sum(ok)), src.dim, framesteps.step_path(args.out, s_)))
+    print("%d frames in %.2f s (reading key points and descriptors included)" % (n, dt))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--synthetic", type=int, default=0, help="number of synthetic 64x2000 scans (caelo.synth)")
@@ -365,6 +437,12 @@ def main():
     ap.add_argument("--keypts-dir", help="directory of the --keypts-source files")
     ap.add_argument("--features-from", help="directory of <frame:06d>.bin.mat files (KeyPts / Features / Weights, isLoadFeaturesFromFile, "
                                             "PoseEstimation.py:49-66): only the pair stage runs on them")
+    ap.add_argument("--desc-dir", help="register on descriptors of another method: <desc-dir>/<frame:06d>.bin, [-1, --desc-dim] f32 (the published "
+                                       "comparison's layout, GenerateTrajactory.m:193-197), up to 256 wide.  Key points: --keypts-source 3dfeatnet|usip "
+                                       "with --keypts-dir, or the KeyPts of --features-from files (their Features are ignored).  No scans are read; "
+                                       "only the pair stage runs (Engine.register_pairs(desc=)), with the seeds, --frame-steps, --matchability, "
+                                       "--no-certify and --out naming of every other run.  One GPU")
+    ap.add_argument("--desc-dim", type=int, default=None, help="width of the --desc-dir descriptors (e.g. 128 for USIP, 32 for 3DFeatNet)")
     ap.add_argument("--calib-angle", type=float, default=None, metavar="DEG",
                     help="correct every scan by the reference's CorrectPC (Transformations.py:28-39: each point rotated by DEG degrees about "
                          "p x z, the HDL-64E's vertical-angle calibration; raw KITTI scans: 0.22) on the device, inside the batch launch, before "
@@ -384,6 +462,13 @@ def main():
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
+    if args.desc_dir or args.desc_dim is not None:
+        if not args.desc_dir:
+            ap.error("--desc-dim goes with --desc-dir")
+        try:
+            return main_desc(args, ap, framesteps.parse_steps(args.frame_steps))
+        except ValueError as e:
+            ap.error(str(e))
     # pair (i - 1, i) draws RandomState(seed_base + i - 1), which takes seeds in [0, 2^32): both loaders refuse a base that leaves it
     # for any frame with a pair (frame 0 has none) -- before any device work, the same way whichever loader would run
     n_frames = len(glob.glob(os.path.join(args.scans, "*.bin"))) if args.scans else args.synthetic

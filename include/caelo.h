@@ -242,14 +242,17 @@ int caelo_encode_profile(caelo_ctx *ctx, const uint64_t *bits, int64_t n_patches
                          int out_stride, void *ws, void *stream, float *ms_host);
 
 /* NN match  (Match.py:257-258): pair_idx[j] = argmin_i ||f0[i]-f1[j]|| (f64, first minimum).
- * f0 [k0][ld0], f1 [k1][ld1] (leading dimensions in floats, >= dim, dim <= 64); k0/k1 read from the
+ * f0 [k0][ld0], f1 [k1][ld1] (leading dimensions in floats, >= dim, dim <= 256; wider: CAELO_ERR_ARG); k0/k1 read from the
  * n0/n1 device words when non-null.
- * ws: caelo_match_ws_bytes(max(k0_max, k1_max)) bytes: two statistics counters the calls only add to (columns re-scanned
+ * ws: a call with dim <= 64 is sized by caelo_match_ws_bytes(max(k0_max, k1_max)), a call with dim > 64 by
+ * caelo_match_ws_bytes_dim(max(k0_max, k1_max), dim) (which returns caelo_match_ws_bytes' figure for dim <= 64 and never
+ * shrinks as dim grows: a workspace sized for the widest descriptor serves every call): two statistics counters the calls only add to (columns re-scanned
  * exactly, columns decided between two rows; zero-fill the first 256 bytes once if you read them) and the scratch images of
  * the two frames (every call rewrites them).  Nothing crosses workgroups.  The distances are screened on the f16 matrix pipe
  * inside a rigorous error window and only the rows that can be the minimum are evaluated in float64 like scipy's cdist: the
  * result is the float64 argmin, bit for bit. */
 int64_t caelo_match_ws_bytes(int64_t k_max);
+int64_t caelo_match_ws_bytes_dim(int64_t k_max, int dim);
 int caelo_match(caelo_ctx *ctx, const float *f0, int ld0, int64_t k0_max, const int32_t *n0, const float *f1, int ld1,
                 int64_t k1_max, const int32_t *n1, int dim, int64_t *pair_idx, void *ws, void *stream);
 
@@ -595,6 +598,18 @@ int64_t caelo_register_pairs_ws_bytes(int64_t n_pairs);
 int caelo_register_pairs(caelo_ctx *ctx, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
                          const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
                          caelo_ransac_cert *certs_out, void *ws, void *stream);
+
+/* caelo_register_pairs on descriptors of the caller's: desc [n_frames][1024][ld_desc] f32 (device, ld_desc >= dim floats per key
+ * point, 1 <= dim <= 256) replaces columns 0:60 of the rows in the NN match; the rows still supply xyz (60:63) and n_key the
+ * counts, and their columns 0:60 are not read.  Everything else is caelo_register_pairs: slices of 8 pairs ordered by
+ * (frame 0, frame 1), the checks before any launch, results and / or certificates.  The match of a slice is caelo_match's for that
+ * width (dim <= 62 the f16 screen, 63 / 64 the float64 kernel, wider the screen over several blocks) over the slice's pairs in ONE
+ * launch set; desc = rows with ld_desc 64 and dim 60 gives caelo_register_pairs' bits.
+ * ws: caelo_register_pairs_ws_bytes_dim(n_pairs, dim) bytes (caelo_register_pairs_ws_bytes' figure for dim <= 64). */
+int64_t caelo_register_pairs_ws_bytes_dim(int64_t n_pairs, int dim);
+int caelo_register_pairs_desc(caelo_ctx *ctx, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                              const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                              caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim);
 
 #ifdef __cplusplus
 }
