@@ -32,6 +32,11 @@ RESPOND_H5 = os.path.join(_DEFAULT_WEIGHTS, "SphericalRingPCRespondLayer.h5")
 ENCODER_H5 = os.path.join(_DEFAULT_WEIGHTS, "EncoderModel4VoxelPatch.h5")
 
 
+# Keras layouts of the two networks' weights, kernel then bias per layer (Engine.set_encoder_weights / set_respond_weights)
+ENCODER_SHAPES = [(3, 3, 3, 1, 8), (8,), (3, 3, 3, 8, 16), (16,), (3, 3, 3, 16, 32), (32,), (2048, 200), (200,), (200, 20), (20,)]
+RESPOND_SHAPES = [(3, 3, 3, 32), (32,), (1, 1, 32, 8), (8,)]
+
+
 def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -647,10 +652,33 @@ class Engine:
     def load_weights(self, path):
         kind, ws = read_keras_weights(path)
         if kind == "respond":
-            _ffi.check(self.lib.caelo_set_respond_weights(self.ctx, *[_hptr(w) for w in ws]))
+            self.set_respond_weights(ws)
         else:
-            _ffi.check(self.lib.caelo_set_encoder_weights(self.ctx, *[_hptr(w) for w in ws]))
+            self.set_encoder_weights(ws)
         return kind
+
+    @staticmethod
+    def _weight_arrays(ws, shapes, what):
+        """A caller's weight list as contiguous f32 arrays; ValueError unless array i has the Keras shape ``shapes[i]`` (kernel then
+        bias per layer) or is that many elements flat."""
+        ws = [np.ascontiguousarray(w, dtype=np.float32) for w in ws]
+        ok = len(ws) == len(shapes) and all(w.shape == s or w.shape == (int(np.prod(s)),) for w, s in zip(ws, shapes))
+        if not ok:
+            raise ValueError("%s weights: %d arrays of shapes %s wanted, got %s" % (what, len(shapes), list(shapes), [w.shape for w in ws]))
+        return ws
+
+    def set_encoder_weights(self, ws):
+        """caelo_set_encoder_weights: the ten arrays of the encoder (conv3d_1..3, dense_1, dense_2: kernel, bias each) as float32
+        arrays in Keras layout.  Every derived operand image of the context is rebuilt; work already issued is waited for first."""
+        ws = self._weight_arrays(ws, ENCODER_SHAPES, "encoder")
+        torch.cuda.synchronize(self.device)
+        _ffi.check(self.lib.caelo_set_encoder_weights(self.ctx, *[_hptr(w) for w in ws]))
+
+    def set_respond_weights(self, ws):
+        """caelo_set_respond_weights: conv2d_1 and conv2d_2 of the response layer (kernel, bias each), float32 arrays in Keras layout."""
+        ws = self._weight_arrays(ws, RESPOND_SHAPES, "response-layer")
+        torch.cuda.synchronize(self.device)
+        _ffi.check(self.lib.caelo_set_respond_weights(self.ctx, *[_hptr(w) for w in ws]))
 
     def _ws(self, kind, need):
         """Scratch bytes of the current stream for one entry point (grown on demand, never shared across streams)."""

@@ -2,8 +2,12 @@
 network): max |difference| after pool2 (P2), after conv3 (F3), of the Dense(200) pre-activations and of the descriptors,
 on every patch of the quantised golden frame.  `CAELO_ENC_S1=f32 python tools/enc_layer_errors.py` measures round 2's
 f32-input stage 1 for comparison.  The budget table of tests/test_gpu_parity.py::test_encoder_layer_error_budget is
-3 x what this prints for the default kernels."""
-import os, sys
+3 x what this prints for the default kernels.
+
+`--family NAME` (repeatable; `--family all`): the same layers under one of the seeded weight families of tests/netref64.py, judged
+against the FLOAT64 network instead of the oracle, for both stage-1 kernels, on the 70 edge patches of the family tests plus every
+sixth patch of the golden frame.  FAMILY_BUDGET of tests/test_weight_families_gpu.py is 3 x the larger of the two kernels' lines."""
+import argparse, os, sys
 import numpy as np
 import torch
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,15 +16,42 @@ import caelo; caelo.configure_runtime()
 import oracle as orc
 from caelo.engine import Engine
 
+ap = argparse.ArgumentParser()
+ap.add_argument("--family", action="append", default=[])
+args = ap.parse_args()
 eng = Engine(device=0)
+golden_bits = np.ascontiguousarray(np.load(os.path.join(REPO, "tests", "golden", "frame_q0.npz"))["patch_bits"].reshape(-1, 64))
+
+
+def report(layers, bd1, ref):
+    p2, f3, pre, out = (x.cpu().numpy() for x in layers)
+    h = np.tanh(pre.astype(np.float64) + np.asarray(bd1, np.float64))
+    for name, a, b in (("P2", p2, ref[0]), ("F3", f3, ref[1]), ("tanh(Dense(200))", h, ref[2]), ("descriptors", out, ref[3])):
+        d = np.abs(a.astype(np.float64) - b)
+        print("%-18s max abs %.3e   mean abs %.3e   element-wise rel (floor 0.1) %.3e" % (name, d.max(), d.mean(), (d / np.maximum(np.abs(b), 0.1)).max()))
+
+
+if args.family:
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import netref64 as nr
+    bits = np.ascontiguousarray(np.concatenate([nr.edge_patches(70), golden_bits[::6]]))
+    t = torch.from_numpy(bits.view(np.int64)).to(eng.device)
+    for fam in (nr.ENCODER_FAMILIES if "all" in args.family else args.family):
+        ws = nr.encoder_family(fam)
+        ref = nr.encoder_layers(ws, bits)
+        eng.set_encoder_weights(ws)
+        for reference in (False, True):
+            eng.set_encoder_reference(reference)
+            layers = eng.encode_layers(t)
+            torch.cuda.synchronize()
+            print("family %s, %d patches, stage 1 = %s, against float64" % (fam, len(bits), "k_enc_stage1 (f32)" if reference else "k_enc_stage1x"))
+            report(layers, ws[7], ref)
+            sys.stdout.flush()
+    sys.exit(0)
+
 if os.environ.get("CAELO_ENC_S1") == "f32":   # (read HERE, by the tool: the library has no environment switch for arithmetic)
     eng.set_encoder_reference(True)
 _, enc_m = orc.load_models(os.path.join(REPO, "weights", "SphericalRingPCRespondLayer.h5"), os.path.join(REPO, "weights", "EncoderModel4VoxelPatch.h5"))
-bits = np.ascontiguousarray(np.load(os.path.join(REPO, "tests", "golden", "frame_q0.npz"))["patch_bits"].reshape(-1, 64))
-o_p2, o_f3, o_h, o_out = enc_m.predict_layers(bits)
-p2, f3, pre, out = eng.encode_layers(torch.from_numpy(bits.view(np.int64)).to(eng.device))
+layers = eng.encode_layers(torch.from_numpy(golden_bits.view(np.int64)).to(eng.device))
 torch.cuda.synchronize()
-h = np.tanh((pre.cpu().numpy().astype(np.float64) + enc_m.w[7].astype(np.float64)))
-for name, a, b in (("P2", p2.cpu().numpy(), o_p2), ("F3", f3.cpu().numpy(), o_f3), ("tanh(Dense(200))", h, o_h), ("descriptors", out.cpu().numpy(), o_out)):
-    d = np.abs(a.astype(np.float64) - b)
-    print("%-18s max abs %.3e   mean abs %.3e   element-wise rel (floor 0.1) %.3e" % (name, d.max(), d.mean(), (d / np.maximum(np.abs(b), 0.1)).max()))
+report(layers, enc_m.w[7], enc_m.predict_layers(golden_bits))
