@@ -1215,6 +1215,17 @@ class Engine:
                                           self.stream))
         return FrameFeatures(rows, kpix, nkey, status, flags)
 
+    def extract_frame_tables(self):
+        """Test aid: what the last ``extract`` on the current stream left in its workspace (caelo_extract_ws_frame_offset) -> host
+        arrays (bits [3072,64] uint64, the patches by key point * 3 + scale; count; list [3072] int32; slot_of [3072] int32) of
+        csrc/dedup.hip's caelo_dedup_tables.  Synchronises."""
+        ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
+        off, n = int(self.lib.caelo_extract_ws_frame_offset()), 3 * MAX_K
+        torch.cuda.current_stream(self.device).synchronize()
+        raw = ws[off:off + n * 512 + 256 + 8 * n].cpu().numpy()
+        tab = raw[n * 512:].view(np.int32)
+        return raw[:n * 512].view(np.uint64).reshape(n, 64), int(tab[0]), tab[64:64 + n].copy(), tab[64 + n:64 + 2 * n].copy()
+
     def resolve_ties(self, ff, pc):
         """The fused path (extract / Pipeline.run) builds voxel SETS; where the 496-nearest cut of Voxel.py:195-196 splits a class
         of equidistant voxels it uses a canonical rule and sets flag bit 2, because scikit-learn's choice depends on the ORDER of

@@ -1345,7 +1345,11 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
         // and pair kernels of the other streams (frames/s at 120 batches against the grid: 448 / 512 / 576 / 640 / 704 / 768 workgroups
         // = 20.0 / 20.4 / 20.2 / 19.6 / 19.2 / 17.8 k, profiles/r04_pipe_sweep.txt); alone, all three (207 against 248 us)
         const int64_t capx = slots_env > 0 ? slots_env : ((ein.yield & 1) ? (int64_t)slots1x * 2 / 3 : slots1x);
-        const unsigned gx = (unsigned)(n_patches < capx ? n_patches : capx);
+        unsigned gx = (unsigned)(n_patches < capx ? n_patches : capx);
+        // a by-hand grid below eight workgroups would leave the queues gridDim.x .. 7 without a workgroup (item j belongs to queue
+        // j % 8, block b serves queue b % 8 only): their patches would keep stale P2 without any error.  The default grid has at
+        // least eight workgroups whenever the launch has eight items.
+        if (slots_env > 0 && gx < 8u && n_patches >= 8) gx = 8u;
         if (ev) {   // profiling calls count the MFMAs the kernel executes (bench.py's roofline); same code otherwise
             CAELO_HIP(hipMemsetAsync(mfma_count, 0, 1024, s));
             CAELO_HIP(hipEventRecord(ev[0], s));

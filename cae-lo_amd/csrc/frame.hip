@@ -136,6 +136,8 @@ static ExtractLayout extract_layout() {
 }
 
 CAELO_API int64_t caelo_extract_ws_bytes(void) { return (int64_t)extract_layout().total; }
+// (read-only, for tests of the de-duplication tables: where the last frame's patch bits and caelo_dedup_tables lie in the workspace)
+CAELO_API int64_t caelo_extract_ws_frame_offset(void) { return (int64_t)extract_layout().bits; }
 
 // The fused path in two halves so that the frame pipeline can put an event edge between them:
 // front = clear + ring image + response + keypoints + voxel map + patch gather (latency-bound kernels),

@@ -48,7 +48,10 @@ typedef enum {
 /* device-side status bits (int32 word, OR-ed by kernels) */
 #define CAELO_ST_COL_OOB 1        /* a point projects to column 1800: IndexError at SphericalRing.py:91 */
 #define CAELO_ST_VOXEL_OOB 2      /* voxel index outside its block: IndexError at Voxel.py:139 */
-#define CAELO_ST_MAP_FULL 4       /* voxel hash table overflow (capacity bug, never data) */
+#define CAELO_ST_MAP_FULL 4       /* voxel hash table overflow: the cloud holds more bricks than a table of the map has slots (scale 0:
+                                    one per point of max_points; scales 1 / 2: a quarter / a sixteenth of that).  The frame's voxels, patches
+                                    and rows are unspecified; the map itself stays usable -- the next build on it, of either kind, gives what
+                                    a new map gives -- and a caller retries the frame with a larger map */
 #define CAELO_ST_FEW_VOXELS 8     /* a scale holds < 496 voxels: sklearn ValueError at Voxel.py:195-196 */
 #define CAELO_ST_FEW_KEYPTS 16    /* K <= 50: assert at SphericalRing.py:286 */
 #define CAELO_ST_NONFINITE 32     /* a NaN coordinate: int(nan) raises ValueError at SphericalRing.py:86-88 / Voxel.py:122-124 (an
@@ -365,6 +368,11 @@ int caelo_host_certify(const void *certs_host, int64_t k, const double *const *r
  * 3 x max_points x 24 B of sort buffers); later calls allocate nothing.  Frames without a tie-split patch get the default mode's
  * results, bit for bit. */
 int64_t caelo_extract_ws_bytes(void);
+/* Byte offset, inside the caelo_extract workspace, of the frame buffer the last call left: the bit-packed patches [3072][64] u64 (patch
+ * = key point * 3 + scale) followed by the de-duplication tables -- int32 count, 63 int32 of padding, int32 list[3072] (the patches
+ * that were encoded, coarsest scale first), int32 slot_of[3072] (a listed patch: its position in list; a copy: -(representative + 1)).
+ * Read-only; meant for tests of the de-duplication. */
+int64_t caelo_extract_ws_frame_offset(void);
 int caelo_extract(caelo_ctx *ctx, caelo_voxmap *map, const float *pc, int64_t n, int dist_channels, int mode, float *key_pts,
                   int kp_ld, float *features, int feat_ld, float *valid, int valid_ld, int64_t *key_pixels,
                   int32_t *n_key, uint8_t *flags, int32_t *status, void *ws, void *stream);

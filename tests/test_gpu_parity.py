@@ -1532,8 +1532,8 @@ def test_dense1_tile_sizes_are_bit_identical(engine):
 @pytest.mark.gpu
 def test_library_reads_no_arithmetic_switch_from_the_environment():
     """the shipped library reads no environment variable that changes arithmetic.  What it still reads are
-    scheduling / tuning / diagnostic knobs; every one of them is listed here, and the kernels' results under them are covered by
-    the bit-identity tests of the pipeline (pacing, plans, streams) and of the Dense(200) tile size."""
+    scheduling / tuning / diagnostic knobs; every one of them is listed here, and tests/test_env_knobs_gpu.py runs each of them once
+    (its registry: the values, or the test that sets the knob) against the results under the default environment, bit for bit."""
     import re
     src = os.path.join(os.path.dirname(GOLDEN), "..", "cae-lo_amd", "csrc")
     seen = set()
