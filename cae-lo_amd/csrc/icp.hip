@@ -15,6 +15,8 @@
 #include "caelo_rigid.h"
 
 #define ICP_TILE 1024
+#define ICP_TERMS 16
+#define ICP_STATE_BYTES 512  // the state record's share of the workspace
 
 struct IcpState {
     double R_star[9], T_star[3];
@@ -25,14 +27,17 @@ struct IcpState {
     int32_t n_pts, n_planar;  // pairs of the last evaluated iteration
     int32_t cnt_pts, cnt_planar;  // scratch: inlier counters of the iteration in flight
     int32_t pad;
+    // ICP_Pt2PtAndPt2Plane from iteration 100 on (:151-153): the pair count and the fifteen sums over the planar pairs of
+    // iteration 99.  Both arrays of those pairs are fitted again as they were then, so their sums are all that is needed
+    double stale[ICP_TERMS];
 };
-static_assert(sizeof(IcpState) <= sizeof(caelo_icp_result) + 64, "state record layout");
+static_assert(sizeof(IcpState) <= ICP_STATE_BYTES, "the state record outgrew its share of the workspace");
 
 // nearest neighbour in set 0 (stride ld0) of every point of set 1 (stride ld1); pairs closer than the threshold of the
 // state record (which = 0: thr0, 1: thr1).  Exact f64 distance, first minimum, like sklearn's kd-tree on these inputs.
 __global__ void __launch_bounds__(256) k_icp_nn2(const float *__restrict__ p0, int ld0, int n0, const float *__restrict__ p1, int ld1, int n1,
                                                  IcpState *st, int which, int64_t *__restrict__ idx0, uint8_t *__restrict__ mask) {
-    if (st->done) return;
+    if (st->done || (which && st->iter >= 100)) return;  // from iteration 100 on the planar pairs are not searched again (:151-153)
     __shared__ float tile[ICP_TILE * 3];
     const int tid = threadIdx.x;
     const int j = blockIdx.x * blockDim.x + tid;
@@ -76,7 +81,6 @@ __device__ inline bool planar_pair(const float *pn0, const float *pn1, const int
     return (double)dist < thr0;                                                                                         // :109
 }
 
-#define ICP_TERMS 16
 struct IcpParams {
     int32_t max_iter, min_iter, min_pairs, fail_only_first;  // fail_only_first: too few pairs is a failure only at iteration 0 (:166-169)
     double decay0, decay1, small_shift, ep;
@@ -93,7 +97,11 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
     __shared__ int s_stop;
     const int tid = threadIdx.x;
     const double thr0 = st->thr0;
-    const bool use_pts = st->iter < 100;  // :146-152 (the loop never gets there with the reference's maxIterTimes = 50)
+    // :147-153: from iteration 100 on ICP_Pt2PtAndPt2Plane fits neither the point pairs nor new planar pairs but the planar
+    // pairs of iteration 99, pedals and frame-1 points as they were then (the reference's maxIterTimes = 50 never gets
+    // there; ICP has no such branch)
+    const int iter0 = st->iter;
+    const bool stale = prm.planar && iter0 >= 100;
     double a[ICP_TERMS + 2];
 #pragma unroll
     for (int t = 0; t < ICP_TERMS + 2; ++t) a[t] = 0.0;
@@ -106,14 +114,31 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
         a[10] += y1 * x0; a[11] += y1 * y0; a[12] += y1 * z0;                         \
         a[13] += z1 * x0; a[14] += z1 * y0; a[15] += z1 * z0;                         \
     }
+    if (prm.planar && iter0 == 99) {  // the planar pairs on their own, kept for the iterations that follow
+        for (int j = tid; j < m1; j += 256) {
+            float pedal[3], in1[3];
+            if (!planar_pair(pn0, pn1, idx_q, mask_q, j, thr0, pedal, in1)) continue;
+            ICP_ACC(pedal[0], pedal[1], pedal[2], in1[0], in1[1], in1[2])
+        }
+#pragma unroll
+        for (int t = 0; t < ICP_TERMS; ++t) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
+            if ((tid & 63) == 0) red[tid >> 6][t] = a[t];
+            a[t] = 0.0;
+        }
+        __syncthreads();
+        if (tid < ICP_TERMS) st->stale[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        __syncthreads();
+    }
     for (int i = tid; i < n1; i += 256) {
         if (!mask_p[i]) continue;
         a[16] += 1.0;
-        if (!use_pts) continue;
+        if (stale) continue;
         const float *u = pc0 + 3 * (size_t)idx_p[i], *v = pc1 + 3 * (size_t)i;
         ICP_ACC(u[0], u[1], u[2], v[0], v[1], v[2])
     }
-    if (prm.planar) {
+    if (prm.planar && !stale) {
         for (int j = tid; j < m1; j += 256) {
             float pedal[3], in1[3];
             if (!planar_pair(pn0, pn1, idx_q, mask_q, j, thr0, pedal, in1)) continue;
@@ -132,6 +157,10 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
     if (tid == 0) {
         double s[ICP_TERMS + 2];
         for (int t = 0; t < ICP_TERMS + 2; ++t) s[t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
+        if (stale) {  // the count that the reference goes on printing is the one of iteration 99 as well (:199)
+            for (int t = 0; t < ICP_TERMS; ++t) s[t] = st->stale[t];
+            s[17] = st->stale[0];
+        }
         const int pairs = (int)s[0];
         st->n_pts = (int)s[16];
         st->n_planar = (int)s[17];
@@ -209,7 +238,7 @@ __global__ void k_icp_result(const IcpState *st, caelo_icp_result *out) {
 }
 
 CAELO_API int64_t caelo_icp_loop_ws_bytes(int64_t n1, int64_t m1) {
-    return 256 + ((n1 + m1) * 9 + 255) / 256 * 256 + 256;
+    return ICP_STATE_BYTES + ((n1 + m1) * 9 + 255) / 256 * 256 + 256;
 }
 
 CAELO_API int caelo_icp(caelo_ctx *c, const float *pc0, int64_t n0, float *pc1, int64_t n1, const float *planar0, int64_t m0,
@@ -226,7 +255,7 @@ CAELO_API int caelo_icp(caelo_ctx *c, const float *pc0, int64_t n0, float *pc1, 
     CAELO_REQUIRE(prm->max_iter >= 1 && prm->max_iter <= 1000, "max_iter must be in [1, 1000]");
     hipStream_t s = caelo_stream(stream);
     IcpState *st = (IcpState *)ws;
-    int64_t *idx_p = (int64_t *)((char *)ws + 256);
+    int64_t *idx_p = (int64_t *)((char *)ws + ICP_STATE_BYTES);
     int64_t *idx_q = idx_p + n1;
     uint8_t *mask_p = (uint8_t *)(idx_q + (planar ? m1 : 0));
     uint8_t *mask_q = mask_p + n1;

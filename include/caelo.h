@@ -408,6 +408,9 @@ int caelo_icp_step(caelo_ctx *ctx, const float *pc0, int64_t n0, float *pc1, int
  * Per iteration: nearest neighbours (exact float64 distance, first minimum) of both sets, the gates, ONE SolveRT over all pairs,
  * R_star / T_star accumulated in float64, the Euler-angle stop rule and the threshold decay -- no host synchronisation; `result`
  * (device) is complete when the stream has passed the call.  ws: caelo_icp_loop_ws_bytes(n1, m1) bytes.
+ * From iteration 100 on, ICP_Pt2PtAndPt2Plane fits the planar pairs of iteration 99 alone, as they were then (MyICP.py:151-153:
+ * the same (R, T) every time; min_pairs applies to that count and n_inliers_planar keeps it, n_inliers_pts is still counted);
+ * ICP goes on as before.  With max_iter = k the result is the loop's state after k iterations.
  * Regime: the reference's use -- up to 50 iterations on a few thousand extended key points.  Every iteration is an exact
  * brute-force nearest-neighbour pass (O(n0 n1) float64 distances) and a one-workgroup update, and ALL max_iter (<= 1000)
  * iterations are enqueued up front (those after convergence return at once): tens of thousands of points or hundreds of

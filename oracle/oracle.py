@@ -145,9 +145,26 @@ def nearest_neighbours(PC0, PC1, chunk=256):
     return dist, idx
 
 
+def _gate_margin(distances, threshold):
+    """Smallest |distance - threshold| of one gate (inf for no distances): how far the gate is from flipping a pair."""
+    d = np.asarray(distances, np.float64)
+    return float(np.abs(d - threshold).min()) if d.size else float("inf")
+
+
+def _icp_step(steps, iterations, success, n_pts, n_planar, thr0, thr1, R_star, T_star, margin, moved):
+    """One entry of ``steps``: the loop's state after an iteration, as caelo_icp reports it when max_iter ends there --
+    iterations that moved the clouds so far, isSuccess, the pair counts of this iteration, the thresholds AFTER this
+    iteration's decay, R_star / T_star, the smallest gate margin of this iteration and whether the clouds moved."""
+    if steps is not None:
+        steps.append(dict(iterations=int(iterations), success=bool(success), n_pts=int(n_pts), n_planar=int(n_planar),
+                          thr0=float(thr0), thr1=float(thr1), R_star=np.array(R_star, np.float64),
+                          T_star=np.array(T_star, np.float64).reshape(3), margin=float(margin), moved=bool(moved)))
+
+
 def ICP(PC0, PC1, maxIterTimes=50, minIterTimes=20 - 1, inlierThreshold=0.5, smallShiftThreshold=0.05, decay_rate=0.9, ep=0.001,
-        trace=None):
-    """MyICP.py:26-72, statement by statement."""
+        trace=None, steps=None):
+    """MyICP.py:26-72, statement by statement.  ``trace``: (pairs, threshold used) per fitted iteration; ``steps``: one
+    _icp_step record per evaluated iteration, the one that finds too few pairs included."""
     PC0 = np.asarray(PC0); PC1 = np.asarray(PC1)
     R_star = np.eye(3, dtype=np.float64)
     T_star = np.zeros((3, 1), dtype=np.float64)
@@ -155,7 +172,9 @@ def ICP(PC0, PC1, maxIterTimes=50, minIterTimes=20 - 1, inlierThreshold=0.5, sma
         distances, indices = nearest_neighbours(PC0, PC1)                # :31-32
         idx1 = distances < inlierThreshold                               # :35
         idx0 = indices[idx1]                                             # :36-37
+        margin = _gate_margin(distances, inlierThreshold)
         if idx0.shape[0] < 100:                                          # :38-40
+            _icp_step(steps, iIter, False, idx0.shape[0], 0, inlierThreshold, 0.0, R_star, T_star, margin, False)
             return R_star, T_star, False
         R, T, _ = SolveRT(PC0[idx0, :], PC1[idx1, :])                    # :42-46
         PC1 = (np.dot(R, PC1.T) + T).T                                   # :49
@@ -165,23 +184,28 @@ def ICP(PC0, PC1, maxIterTimes=50, minIterTimes=20 - 1, inlierThreshold=0.5, sma
         normT = np.linalg.norm(T)                                        # :56
         if trace is not None:
             trace.append((int(idx0.shape[0]), float(inlierThreshold)))
-        if iIter >= minIterTimes and normEulers < ep and normT < ep:     # :57-59
-            break
-        if normEulers < smallShiftThreshold and normT < smallShiftThreshold:   # :63-65
+        converged = iIter >= minIterTimes and normEulers < ep and normT < ep   # :57-59
+        if not converged and normEulers < smallShiftThreshold and normT < smallShiftThreshold:   # :63-65
             inlierThreshold *= decay_rate
+        _icp_step(steps, iIter + 1, True, idx0.shape[0], 0, inlierThreshold, 0.0, R_star, T_star, margin, True)
+        if converged:
+            break
     return R_star, T_star, True
 
 
-def GetPtsInliners(PC0, PC1, inlierThreshold):
-    """MyICP.py:75-85."""
+def GetPtsInliners(PC0, PC1, inlierThreshold, margins=None):
+    """MyICP.py:75-85.  ``margins``: list that receives this gate's margin."""
     distances, indices = nearest_neighbours(PC0, PC1)
     idx1 = distances < inlierThreshold
+    if margins is not None:
+        margins.append(_gate_margin(distances, inlierThreshold))
     return PC0[indices[idx1], :], PC1[idx1, :]
 
 
-def GetPlanarPtsInliners(PtsWithNorm0, PtsWithNorm1, inlierThreshold0, inlierThreshold1):
+def GetPlanarPtsInliners(PtsWithNorm0, PtsWithNorm1, inlierThreshold0, inlierThreshold1, margins=None):
     """MyICP.py:88-114: planar pairs = (foot of the perpendicular from the frame-0 neighbour onto the plane through the
-    frame-1 point, that point).  An empty set raises like sklearn's fit (:94)."""
+    frame-1 point, that point).  An empty set raises like sklearn's fit (:94).  ``margins``: list that receives the
+    margins of both gates."""
     PC0, PC1, Norms1 = PtsWithNorm0[:, 0:3], PtsWithNorm1[:, 0:3], PtsWithNorm1[:, 3:6]
     if PC0.shape[0] == 0 or PC0.ndim != 2 or PC0.shape[1] == 0:
         raise ValueError("Found array with 0 sample(s) (shape=%s) while a minimum of 1 is required." % (PC0.shape,))
@@ -193,12 +217,17 @@ def GetPlanarPtsInliners(PtsWithNorm0, PtsWithNorm1, inlierThreshold0, inlierThr
     pedals = inliers1 + norms1 * np.tile(dist2Planes.reshape(dist2Planes.shape[0], 1), [1, 3])   # :106
     d = np.linalg.norm(pedals - inliers1, axis=1)                        # :108
     idx = (d < inlierThreshold0).flatten()                               # :109
+    if margins is not None:
+        margins += [_gate_margin(distances, inlierThreshold1), _gate_margin(d, inlierThreshold0)]
     return pedals[idx, :], inliers1[idx, :]
 
 
 def ICP_Pt2PtAndPt2Plane(PC0, PC1, PtsWithNorm0, PtsWithNorm1, maxIterTimes=50, minIterTimes=20 - 1, inlierThreshold0=0.5,
-                         decay_rate0=0.9, inlierThreshold1=2.0, decay_rate1=0.5, smallShiftThreshold=0.1, ep=0.01, rng=None, trace=None):
-    """MyICP.py:127-201, statement by statement (rng: RandomState standing in for NumPy's global generator at :137)."""
+                         decay_rate0=0.9, inlierThreshold1=2.0, decay_rate1=0.5, smallShiftThreshold=0.1, ep=0.01, rng=None, trace=None,
+                         steps=None):
+    """MyICP.py:127-201, statement by statement (rng: RandomState standing in for NumPy's global generator at :137).
+    ``trace``: (point pairs, planar pairs, thresholds used) per fitted iteration; ``steps``: one _icp_step record per
+    evaluated iteration, the one that finds too few pairs included."""
     PC0 = np.asarray(PC0); PC1 = np.asarray(PC1)
     PtsWithNorm0 = np.asarray(PtsWithNorm0); PtsWithNorm1 = np.array(PtsWithNorm1)
     R_star = np.eye(3, dtype=np.float64)
@@ -209,12 +238,18 @@ def ICP_Pt2PtAndPt2Plane(PC0, PC1, PtsWithNorm0, PtsWithNorm1, maxIterTimes=50, 
         PtsWithNorm1 = PtsWithNorm1[np.array(RandIdxes, dtype=np.int32), :]
     isSuccess = True
     for iIter in range(maxIterTimes):
-        in0p, in1p = GetPtsInliners(PC0, PC1, inlierThreshold0)          # :145
-        in0q, in1q = GetPlanarPtsInliners(PtsWithNorm0, PtsWithNorm1, inlierThreshold0, inlierThreshold1)   # :148 (iIter < 100)
-        inliers0, inliers1 = np.r_[in0p, in0q], np.r_[in1p, in1q]
+        margins = []
+        in0p, in1p = GetPtsInliners(PC0, PC1, inlierThreshold0, margins)   # :145
+        if iIter < 100:                                                  # :147-150
+            in0q, in1q = GetPlanarPtsInliners(PtsWithNorm0, PtsWithNorm1, inlierThreshold0, inlierThreshold1, margins)
+            inliers0, inliers1 = np.r_[in0p, in0q], np.r_[in1p, in1q]
+        else:                                                            # :151-153: the planar pairs of iteration 99, both
+            inliers0, inliers1 = in0q, in1q                              # arrays as they were then -- the same (R, T) every time
         if inliers0.shape[0] < 200:                                      # :166-169
             if iIter < 1:
                 isSuccess = False
+            _icp_step(steps, iIter, isSuccess, in0p.shape[0], in0q.shape[0], inlierThreshold0, inlierThreshold1, R_star, T_star,
+                      min(margins), False)
             break
         R, T, _ = SolveRT(inliers0, inliers1)                            # :172
         PC1 = (np.dot(R, PC1.T) + T).T                                   # :175
@@ -225,12 +260,14 @@ def ICP_Pt2PtAndPt2Plane(PC0, PC1, PtsWithNorm0, PtsWithNorm1, maxIterTimes=50, 
         normT = np.linalg.norm(T)
         if trace is not None:
             trace.append((int(in0p.shape[0]), int(in0q.shape[0]), float(inlierThreshold0), float(inlierThreshold1)))
-        if iIter >= minIterTimes:                                        # :185-187
-            if normEulers < ep and normT < ep:
-                break
-        if normEulers < smallShiftThreshold and normT < smallShiftThreshold:   # :190-192
+        converged = iIter >= minIterTimes and normEulers < ep and normT < ep   # :185-187
+        if not converged and normEulers < smallShiftThreshold and normT < smallShiftThreshold:   # :190-192
             inlierThreshold0 *= decay_rate0
             inlierThreshold1 *= decay_rate1
+        _icp_step(steps, iIter + 1, True, in0p.shape[0], in0q.shape[0], inlierThreshold0, inlierThreshold1, R_star, T_star,
+                  min(margins), True)
+        if converged:
+            break
     return R_star, T_star, isSuccess
 
 

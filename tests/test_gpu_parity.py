@@ -1037,9 +1037,10 @@ def test_four_ranks_on_one_gpu(tmp_path):
 
 
 def test_icp_vs_reference_golden(api, orc, models, scans):
-    """caelo.api.ICP (nearest neighbours, inlier selection, SolveRT and the point update on the GPU, the
-    reference's loop control on the host) against MyICP.ICP run by the reference itself: same number of iterations,
-    same inlier counts along the way, pose within tolerance."""
+    """caelo.api.ICP (the whole loop on the device, caelo_icp) against MyICP.ICP run by the reference itself on
+    the extended key points of frames 0 and 1: the first iteration's pair count (through caelo_icp_step), the iteration
+    count and the last iteration's threshold (through Engine.icp), the pose within tolerance.  The pair counts and
+    thresholds of every iteration are held on crafted clouds by tests/test_icp_loop_gpu.py."""
     g = np.load(os.path.join(GOLDEN, "icp_0_1.npz"))
     ext = []
     for f in (0, 1):
@@ -1058,6 +1059,10 @@ def test_icp_vs_reference_golden(api, orc, models, scans):
     assert int(n_in.item()) == int(g["trace_inliers"][0])
     R, T, ok = api.ICP(ext[0], pc1)
     assert ok == bool(g["success"]) and R.dtype == np.float64 and T.shape == (3, 1)
+    info = e.icp_result(e.icp(torch.from_numpy(ext[0]).to(e.device), torch.from_numpy(pc1).to(e.device)))
+    assert info.iterations == int(g["iters"]) == len(g["trace_thr"]) and info.success == 1
+    assert info.iterations < 50 and info.threshold0 == float(g["trace_thr"][-1])   # converged: the last iteration decays nothing
+    assert np.array_equal(np.array(info.R_star).reshape(3, 3), R) and np.array_equal(np.array(info.T_star).reshape(3, 1), T)
     # ICP stops when a step moves less than ep = 1e-3 (degrees / metres), so two runs whose float32 point updates
     # round differently (BLAS sgemm in the reference, explicit mul/add here) agree to a fraction of ep, not to 1e-4 of
     # the ~3 cm correction: the bar is half the stop threshold for T and 1e-4 for the rotation entries

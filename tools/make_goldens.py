@@ -429,6 +429,45 @@ def icp_golden():
     print("  icp golden: %d iterations, %d inliers, ok=%s, T_star=%s" % (iters, inl, ok, np.round(np.asarray(Ts).ravel(), 4)))
 
 
+def icp_loop_golden():
+    """The reference's two loops on the crafted clouds of tests/icp_clouds.py: MyICP.ICP on `points`, `points_102` (102
+    iterations: MyICP.ICP has no branch at iteration 100) and `late_fail` (too few pairs at a late iteration), MyICP.ICP_Pt2PtAndPt2Plane on `planar`, `planar_late_stop` (too few pairs after the first
+    iteration: success, loop ended) and `planar_103` (103 iterations: the branch of MyICP.py:151-153 that fits the planar
+    pairs of iteration 99 again and again).  The oracle is asserted against each; stored are the results, the parameters and
+    the SHA-256 of every input array -- the arrays themselves are rebuilt from their seeds."""
+    import json
+    import MyICP as RefICP
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import icp_clouds
+    g = {"cases": np.array(sorted(icp_clouds.CASES))}
+    for name in sorted(icp_clouds.CASES):
+        loop, kw = icp_clouds.CASES[name][1], icp_clouds.loop_kw(name)
+        arrays = icp_clouds.clouds(name)
+        fn = RefICP.ICP if loop == "icp" else RefICP.ICP_Pt2PtAndPt2Plane
+        (Rs, Ts, ok), log = quiet(fn, *[a.copy() for a in arrays], **kw)
+        oR, oT, ook, steps = icp_clouds.run_oracle(orc, name)
+        iters = int(log.split("ICP iters:")[1].split(",")[0])
+        if loop == "icp":
+            counts = (int(log.split("inliers:")[1].split(",")[0]), 0)
+            thr = (float(log.split("inlierThreshold:")[1]), 0.0)
+        else:
+            counts = (int(log.split("inliers0:")[1].split(",")[0]), int(log.split("inliers1:")[1].split(",")[0]))
+            thr = (float(log.split("th0:")[1].split(",")[0]), float(log.split("th1:")[1]))
+        last = steps[-1]
+        assert ook == ok and len(steps) == iters and (last["n_pts"], last["n_planar"]) == counts, (name, ook, ok, len(steps), iters, last, counts)
+        assert (round(last["thr0"], 5), round(last["thr1"], 5)) == thr, (name, last, thr)
+        assert np.allclose(oR, Rs, atol=1e-7) and np.allclose(oT, Ts, atol=1e-6), "oracle != reference on %s: T %s vs %s" % (name, np.ravel(oT), np.ravel(Ts))
+        margin = min(s["margin"] for s in steps)
+        assert margin >= icp_clouds.GATE_MARGIN, (name, margin)
+        g.update({name + "_R_star": np.asarray(Rs, np.float64), name + "_T_star": np.asarray(Ts, np.float64).reshape(3), name + "_success": bool(ok),
+                  name + "_iters": iters, name + "_moves": last["iterations"], name + "_counts": np.array(counts, np.int32),
+                  name + "_thr": np.array(thr, np.float64), name + "_kw": json.dumps(kw, sort_keys=True),
+                  name + "_sha256": np.array([sha(a) for a in arrays])})
+        print("  icp loop golden %-16s: %3d iterations, pairs %d + %d, ok=%s, margin %.2e, T_star=%s"
+              % (name, iters, counts[0], counts[1], ok, margin, np.round(np.asarray(Ts).ravel(), 4)))
+    np.savez_compressed(os.path.join(GOLD, "icp_loop.npz"), **g)
+
+
 def refine_golden():
     """SURVEY 8f-4, the rest: MyICP.ICP_Pt2PtAndPt2Plane (MyICP.py:127-201) and RefinePoses.RefinementCore
     (RefinePoses.py:273-334, with ForwardUpdatePoses :120-145) run by the reference itself.
@@ -758,6 +797,7 @@ if __name__ == "__main__":
         sys.exit(0)
     if "--icp-only" in sys.argv:
         icp_golden()
+        icp_loop_golden()
         sys.exit(0)
     trunc_golden()
     brute_golden()
@@ -775,6 +815,7 @@ if __name__ == "__main__":
     mat_golden()
     extend_golden()
     icp_golden()
+    icp_loop_golden()
     refine_golden()
     print("done in %.1fs" % (time.time() - t0))
     for f in sorted(os.listdir(GOLD)):
