@@ -93,22 +93,32 @@ def note_ties_left(eng, st):
     return n
 
 
-def read_keras_weights(path):
-    """-> ("respond", [w1,b1,w2,b2]) or ("encoder", [10 arrays]) from a Keras 2.2 .h5 file.  The layer stack is read
-    from the file's ``model_config`` and compared field by field with what the kernels implement (keras_config.check):
-    any other activation / padding / stride / data format / shape is refused."""
+ACTIVATION_CODES = {"tanh": _ffi.ACT_TANH, "relu": _ffi.ACT_RELU, "linear": _ffi.ACT_LINEAR}
+ACTIVATION_NAMES = {v: k for k, v in ACTIVATION_CODES.items()}
+ENCODER_LAYERS = ("conv3d_1", "conv3d_2", "conv3d_3", "dense_1", "dense_2")   # caelo_host_encoder_range's five bounds, in order
+
+
+def _activation_codes(activations):
+    """("relu", "linear") or CAELO_ACT_* integers -> (hidden, code) as CAELO_ACT_* integers; ValueError for anything else."""
+    try:
+        h, c = activations
+        h, c = (ACTIVATION_CODES[a] if isinstance(a, str) else int(a) for a in (h, c))
+    except (KeyError, TypeError, ValueError):
+        raise ValueError("encoder activations: (hidden, code) with hidden in ('tanh', 'relu') and code in ('tanh', 'linear'), got %r" % (activations,))
+    if h not in (_ffi.ACT_TANH, _ffi.ACT_RELU) or c not in (_ffi.ACT_TANH, _ffi.ACT_LINEAR):
+        raise ValueError("encoder activations: (hidden, code) with hidden in ('tanh', 'relu') and code in ('tanh', 'linear'), got %r" % (activations,))
+    return h, c
+
+
+def read_keras_model(path):
+    """-> ("respond", [w1,b1,w2,b2], None) or ("encoder", [10 arrays], (H, C)) from a Keras 2.2 .h5 file: keras_config.read_model."""
     from . import keras_config
-    h = H5File(path)
-    kind = keras_config.check(keras_config.layers(h))
-    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
-    ws = []
-    for ln in names:
-        for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
-            ws.append(np.ascontiguousarray(h.dataset("/model_weights/%s/%s" % (ln, wn.decode())), np.float32))
-    want = [864, 32, 256, 8] if kind == "respond" else [216, 8, 3456, 16, 13824, 32, 409600, 200, 4000, 20]
-    if [w.size for w in ws] != want:
-        raise ValueError("%s: weight shapes %s do not match the %s architecture" % (path, [w.shape for w in ws], kind))
-    return kind, ws
+    return keras_config.read_model(path)
+
+
+def read_keras_weights(path):
+    """-> ("respond", [w1,b1,w2,b2]) or ("encoder", [10 arrays]): read_keras_model without the activations."""
+    return read_keras_model(path)[:2]
 
 
 class VoxelMap:
@@ -650,11 +660,13 @@ class Engine:
         return torch.zeros(shape, dtype=dtype, device=self.device)
 
     def load_weights(self, path):
-        kind, ws = read_keras_weights(path)
+        """A Keras .h5 of either network.  An encoder file always sets ITS activations with its weights: loading the shipped file
+        after a relu model restores tanh / tanh."""
+        kind, ws, activations = read_keras_model(path)
         if kind == "respond":
             self.set_respond_weights(ws)
         else:
-            self.set_encoder_weights(ws)
+            self.set_encoder_weights(ws, activations=activations)
         return kind
 
     @staticmethod
@@ -667,12 +679,39 @@ class Engine:
             raise ValueError("%s weights: %d arrays of shapes %s wanted, got %s" % (what, len(shapes), list(shapes), [w.shape for w in ws]))
         return ws
 
-    def set_encoder_weights(self, ws):
-        """caelo_set_encoder_weights: the ten arrays of the encoder (conv3d_1..3, dense_1, dense_2: kernel, bias each) as float32
-        arrays in Keras layout.  Every derived operand image of the context is rebuilt; work already issued is waited for first."""
+    def set_encoder_weights(self, ws, activations=None):
+        """caelo_set_encoder_weights / caelo_set_encoder_model: the ten arrays of the encoder (conv3d_1..3, dense_1, dense_2: kernel,
+        bias each) as float32 arrays in Keras layout.  ``activations``: (hidden, code), hidden in ("tanh", "relu") for the four hidden
+        layers, code in ("tanh", "linear") for dense_2; None keeps the engine's current pair (tanh / tanh until one is set).  Every
+        derived operand image of the context is rebuilt; work already issued is waited for first.  A relu model whose activations can
+        leave the f16 range of the split operands (encoder_range) is refused with a CaeloError naming the layer; the engine then
+        still holds its previous model."""
         ws = self._weight_arrays(ws, ENCODER_SHAPES, "encoder")
+        codes = None if activations is None else _activation_codes(activations)
         torch.cuda.synchronize(self.device)
-        _ffi.check(self.lib.caelo_set_encoder_weights(self.ctx, *[_hptr(w) for w in ws]))
+        if codes is None:
+            _ffi.check(self.lib.caelo_set_encoder_weights(self.ctx, *[_hptr(w) for w in ws]))
+        else:
+            _ffi.check(self.lib.caelo_set_encoder_model(self.ctx, *([_hptr(w) for w in ws] + [codes[0], codes[1]])))
+
+    def encoder_activations(self):
+        """caelo_get_encoder_activations -> (hidden, code) of the engine's encoder, e.g. ("tanh", "tanh")."""
+        out = (C.c_int32 * 2)()
+        _ffi.check(self.lib.caelo_get_encoder_activations(self.ctx, C.cast(out, C.c_void_p)))
+        return ACTIVATION_NAMES[int(out[0])], ACTIVATION_NAMES[int(out[1])]
+
+    @staticmethod
+    def encoder_range(ws, activations):
+        """caelo_host_encoder_range (host only, no device): -> (bounds [5] f64, over) -- the worst-case magnitude of each layer's
+        output over binary patches (1 behind a tanh layer), and the name of the first layer whose output a kernel splits into f16
+        halves and that can exceed 65504 (conv3d_1..3), or None when the model is in range."""
+        ws = Engine._weight_arrays(ws, ENCODER_SHAPES, "encoder")
+        h, c = _activation_codes(activations)
+        out = (C.c_double * 5)()
+        rc = _ffi.load().caelo_host_encoder_range(*([_hptr(w) for w in ws] + [h, c, C.cast(out, C.c_void_p)]))
+        if rc < 0:
+            _ffi.check(rc)
+        return np.array(out, np.float64), (ENCODER_LAYERS[rc - 1] if rc > 0 else None)
 
     def set_respond_weights(self, ws):
         """caelo_set_respond_weights: conv2d_1 and conv2d_2 of the response layer (kernel, bias each), float32 arrays in Keras layout."""
@@ -734,7 +773,7 @@ class Engine:
 
     def lane_faults(self):
         """caelo_lane_faults: wavefronts of the pose kernels whose lanes disagreed on a hypothesis they all derive from the
-        same inputs, plus descriptors the encoder wrote that are not a finite value within [-1, 1] (self-checks of the two
+        same inputs, plus descriptors the encoder wrote that are not finite or, under a tanh code, not within [-1, 1] (self-checks of the two
         halves; synchronises).  0 on healthy hardware with sane weights."""
         out = C.c_int64(0)
         _ffi.check(self.lib.caelo_lane_faults(self.ctx, C.byref(out)))
@@ -981,7 +1020,9 @@ class Engine:
     def encode_layers(self, bits):
         """Test aid: encode (group 1, every patch) and return the activations the four encoder kernels leave in the
         workspace -- P2 [n,1024] (after pool2), F3 [n,2048] (after conv3), the Dense(200) pre-activations summed over the
-        k slices [n,200] (bias not added) -- and the descriptors [n,20].  Workspace layout: caelo_encode_ws_layout."""
+        k slices [n,200] (bias not added) -- and the descriptors [n,20].  P2, F3 and the descriptors are activated; to the
+        fourth output the caller adds dense_1's bias and applies the model's HIDDEN activation (encoder_activations()[0]: tanh
+        or relu).  Workspace layout: caelo_encode_ws_layout."""
         n = bits.numel() // 64
         out = self.encode(bits, 1)
         ws = self._encode_ws(n)

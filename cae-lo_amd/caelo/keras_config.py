@@ -1,12 +1,18 @@
 """The layer stack recorded in a Keras ``.h5`` (root attribute ``model_config``) -- parsed, never assumed.
 
 The reference obtains its two networks with ``keras.models.load_model(path)`` (Dirs.py:29-30, Match.py:313,324), which
-rebuilds the layers from this JSON.  The HIP kernels implement exactly one architecture per network; ``check`` compares
-every semantic field of every layer (kernel size, strides, padding, dilation, data format, activation, bias, pooling,
-units, input shape) with what the kernels do and refuses anything else, so a different ``.h5`` can never be run
-silently through the wrong arithmetic.
+rebuilds the layers from this JSON.  ``check`` compares every semantic field of every layer (kernel size, strides, padding,
+dilation, data format, activation, bias, pooling, units, input shape) with the stack the shipped files hold and refuses
+anything else, so a different ``.h5`` can never be run silently through the wrong arithmetic.
+
+The encoder kernels implement that one stack with two activation sets (``encoder_model``): a hidden activation H in
+{tanh, relu} on conv3d_1..3 and dense_1 alike, and a code activation C in {tanh, linear} on dense_2.  The shipped
+EncoderModel4VoxelPatch.h5 is (tanh, tanh); the reference's training script (AE4VoxelPatch.py:177-197) builds (relu, linear).
+A file may be the bare encoder or a full autoencoder whose first layers, up to the first Dense(20) behind Flatten, are it.
 """
 import json
+
+import numpy as np
 
 from .h5lite import H5File
 
@@ -28,6 +34,11 @@ ENCODER_SPEC = [
     ("Dense", dict(units=200, activation="tanh", use_bias=True)),
     ("Dense", dict(units=20, activation="tanh", use_bias=True)),
 ]
+
+
+HIDDEN_ACTIVATIONS = ("tanh", "relu")     # conv3d_1, conv3d_2, conv3d_3, dense_1: one of these, the same on all four
+CODE_ACTIVATIONS = ("tanh", "linear")     # dense_2
+_ACTIVATED = [i for i, (c, _) in enumerate(ENCODER_SPEC) if c in ("Conv3D", "Dense")]
 
 
 def _norm(v):
@@ -72,3 +83,71 @@ def check(lys, kind=None):
             if _norm(got) != _norm(val):
                 raise ValueError("unsupported %s: %s(%s).%s = %r, the kernels implement %r" % (kind, cls, cfg.get("name"), key, got, val))
     return kind
+
+
+def encoder_model(lys):
+    """The encoder inside a linear Conv3D stack -> (number of leading layers that are the encoder, (H, C)).
+
+    ``lys`` is a bare encoder (every layer is used) or a full autoencoder: then the prefix up to and including the first
+    ``Dense(20)`` behind ``Flatten`` must be the encoder stack and the rest (the decoder) is ignored.  ValueError, in ``check``'s
+    words, for everything the kernels do not implement: hidden activations that differ from each other, any activation outside
+    ``HIDDEN_ACTIVATIONS`` / ``CODE_ACTIVATIONS``, other kernel sizes, strides, paddings, units."""
+    classes = [c for c, _ in lys]
+    if "Conv3D" not in classes:
+        raise ValueError("not a voxel-patch encoder (layers: %s)" % classes)
+    cut = None
+    if "Flatten" in classes:
+        for i in range(classes.index("Flatten") + 1, len(lys)):
+            if classes[i] == "Dense" and lys[i][1].get("units") == 20:
+                cut = i + 1
+                break
+    want = [c for c, _ in ENCODER_SPEC]
+    if cut is None or classes[:cut] != want:
+        raise ValueError("unsupported encoder layer stack %s (kernels implement %s, alone or followed by a decoder)" % (classes, want))
+    head = lys[:cut]
+    acts = [head[i][1].get("activation") for i in _ACTIVATED]
+    hidden, code = acts[0], acts[-1]
+    for i, a in zip(_ACTIVATED[:-1], acts[:-1]):
+        if a not in HIDDEN_ACTIVATIONS or a != hidden:
+            raise ValueError("unsupported encoder: %s(%s).activation = %r, the kernels implement one of %r on all four hidden layers (%s has %r)"
+                             % (head[i][0], head[i][1].get("name"), a, HIDDEN_ACTIVATIONS, head[_ACTIVATED[0]][1].get("name"), hidden))
+    if code not in CODE_ACTIVATIONS:
+        raise ValueError("unsupported encoder: Dense(%s).activation = %r, the kernels implement one of %r for the code"
+                         % (head[-1][1].get("name"), code, CODE_ACTIVATIONS))
+    for (cls, cfg), (_, spec) in zip(head, ENCODER_SPEC):
+        for key, val in spec.items():
+            if key == "activation":
+                continue
+            got = cfg.get(key, "channels_last" if key == "data_format" else None)
+            if _norm(got) != _norm(val):
+                raise ValueError("unsupported encoder: %s(%s).%s = %r, the kernels implement %r" % (cls, cfg.get("name"), key, got, val))
+    return cut, (hidden, code)
+
+
+def read_model(path):
+    """-> ("respond", [w1,b1,w2,b2], None) or ("encoder", [10 arrays], (H, C)) from a Keras 2.2 .h5 file.  The layer stack is read
+    from the file's ``model_config`` and compared field by field with what the kernels implement: the response layer exactly
+    (``check``), the encoder up to its two activation sets (``encoder_model``; a full autoencoder gives its encoder half, and only
+    those five layers' datasets are read).  Any other activation / padding / stride / data format / shape is refused before a
+    weight is read."""
+    h = H5File(path)
+    lys = layers(h)
+    kind = kind_of(lys)
+    activations, keep = None, None
+    if kind == "respond":
+        check(lys, kind)
+    else:
+        cut, activations = encoder_model(lys)
+        keep = {cfg["name"] for _, cfg in lys[:cut]}
+    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
+    ws = []
+    for ln in names:
+        if keep is not None and ln not in keep:
+            continue
+        for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+            ws.append(np.ascontiguousarray(h.dataset("/model_weights/%s/%s" % (ln, wn.decode())), np.float32))
+    want = [864, 32, 256, 8] if kind == "respond" else [216, 8, 3456, 16, 13824, 32, 409600, 200, 4000, 20]
+    if [w.size for w in ws] != want:
+        raise ValueError("%s: weight shapes %s do not match the %s architecture" % (path, [w.shape for w in ws], kind))
+    return kind, ws, activations
+

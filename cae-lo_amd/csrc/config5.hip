@@ -412,6 +412,7 @@ __global__ void __launch_bounds__(256) k5_conv1pool_x3(const unsigned long long 
 CAELO_API int caelo_patches32(caelo_ctx *c, const caelo_voxmap *m, const float *pts, int pts_ld, int64_t k_max,
                               const int32_t *n_key, uint64_t *bits, void *stream) {
     CAELO_REQUIRE(c && m && pts && bits, "null argument");
+    CAELO_REQUIRE(c->enc_hidden == CAELO_ACT_TANH && c->enc_code == CAELO_ACT_TANH, "the 32^3 path implements the tanh / tanh encoder only");
     CAELO_REQUIRE(k_max > 0 && pts_ld >= 3 && k_max * 3 < (1ll << 31), "bad shape");
     k5_patches<<<(unsigned)(k_max * 3), 256, 0, caelo_stream(stream)>>>(pts, pts_ld, k_max, n_key, m->brick[0], m->brick[1],
                                                                        m->brick[2], (unsigned long long *)bits);
@@ -437,6 +438,7 @@ static int encode32_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, 
                          void *ws, void *stream, hipEvent_t *ev /* 5 events or null */) {
     CAELO_REQUIRE(c && bits && out && ws, "null argument");
     CAELO_REQUIRE(c->has_enc, "encoder weights not set (caelo_set_encoder_weights)");
+    CAELO_REQUIRE(c->enc_hidden == CAELO_ACT_TANH && c->enc_code == CAELO_ACT_TANH, "the 32^3 path implements the tanh / tanh encoder only");
     CAELO_REQUIRE(c->enc32_wd1x, "32^3 dense_1 not set (caelo_set_encoder32_dense)");
     CAELO_REQUIRE(n_patches > 0 && n_patches < (1ll << 27) && group >= 1 && out_stride >= group * 20, "bad shape");
     hipStream_t s = caelo_stream(stream);

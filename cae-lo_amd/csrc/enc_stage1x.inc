@@ -151,7 +151,8 @@ __device__ inline void s1x_item(const caelo_enc_in &in, const S1xItems &it, int 
 // pooled outputs (pool2 + tanh) of a tile pair whose input rows are all background, for pair (xp, yi) = blockIdx.x and every lane of
 // the wavefront that owns it: what the kernel's epilogue would compute from the C0 accumulator starts alone.  Written once per
 // model behind the C0 table; an all-background pair is then one 8-byte load per lane that nothing waits for until the patch is stored.
-__global__ void __launch_bounds__(64) k_enc_bgo_table(float *c0g) {
+template <int H>
+static __device__ __forceinline__ void enc_bgo_table_body(float *c0g) {
     const int lane = threadIdx.x, g = lane >> 4, n = lane & 15;
     const int xp = blockIdx.x >> 2, yi = blockIdx.x & 3;
     f32x4 c[2];
@@ -164,11 +165,14 @@ __global__ void __launch_bounds__(64) k_enc_bgo_table(float *c0g) {
     float v1 = fmaxf(fmaxf(c[0][2], c[0][3]), fmaxf(c[1][2], c[1][3]));
     v0 = fmaxf(v0, __shfl_xor(v0, 16));   // the y pair sits in lane groups g and g ^ 1
     v1 = fmaxf(v1, __shfl_xor(v1, 16));
-    ((float2 *)(c0g + S1X_BGO_OFF))[blockIdx.x * 64 + lane] = make_float2(enc_tanh(v0), enc_tanh(v1));
+    ((float2 *)(c0g + S1X_BGO_OFF))[blockIdx.x * 64 + lane] = make_float2(enc_act<H>(v0), enc_act<H>(v1));
 }
+__global__ void __launch_bounds__(64) k_enc_bgo_table(float *c0g) { enc_bgo_table_body<CAELO_ACT_TANH>(c0g); }
+__global__ void __launch_bounds__(64) k_enc_bgo_table_relu(float *c0g) { enc_bgo_table_body<CAELO_ACT_RELU>(c0g); }
 
-template <bool COUNT>
-__global__ void __launch_bounds__(256, 3) k_enc_stage1x(const caelo_enc_in in, int64_t n_patches, int group, int *__restrict__ work_counter,
+// (the body of k_enc_stage1x and of its relu sibling: H = the hidden activation of conv1 and conv2)
+template <int H, bool COUNT>
+static __device__ __forceinline__ void enc_stage1x_body(const caelo_enc_in &in, int64_t n_patches, int group, int *__restrict__ work_counter,
                                                         const uint4 *__restrict__ w1f, const float *__restrict__ b1g,
                                                         const uint4 *__restrict__ w2x, const float *__restrict__ c0g,
                                                         float *__restrict__ p2out, unsigned long long *__restrict__ mfma_count) {
@@ -375,7 +379,7 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1x(const caelo_enc_in in, i
                     const int cell = rr ? cell1 : cell0;
                     const int yp = ((cell >> 3) & 7) + 1;
                     const int q = ((cell >> 6) * 10 + yp) * 10 + (cell & 7) + 1;
-                    const float dv = enc_tanh(v + b1c) - bgc;
+                    const float dv = enc_act<H>(v + b1c) - bgc;
                     const _Float16 hi = (_Float16)dv;
                     const _Float16 lo = (_Float16)(dv - (float)hi);
                     _Float16 *du = (_Float16 *)&L.d[2 * q];   // units: d_hi x 8 channels, d_lo x 8 channels; swapped in odd padded-y rows
@@ -491,7 +495,7 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1x(const caelo_enc_in in, i
                 const auto s1 = __builtin_amdgcn_permlane16_swap(__float_as_uint(v1), __float_as_uint(v1), false, false);
                 v0 = fmaxf(__uint_as_float(s0[0]), __uint_as_float(s0[1]));
                 v1 = fmaxf(__uint_as_float(s1[0]), __uint_as_float(s1[1]));
-                pout[yi] = make_float2(enc_tanh(v0), enc_tanh(v1));
+                pout[yi] = make_float2(enc_act<H>(v0), enc_act<H>(v1));
             }
         }
         S1X_STAMP(8);
@@ -562,4 +566,15 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1x(const caelo_enc_in in, i
         __syncthreads();
         if (tid == 0) atomicAdd(mfma_count + 16 * (blockIdx.x & 7), (unsigned long long)(unsigned)L.list_n[0]);
     }
+}
+#define ENC_STAGE1X_ARGS const caelo_enc_in in, int64_t n_patches, int group, int *__restrict__ work_counter,                     \
+                         const uint4 *__restrict__ w1f, const float *__restrict__ b1g, const uint4 *__restrict__ w2x,             \
+                         const float *__restrict__ c0g, float *__restrict__ p2out, unsigned long long *__restrict__ mfma_count
+template <bool COUNT>
+__global__ void __launch_bounds__(256, 3) k_enc_stage1x(ENC_STAGE1X_ARGS) {
+    enc_stage1x_body<CAELO_ACT_TANH, COUNT>(in, n_patches, group, work_counter, w1f, b1g, w2x, c0g, p2out, mfma_count);
+}
+template <bool COUNT>
+__global__ void __launch_bounds__(256, 3) k_enc_stage1x_relu(ENC_STAGE1X_ARGS) {
+    enc_stage1x_body<CAELO_ACT_RELU, COUNT>(in, n_patches, group, work_counter, w1f, b1g, w2x, c0g, p2out, mfma_count);
 }

@@ -4,8 +4,10 @@
 // GetFeaturesFromPatches (Match.py:130-135) with the shipped EncoderModel4VoxelPatch.h5:
 //   Conv3D(1->8,3^3,same) tanh -> MaxPool3D(2) -> Conv3D(8->16) tanh -> MaxPool3D(2)
 //   -> Conv3D(16->32) tanh -> Flatten(x,y,z,c) -> Dense(200) tanh -> Dense(20) tanh
-// (Keras channels-last, zero 'same' padding, cross-correlation; the stale relu/linear script
-// AE4VoxelPatch.py:177-197 is NOT what ships).  7.905 MFLOP per patch, 24.28 GFLOP
+// (Keras channels-last, zero 'same' padding, cross-correlation).  The training script AE4VoxelPatch.py:177-197 builds the same stack
+// with relu on the four hidden layers and a linear code: the kernel bodies are templates over the activation, the kernels named
+// below are their tanh instantiation and the _relu / _act siblings serve such a model (caelo_set_encoder_model).
+// 7.905 MFLOP per patch, 24.28 GFLOP
 // per 3072-patch frame: MFMA-bound (157 TFLOP/s f32 matrix peak; conv3 and Dense(200) go through the 16x faster bf16
 // pipe with exact 3-way operand splits, see k_enc_conv3).
 //
@@ -43,6 +45,19 @@ __device__ inline float enc_tanh(float x) {
     const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);  // exp(2x)
     return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
 }
+// The activation of a layer as a template argument (CAELO_ACT_*): the hidden layers' H in {tanh, relu}, the code's C in {tanh,
+// linear}.  relu and the identity are monotone like tanh, so pooling the pre-activations stays exact: relu(max) == max(relu) bit for
+// bit.  relu is fmaxf(x, 0.0f): +0.0 for every negative pre-activation.
+template <int ACT>
+__device__ __forceinline__ float enc_act(float x) {
+    if (ACT == CAELO_ACT_RELU) return fmaxf(x, 0.0f);
+    if (ACT == CAELO_ACT_LINEAR) return x;
+    return enc_tanh(x);
+}
+// the same on the host, for the background vector bg = act(b1) of the C0 table (relu: the bits the device's fmaxf gives)
+static float enc_act_host(int act, float x) {
+    return act == CAELO_ACT_RELU ? fmaxf(x, 0.0f) : (act == CAELO_ACT_LINEAR ? x : tanhf(x));
+}
 
 // ------------------------------------------------------------------------------------------------
 // weights
@@ -60,11 +75,22 @@ static void head_weight_fragments(const float *wd2, float *out);
 
 #define S1X_BGO_OFF (512 * 16 + 16)
 __global__ void k_enc_bgo_table(float *c0g);
+__global__ void k_enc_bgo_table_relu(float *c0g);
 
-CAELO_API int caelo_set_encoder_weights(caelo_ctx *c, const float *w1, const float *b1, const float *w2,
-                                        const float *b2, const float *w3, const float *b3, const float *wd1,
-                                        const float *bd1, const float *wd2, const float *bd2) {
+// Weights and activations together: the range guard first (enc_range.hip; nothing of the context is touched when it refuses), then
+// every derived operand image.  hidden: the activation of conv3d_1..3 and dense_1 (tanh | relu), code: dense_2's (tanh | linear).
+CAELO_API int caelo_set_encoder_model(caelo_ctx *c, const float *w1, const float *b1, const float *w2,
+                                      const float *b2, const float *w3, const float *b3, const float *wd1,
+                                      const float *bd1, const float *wd2, const float *bd2, int hidden, int code) {
     CAELO_REQUIRE(c && w1 && b1 && w2 && b2 && w3 && b3 && wd1 && bd1 && wd2 && bd2, "null argument");
+    CAELO_REQUIRE(hidden == CAELO_ACT_TANH || hidden == CAELO_ACT_RELU, "hidden activation: CAELO_ACT_TANH or CAELO_ACT_RELU");
+    CAELO_REQUIRE(code == CAELO_ACT_TANH || code == CAELO_ACT_LINEAR, "code activation: CAELO_ACT_TANH or CAELO_ACT_LINEAR");
+    {
+        double bound[5];
+        const int rc = caelo_host_encoder_range(w1, b1, w2, b2, w3, b3, wd1, bd1, wd2, bd2, hidden, code, bound);
+        if (rc < 0) return rc;
+        if (rc > 0) return CAELO_ERR_ARG;   // (caelo_last_error names the layer)
+    }
     struct { float **dst; const float *src; size_t n; } plain[] = {
         {&c->enc_w1, w1, 27 * 8}, {&c->enc_b1, b1, 8},   {&c->enc_w2, w2, 27 * 8 * 16}, {&c->enc_b2, b2, 16},
         {&c->enc_w3, w3, 27 * 16 * 32}, {&c->enc_b3, b3, 32}, {&c->enc_wd2, wd2, 200 * 20}, {&c->enc_bd2, bd2, 20}};
@@ -73,10 +99,10 @@ CAELO_API int caelo_set_encoder_weights(caelo_ctx *c, const float *w1, const flo
         CAELO_HIP(hipMemcpy(*p.dst, p.src, p.n * sizeof(float), hipMemcpyHostToDevice));
     }
     {
-        // C0[pos][ch] = b2[ch] + conv2(BG)[pos][ch], BG = tanh(b1) in every valid 8^3 cell, zero padding outside;
+        // C0[pos][ch] = b2[ch] + conv2(BG)[pos][ch], BG = act(b1) in every valid 8^3 cell, zero padding outside;
         // entries 8192..8199 carry bg itself (the kernel subtracts the same float it was built from)
         float c0[512 * 16 + 8], bg[8];
-        for (int ch = 0; ch < 8; ++ch) bg[ch] = tanhf(b1[ch]);
+        for (int ch = 0; ch < 8; ++ch) bg[ch] = enc_act_host(hidden, b1[ch]);
         for (int x = 0; x < 8; ++x) for (int y = 0; y < 8; ++y) for (int z = 0; z < 8; ++z)
             for (int o = 0; o < 16; ++o) {
                 float acc = b2[o];
@@ -89,10 +115,11 @@ CAELO_API int caelo_set_encoder_weights(caelo_ctx *c, const float *w1, const flo
             }
         for (int ch = 0; ch < 8; ++ch) c0[512 * 16 + ch] = bg[ch];
         // + the pooled outputs of a tile pair that sees nothing but background, per pair and lane of k_enc_stage1x (S1X_BGO_OFF floats
-        // in: [16 pairs][64 lanes] float2), computed on the DEVICE with the kernel's own tanh (k_enc_bgo_table)
+        // in: [16 pairs][64 lanes] float2), computed on the DEVICE with the kernel's own activation (k_enc_bgo_table)
         if (!c->enc_c0) CAELO_HIP(hipMalloc(&c->enc_c0, (S1X_BGO_OFF + 16 * 64 * 2) * sizeof(float)));
         CAELO_HIP(hipMemcpy(c->enc_c0, c0, sizeof(c0), hipMemcpyHostToDevice));
-        k_enc_bgo_table<<<16, 64>>>(c->enc_c0);
+        if (hidden == CAELO_ACT_RELU) k_enc_bgo_table_relu<<<16, 64>>>(c->enc_c0);
+        else k_enc_bgo_table<<<16, 64>>>(c->enc_c0);
         CAELO_LAUNCH_CHECK();
         CAELO_HIP(hipDeviceSynchronize());
     }
@@ -127,6 +154,23 @@ CAELO_API int caelo_set_encoder_weights(caelo_ctx *c, const float *w1, const flo
         CAELO_HIP(hipMemcpy(c->enc_wd2q, wq, n * sizeof(float), hipMemcpyHostToDevice));
     }
     c->has_enc = true;
+    c->enc_hidden = hidden;
+    c->enc_code = code;
+    return CAELO_OK;
+}
+
+// these weights with the context's current activations (tanh / tanh until caelo_set_encoder_model says otherwise)
+CAELO_API int caelo_set_encoder_weights(caelo_ctx *c, const float *w1, const float *b1, const float *w2,
+                                        const float *b2, const float *w3, const float *b3, const float *wd1,
+                                        const float *bd1, const float *wd2, const float *bd2) {
+    CAELO_REQUIRE(c, "null argument");
+    return caelo_set_encoder_model(c, w1, b1, w2, b2, w3, b3, wd1, bd1, wd2, bd2, c->enc_hidden, c->enc_code);
+}
+
+CAELO_API int caelo_get_encoder_activations(caelo_ctx *c, int32_t out[2]) {
+    CAELO_REQUIRE(c && out, "null argument");
+    out[0] = c->enc_hidden;
+    out[1] = c->enc_code;
     return CAELO_OK;
 }
 
@@ -257,11 +301,13 @@ __device__ inline void enc_item(const caelo_enc_in &in, int J, int nk, int group
     }
 }
 
-__global__ void __launch_bounds__(256, 3) k_enc_stage1(const caelo_enc_in in, int64_t n_patches,
-                                                    int group, int *__restrict__ work_counter,
-                                                    const float *__restrict__ w1g, const float *__restrict__ b1g,
-                                                    const float *__restrict__ w2g, const float *__restrict__ c0g,
-                                                    float *__restrict__ p2out) {
+// (the body of k_enc_stage1 and of its relu sibling: H = the hidden activation)
+template <int H>
+static __device__ __forceinline__ void enc_stage1_body(const caelo_enc_in &in, int64_t n_patches,
+                                                       int group, int *__restrict__ work_counter,
+                                                       const float *__restrict__ w1g, const float *__restrict__ b1g,
+                                                       const float *__restrict__ w2g, const float *__restrict__ c0g,
+                                                       float *__restrict__ p2out) {
     __shared__ __attribute__((aligned(16))) Stage1Lds L;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -296,7 +342,7 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1(const caelo_enc_in in, in
         float v1 = fmaxf(fmaxf(c0r[yi][0][2], c0r[yi][0][3]), fmaxf(c0r[yi][1][2], c0r[yi][1][3]));
         v0 = fmaxf(v0, __shfl_xor(v0, 32));
         v1 = fmaxf(v1, __shfl_xor(v1, 32));
-        if (lane < 32) L.bgout[wave][yi][lane] = make_float2(enc_tanh(v0), enc_tanh(v1));
+        if (lane < 32) L.bgout[wave][yi][lane] = make_float2(enc_act<H>(v0), enc_act<H>(v1));
     }
     for (int i = tid; i < 27 * 8; i += 256) L.w1[i] = w1g[i];
     if (tid < 8) { L.b1[tid] = b1g[tid]; L.bg[tid] = c0g[512 * 16 + tid]; }  // bg = tanh(b1), from the host table
@@ -431,7 +477,7 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1(const caelo_enc_in in, in
                 for (int c = 1; c < 8; ++c) mine = (sub == c) ? acc[c] : mine;
                 const int px = cell >> 6, py = (cell >> 3) & 7, pz = cell & 7;
                 const int q = ((px + 1) * 10 + (py + 1)) * 10 + pz + 1;
-                L.p1[(sub >> 2) * S1P_PLANE + q * 4 + (sub & 3)] = enc_tanh(mine) - L.bg[sub];
+                L.p1[(sub >> 2) * S1P_PLANE + q * 4 + (sub & 3)] = enc_act<H>(mine) - L.bg[sub];
             }
         }
         if (tid == 0) L.next_j = (int)gridDim.x + j_fetch;
@@ -485,8 +531,8 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1(const caelo_enc_in in, in
                 v0 = fmaxf(v0, __shfl_xor(v0, 32));
                 v1 = fmaxf(v1, __shfl_xor(v1, 32));
                 if (g < 2) {
-                    dst[0] = enc_tanh(v0);
-                    dst[16] = enc_tanh(v1);
+                    dst[0] = enc_act<H>(v0);
+                    dst[16] = enc_act<H>(v1);
                 }
             }
         }
@@ -518,6 +564,15 @@ __global__ void __launch_bounds__(256, 3) k_enc_stage1(const caelo_enc_in in, in
     if (threadIdx.x == 0)
         for (int i = 0; i < 8; ++i) atomicAdd(&g_enc_stamp[i], (unsigned long long)L.prof[i]);
 #endif
+}
+#define ENC_STAGE1_ARGS const caelo_enc_in in, int64_t n_patches, int group, int *__restrict__ work_counter,                      \
+                        const float *__restrict__ w1g, const float *__restrict__ b1g, const float *__restrict__ w2g,              \
+                        const float *__restrict__ c0g, float *__restrict__ p2out
+__global__ void __launch_bounds__(256, 3) k_enc_stage1(ENC_STAGE1_ARGS) {
+    enc_stage1_body<CAELO_ACT_TANH>(in, n_patches, group, work_counter, w1g, b1g, w2g, c0g, p2out);
+}
+__global__ void __launch_bounds__(256, 3) k_enc_stage1_relu(ENC_STAGE1_ARGS) {
+    enc_stage1_body<CAELO_ACT_RELU>(in, n_patches, group, work_counter, w1g, b1g, w2g, c0g, p2out);
 }
 
 #include "enc_stage1x.inc"
@@ -627,7 +682,8 @@ static void conv3_split_weights(const float *w3, uint4 *out) {
 #ifndef C3X_WGS
 #define C3X_WGS 2   // workgroups per CU the register budget is set for (3 spill at 168 registers: 183 instead of 92 us per 8 frames)
 #endif
-__global__ void __launch_bounds__(256, C3X_WGS) k_enc_conv3(const float *__restrict__ p2, int64_t n_patches, const caelo_enc_in in,
+template <int H>
+static __device__ __forceinline__ void enc_conv3_body(const float *__restrict__ p2, int64_t n_patches, const caelo_enc_in &in,
                                                       const uint4 *__restrict__ w3x, const float *__restrict__ b3g,
                                                       float *__restrict__ f3, int *__restrict__ stage1_counter,
                                                       int *__restrict__ xcd_counters) {
@@ -785,7 +841,7 @@ __global__ void __launch_bounds__(256, C3X_WGS) k_enc_conv3(const float *__restr
 #pragma unroll
                 for (int j = 0; j < 2; ++j)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) dst[(((2 * round + j) * 4 + g) * 4 + r) * 32] = enc_tanh(acc[j][r]);
+                    for (int r = 0; r < 4; ++r) dst[(((2 * round + j) * 4 + g) * 4 + r) * 32] = enc_act<H>(acc[j][r]);
             }
         }
         C3_STAMP(2);
@@ -797,6 +853,15 @@ __global__ void __launch_bounds__(256, C3X_WGS) k_enc_conv3(const float *__restr
         atomicAdd(&g_enc_stamp[12], 1ull);
     }
 #endif
+}
+#define ENC_CONV3_ARGS const float *__restrict__ p2, int64_t n_patches, const caelo_enc_in in, const uint4 *__restrict__ w3x,     \
+                       const float *__restrict__ b3g, float *__restrict__ f3, int *__restrict__ stage1_counter,                   \
+                       int *__restrict__ xcd_counters
+__global__ void __launch_bounds__(256, C3X_WGS) k_enc_conv3(ENC_CONV3_ARGS) {
+    enc_conv3_body<CAELO_ACT_TANH>(p2, n_patches, in, w3x, b3g, f3, stage1_counter, xcd_counters);
+}
+__global__ void __launch_bounds__(256, C3X_WGS) k_enc_conv3_relu(ENC_CONV3_ARGS) {
+    enc_conv3_body<CAELO_ACT_RELU>(p2, n_patches, in, w3x, b3g, f3, stage1_counter, xcd_counters);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1155,11 +1220,12 @@ static void head_weight_fragments(const float *wd2, float *out) {
                 }
 }
 
-template <int SPLIT>
-__global__ void __launch_bounds__(256) k_enc_head_mfma(const float *__restrict__ part, int64_t n_patches, int64_t n_rows_pad,
-                                                       const float *__restrict__ bd1p, const float4 *__restrict__ wd2q,
-                                                       const float *__restrict__ bd2, int group, caelo_enc_out outs,
-                                                       int out_stride, const caelo_enc_in in, int32_t *faults) {
+// H: dense_1's activation, C: dense_2's.  The self-check on the way out follows C: a tanh code lies within [-1, 1], a linear code is finite.
+template <int SPLIT, int H, int C>
+static __device__ __forceinline__ void enc_head_body(const float *__restrict__ part, int64_t n_patches, int64_t n_rows_pad,
+                                                     const float *__restrict__ bd1p, const float4 *__restrict__ wd2q,
+                                                     const float *__restrict__ bd2, int group, const caelo_enc_out &outs,
+                                                     int out_stride, const caelo_enc_in &in, int32_t *faults) {
     __shared__ f32x4 s_c[3][2][64];   // partial products of wavefronts 1 .. 3
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int m = lane & 15, g = lane >> 4;
@@ -1203,7 +1269,7 @@ __global__ void __launch_bounds__(256) k_enc_head_mfma(const float *__restrict__
             float4 sum = b1[c];
 #pragma unroll
             for (int sp = 0; sp < SPLIT; ++sp) { sum.x += v[c][sp].x; sum.y += v[c][sp].y; sum.z += v[c][sp].z; sum.w += v[c][sp].w; }
-            const float hv[4] = {enc_tanh(sum.x), enc_tanh(sum.y), enc_tanh(sum.z), enc_tanh(sum.w)};
+            const float hv[4] = {enc_act<H>(sum.x), enc_act<H>(sum.y), enc_act<H>(sum.z), enc_act<H>(sum.w)};
             const float w0[4] = {wq[c][0].x, wq[c][0].y, wq[c][0].z, wq[c][0].w}, w1[4] = {wq[c][1].x, wq[c][1].y, wq[c][1].z, wq[c][1].w};
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1225,6 +1291,7 @@ __global__ void __launch_bounds__(256) k_enc_head_mfma(const float *__restrict__
         acc1 += s_c[w][1][lane];
     }
     const float bo0 = bd2[m], bo1 = m < 4 ? bd2[16 + m] : 0.0f;   // output bias of this lane's two C columns
+    constexpr float lim = C == CAELO_ACT_TANH ? 1.0f : 3.402823466e+38f;   // (NaN and inf fail `<= lim` either way)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const unsigned pp = tile * 16u + 4u * (unsigned)g + (unsigned)i;
@@ -1233,16 +1300,27 @@ __global__ void __launch_bounds__(256) k_enc_head_mfma(const float *__restrict__
             const unsigned f = pp / per_out, q = pp - f * per_out, kp = q / (unsigned)group;
             float *dst = outs.base[f] + (size_t)kp * out_stride + (size_t)(q - kp * (unsigned)group) * 20;
             // the encoder's own invariant (see k_enc_head): a descriptor is a tanh -- finite and within [-1, 1]; counted per value
-            const float d0 = enc_tanh(bo0 + acc0[i]);
+            const float d0 = enc_act<C>(bo0 + acc0[i]);
             dst[m] = d0;
-            if (!(fabsf(d0) <= 1.0f)) atomicAdd(faults, 1);
+            if (!(fabsf(d0) <= lim)) atomicAdd(faults, 1);
             if (m < 4) {
-                const float d1 = enc_tanh(bo1 + acc1[i]);
+                const float d1 = enc_act<C>(bo1 + acc1[i]);
                 dst[16 + m] = d1;
-                if (!(fabsf(d1) <= 1.0f)) atomicAdd(faults, 1);
+                if (!(fabsf(d1) <= lim)) atomicAdd(faults, 1);
             }
         }
     }
+}
+#define ENC_HEAD_ARGS const float *__restrict__ part, int64_t n_patches, int64_t n_rows_pad, const float *__restrict__ bd1p,      \
+                      const float4 *__restrict__ wd2q, const float *__restrict__ bd2, int group, caelo_enc_out outs,             \
+                      int out_stride, const caelo_enc_in in, int32_t *faults
+template <int SPLIT>
+__global__ void __launch_bounds__(256) k_enc_head_mfma(ENC_HEAD_ARGS) {
+    enc_head_body<SPLIT, CAELO_ACT_TANH, CAELO_ACT_TANH>(part, n_patches, n_rows_pad, bd1p, wd2q, bd2, group, outs, out_stride, in, faults);
+}
+template <int SPLIT, int H, int C>   // the three other (hidden, code) pairs
+__global__ void __launch_bounds__(256) k_enc_head_mfma_act(ENC_HEAD_ARGS) {
+    enc_head_body<SPLIT, H, C>(part, n_patches, n_rows_pad, bd1p, wd2q, bd2, group, outs, out_stride, in, faults);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1309,6 +1387,7 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
     // with -- one wavefront per patch, conv1 / conv2 as two kernels, the two-barrier Dense(200), the one-patch-per-wavefront head, the
     // VALU response layer, the all-f64 match as a default -- are gone from the library; DESIGN.md 4 keeps their numbers.)
     const bool stage1x = !c->enc_reference;
+    const bool relu = c->enc_hidden == CAELO_ACT_RELU;   // the relu siblings have their tanh kernels' registers, LDS and occupancy
     static int slots1x_slot[CAELO_MAX_DEVICES];
     static bool slots1x_have[CAELO_MAX_DEVICES];
     static std::mutex slots1x_mu;
@@ -1353,22 +1432,31 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
         if (ev) {   // profiling calls count the MFMAs the kernel executes (bench.py's roofline); same code otherwise
             CAELO_HIP(hipMemsetAsync(mfma_count, 0, 1024, s));
             CAELO_HIP(hipEventRecord(ev[0], s));
-            k_enc_stage1x<true><<<gx, 256, 0, s>>>(ein, n_patches, order_group, work_counter, (const uint4 *)c->enc_w1f, c->enc_b1,
-                                                   (const uint4 *)c->enc_w2x, c->enc_c0, p2, mfma_count);
-        } else
+            if (relu)
+                k_enc_stage1x_relu<true><<<gx, 256, 0, s>>>(ein, n_patches, order_group, work_counter, (const uint4 *)c->enc_w1f, c->enc_b1,
+                                                            (const uint4 *)c->enc_w2x, c->enc_c0, p2, mfma_count);
+            else
+                k_enc_stage1x<true><<<gx, 256, 0, s>>>(ein, n_patches, order_group, work_counter, (const uint4 *)c->enc_w1f, c->enc_b1,
+                                                       (const uint4 *)c->enc_w2x, c->enc_c0, p2, mfma_count);
+        } else if (relu)
+            k_enc_stage1x_relu<false><<<gx, 256, 0, s>>>(ein, n_patches, order_group, work_counter, (const uint4 *)c->enc_w1f, c->enc_b1,
+                                                         (const uint4 *)c->enc_w2x, c->enc_c0, p2, mfma_count);
+        else
             k_enc_stage1x<false><<<gx, 256, 0, s>>>(ein, n_patches, order_group, work_counter, (const uint4 *)c->enc_w1f, c->enc_b1,
                                                     (const uint4 *)c->enc_w2x, c->enc_c0, p2, mfma_count);
         CAELO_LAUNCH_CHECK();
     } else {
         if (ev) CAELO_HIP(hipMemsetAsync(mfma_count, 0, 1024, s));   // (the f32 kernel has no register left to count)
-        k_enc_stage1<<<g1, 256, 0, s>>>(ein, n_patches, order_group, work_counter, c->enc_w1, c->enc_b1, c->enc_w2, c->enc_c0, p2);
+        if (relu) k_enc_stage1_relu<<<g1, 256, 0, s>>>(ein, n_patches, order_group, work_counter, c->enc_w1, c->enc_b1, c->enc_w2, c->enc_c0, p2);
+        else k_enc_stage1<<<g1, 256, 0, s>>>(ein, n_patches, order_group, work_counter, c->enc_w1, c->enc_b1, c->enc_w2, c->enc_c0, p2);
         CAELO_LAUNCH_CHECK();
     }
     if (ev) CAELO_HIP(hipEventRecord(ev[1], s));
     const int64_t pairs = (n_patches + 1) / 2;
     const int64_t cap3 = ((ein.yield & 2) ? 256 : ((ein.yield & 4) ? 384 : 512)) * C3X_WGS / 2;
     const unsigned g3 = (unsigned)(pairs < cap3 ? pairs : cap3);  // persistent: two 4-wave workgroups per CU
-    k_enc_conv3<<<g3, 256, 0, s>>>(p2, n_patches, ein, (const uint4 *)c->enc_w3x, c->enc_b3, f3, work_counter, xcd_counters);
+    if (relu) k_enc_conv3_relu<<<g3, 256, 0, s>>>(p2, n_patches, ein, (const uint4 *)c->enc_w3x, c->enc_b3, f3, work_counter, xcd_counters);
+    else k_enc_conv3<<<g3, 256, 0, s>>>(p2, n_patches, ein, (const uint4 *)c->enc_w3x, c->enc_b3, f3, work_counter, xcd_counters);
     CAELO_LAUNCH_CHECK();
     if (ev) CAELO_HIP(hipEventRecord(ev[2], s));
     {
@@ -1376,8 +1464,17 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
         if (rc) return rc;
     }
     if (ev) CAELO_HIP(hipEventRecord(ev[3], s));
-    k_enc_head_mfma<D1_SPLIT_OF(DENSE_K)><<<(unsigned)((n_patches + 15) / 16), 256, 0, s>>>(part, n_patches, np, c->enc_bd1, (const float4 *)c->enc_wd2q,
-                                                                                       c->enc_bd2, group, outs, out_stride, ein, c->faults);
+    {
+        constexpr int SP = D1_SPLIT_OF(DENSE_K);
+        const dim3 gh((unsigned)((n_patches + 15) / 16));
+#define ENC_HEAD_LAUNCH(K) K<<<gh, 256, 0, s>>>(part, n_patches, np, c->enc_bd1, (const float4 *)c->enc_wd2q, c->enc_bd2, group, outs, out_stride, ein, c->faults)
+        const bool linear = c->enc_code == CAELO_ACT_LINEAR;
+        if (relu && linear) ENC_HEAD_LAUNCH((k_enc_head_mfma_act<SP, CAELO_ACT_RELU, CAELO_ACT_LINEAR>));
+        else if (relu) ENC_HEAD_LAUNCH((k_enc_head_mfma_act<SP, CAELO_ACT_RELU, CAELO_ACT_TANH>));
+        else if (linear) ENC_HEAD_LAUNCH((k_enc_head_mfma_act<SP, CAELO_ACT_TANH, CAELO_ACT_LINEAR>));
+        else ENC_HEAD_LAUNCH(k_enc_head_mfma<SP>);
+#undef ENC_HEAD_LAUNCH
+    }
     CAELO_LAUNCH_CHECK();
     if (ev) CAELO_HIP(hipEventRecord(ev[4], s));
     return CAELO_OK;

@@ -33,7 +33,7 @@ from caelo import _ffi, framesteps, stageio, synth  # noqa: E402
 import caelo  # noqa: E402
 caelo.configure_runtime()  # this script owns its process: before HIP starts (the queue count is left to the caller)
 from caelo import dist as cdist  # noqa: E402
-from caelo.engine import Engine, FrameBatch, FrameFeatures, note_ties_left, raise_status, ransac_draws  # noqa: E402
+from caelo.engine import ENCODER_H5, RESPOND_H5, Engine, FrameBatch, FrameFeatures, note_ties_left, raise_status, ransac_draws  # noqa: E402
 
 
 def _host_times(host_times):
@@ -459,12 +459,28 @@ def main():
                          "--frame-step s reads the multiples only.)  --matchability M gets the same prefix per step.  With --gpus > 1 a rank "
                          "registers the step pairs whose frame 0 it owns: its halo is the next rank's first max(S) frames' rows (one more "
                          "all-gather), and every rank needs at least max(S) frames")
+    ap.add_argument("--encoder-h5", metavar="PATH", help="the patch encoder's Keras .h5 instead of the shipped EncoderModel4VoxelPatch.h5: a bare "
+                    "encoder or a full autoencoder (its encoder half is taken), tanh or relu hidden layers, tanh or linear code -- "
+                    "e.g. what the reference's AE4VoxelPatch.py trains.  Every rank loads it")
+    ap.add_argument("--respond-h5", metavar="PATH", help="the response layer's Keras .h5 instead of the shipped SphericalRingPCRespondLayer.h5")
     ap.add_argument("--gpus", type=int, default=int(os.environ.get("WORLD_SIZE", "1")),
                     help="ranks = GPUs; without a launcher the script starts them itself (caelo.dist.ensure_ranks)")
     args = ap.parse_args()
+    # the model files are parsed (layer stack, activations, shapes) before any device work; the engines load them below
+    for opt, path, kind in (("--encoder-h5", args.encoder_h5, "encoder"), ("--respond-h5", args.respond_h5, "respond")):
+        if path:
+            from caelo import keras_config
+            try:
+                got = keras_config.read_model(path)[0]
+            except (OSError, KeyError, ValueError) as e:
+                ap.error("%s %s: %s" % (opt, path, e))
+            if got != kind:
+                ap.error("%s %s holds the %s network" % (opt, path, "response" if got == "respond" else "encoder"))
     if args.desc_dir or args.desc_dim is not None:
         if not args.desc_dir:
             ap.error("--desc-dim goes with --desc-dir")
+        if args.encoder_h5 or args.respond_h5:
+            ap.error("--desc-dir reads descriptors from files: no network runs, --encoder-h5 / --respond-h5 do not go with it")
         try:
             return main_desc(args, ap, framesteps.parse_steps(args.frame_steps))
         except ValueError as e:
@@ -507,7 +523,7 @@ def main():
     backend = os.environ.get("CAELO_DIST_BACKEND", "nccl")   # gloo: several ranks on one GPU (functional tests)
     local_rank %= torch.cuda.device_count()
     torch.cuda.set_device(local_rank)
-    eng = Engine(device=local_rank)
+    eng = Engine(respond_h5=args.respond_h5 or RESPOND_H5, encoder_h5=args.encoder_h5 or ENCODER_H5, device=local_rank)
     if world > 1:
         dist.init_process_group(backend=backend, **({"device_id": torch.device("cuda", local_rank)} if backend == "nccl" else {}))
     if args.scans:

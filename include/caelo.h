@@ -119,6 +119,31 @@ int caelo_set_encoder_weights(caelo_ctx *ctx, const float *w1_host /*[27][1][8]*
                               const float *w3_host /*[27][16][32]*/, const float *b3_host,
                               const float *wd1_host /*[2048][200]*/, const float *bd1_host,
                               const float *wd2_host /*[200][20]*/, const float *bd2_host);
+/* The encoder's activations.  The reference produces two sets: the shipped EncoderModel4VoxelPatch.h5 is tanh on all five layers,
+ * its training script (AE4VoxelPatch.py:177-197) builds relu on the four hidden layers and a linear 20-d code.  hidden in
+ * {CAELO_ACT_TANH, CAELO_ACT_RELU} is applied to conv3d_1..3 and dense_1 alike, code in {CAELO_ACT_TANH, CAELO_ACT_LINEAR} to dense_2;
+ * anything else is CAELO_ERR_ARG.  A context starts as tanh / tanh.
+ * caelo_set_encoder_model: weights and activations together; every derived operand image is rebuilt.  Refused (CAELO_ERR_ARG, the
+ *   layer named in caelo_last_error, the context unchanged) when caelo_host_encoder_range finds a tensor the kernels split into f16
+ *   halves that can leave the f16 range.
+ * caelo_set_encoder_weights: these weights with the context's CURRENT activations.
+ * caelo_host_encoder_range (host only, no device): worst-case magnitude of each layer's output in float64 over binary patches,
+ *   kept per channel: b_1[c] = sum |w1[.][c]| + |b1[c]|, b_l[c] = sum_k |w_l[k][c]| b_(l-1)[channel of k] + |b_l[c]|, 1 behind a tanh layer;
+ *   out[l-1] = max_c b_l[c].  Returns 0 when
+ *   every split tensor fits (a tanh hidden stack always does), the 1-based number of the first layer whose output can exceed
+ *   65504 where a kernel splits it -- layers 1..3 feed conv2, conv3 and Dense(200) as f16 halves; the hidden vector and the code
+ *   stay f32 -- or CAELO_ERR_ARG.  The 32^3 entry points (caelo_patches32, caelo_encode32*) are tanh / tanh only and refuse any
+ *   other model before launching. */
+#define CAELO_ACT_TANH 0
+#define CAELO_ACT_RELU 1
+#define CAELO_ACT_LINEAR 2
+int caelo_set_encoder_model(caelo_ctx *ctx, const float *w1_host, const float *b1_host, const float *w2_host, const float *b2_host,
+                            const float *w3_host, const float *b3_host, const float *wd1_host, const float *bd1_host,
+                            const float *wd2_host, const float *bd2_host, int hidden, int code);
+int caelo_get_encoder_activations(caelo_ctx *ctx, int32_t out[2] /* hidden, code */);
+int caelo_host_encoder_range(const float *w1_host, const float *b1_host, const float *w2_host, const float *b2_host,
+                             const float *w3_host, const float *b3_host, const float *wd1_host, const float *bd1_host,
+                             const float *wd2_host, const float *bd2_host, int hidden, int code, double out_host[5]);
 /* on != 0: this context's encoder runs conv1 / conv2 with the exact-f32 kernel of round 2 instead of the default (f32 products
  * from 2-way f16 splits on the f16 matrix pipe) -- the precision reference of the tests and of tools/enc_layer_errors.py; slower.
  * An explicit, per-context choice: the library reads NO environment variable that changes arithmetic (no reference counterpart:

@@ -6,7 +6,12 @@ f32-input stage 1 for comparison.  The budget table of tests/test_gpu_parity.py:
 
 `--family NAME` (repeatable; `--family all`): the same layers under one of the seeded weight families of tests/netref64.py, judged
 against the FLOAT64 network instead of the oracle, for both stage-1 kernels, on the 70 edge patches of the family tests plus every
-sixth patch of the golden frame.  FAMILY_BUDGET of tests/test_weight_families_gpu.py is 3 x the larger of the two kernels' lines."""
+sixth patch of the golden frame.  FAMILY_BUDGET of tests/test_weight_families_gpu.py is 3 x the larger of the two kernels' lines.
+
+`--activations`: the models of tests/test_encoder_activations_gpu.py (tests/netref64_act.py MODELS: the trained relu / linear fixture
+and seeded families under relu / linear, relu / tanh and tanh / linear) on that test's 582 patches, for both stage-1 kernels, against
+the FLOAT64 network -- and, first, what the plain float32 NumPy restatement costs on the same patches: the test's per-layer bars are
+4 x those lines, its descriptor bar is 1e-4 relative.  profiles/enc_layer_errors_activations.txt is this output."""
 import argparse, os, sys
 import numpy as np
 import torch
@@ -18,18 +23,46 @@ from caelo.engine import Engine
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--family", action="append", default=[])
+ap.add_argument("--activations", action="store_true")
 args = ap.parse_args()
 eng = Engine(device=0)
 golden_bits = np.ascontiguousarray(np.load(os.path.join(REPO, "tests", "golden", "frame_q0.npz"))["patch_bits"].reshape(-1, 64))
 
 
-def report(layers, bd1, ref):
-    p2, f3, pre, out = (x.cpu().numpy() for x in layers)
-    h = np.tanh(pre.astype(np.float64) + np.asarray(bd1, np.float64))
-    for name, a, b in (("P2", p2, ref[0]), ("F3", f3, ref[1]), ("tanh(Dense(200))", h, ref[2]), ("descriptors", out, ref[3])):
+def report(layers, bd1, ref, hidden=np.tanh, hidden_name="tanh"):
+    p2, f3, pre, out = (x.cpu().numpy() if hasattr(x, "cpu") else x for x in layers)
+    h = hidden(pre.astype(np.float64) + np.asarray(bd1, np.float64)) if bd1 is not None else pre
+    for name, a, b in (("P2", p2, ref[0]), ("F3", f3, ref[1]), ("%s(Dense(200))" % hidden_name, h, ref[2]), ("descriptors", out, ref[3])):
         d = np.abs(a.astype(np.float64) - b)
         print("%-18s max abs %.3e   mean abs %.3e   element-wise rel (floor 0.1) %.3e" % (name, d.max(), d.mean(), (d / np.maximum(np.abs(b), 0.1)).max()))
 
+
+if args.activations:
+    import tempfile
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import netref64_act as na
+    bits = na.test_patches()
+    t = torch.from_numpy(bits.view(np.int64)).to(eng.device)
+    with tempfile.TemporaryDirectory() as tmp:
+        for name, _, _ in na.MODELS:
+            ws, acts = na.model(name, tmp)
+            ref, _ = na.encoder_layers(ws, bits, acts)
+            f32, _ = na.encoder_layers(ws, bits, acts, np.float32)
+            bounds = na.range_bounds(ws, acts)
+            print("model %s, hidden %s, code %s, %d patches; range bounds %s" % (name, acts[0], acts[1], len(bits), " ".join("%.4g" % b for b in bounds)))
+            print("  plain float32 NumPy restatement, against float64")
+            report(f32, None, ref, hidden_name=acts[0])
+            eng.set_encoder_weights(ws, activations=acts)
+            for reference in (False, True):
+                eng.set_encoder_reference(reference)
+                layers = eng.encode_layers(t)
+                torch.cuda.synchronize()
+                print("  stage 1 = %s, against float64" % ("k_enc_stage1 (f32)" if reference else "k_enc_stage1x"))
+                report(layers, ws[7], ref, na.ACTS[acts[0]], acts[0])
+                sys.stdout.flush()
+            eng.set_encoder_reference(False)
+    print("lane_faults %d" % eng.lane_faults())
+    sys.exit(0)
 
 if args.family:
     sys.path.insert(0, os.path.join(REPO, "tests"))
