@@ -51,6 +51,7 @@ ST_BAD_KEYPTS = 128   # status bit of EXTRACT_GIVEN_KEYPTS: K outside [1, 1024],
 GIVEN_KEYPTS_RANGE = 16384.0   # metres, include/caelo.h CAELO_GIVEN_KEYPTS_RANGE
 EXTRACT_CORRECT_PC = 32   # the scan is rotated by the context's calibration angle first (caelo_set_calib_angle; CorrectPC)
 ABI_VERSION = 6   # include/caelo.h CAELO_ABI_VERSION
+ACT_SIGMOID = 3   # include/caelo.h CAELO_ACT_SIGMOID: the decoder's output activation (caelo_set_decoder_model)
 ACT_TANH, ACT_RELU, ACT_LINEAR = 0, 1, 2   # include/caelo.h CAELO_ACT_*: the encoder's activations (caelo_set_encoder_model)
 KP_NN_MAX_K, KP_NN_MAX_THRESHOLDS = 65536, 16   # include/caelo.h CAELO_KP_NN_MAX_K / CAELO_KP_NN_MAX_THRESHOLDS (caelo_kp_nn_pairs)
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
@@ -84,6 +85,12 @@ SIGNATURES = [
     ("caelo_get_encoder_activations", c_int, [c_vp, c_vp]),
     ("caelo_host_encoder_range", c_int, [c_vp] * 10 + [c_int, c_int, c_vp]),
     ("caelo_set_encoder_reference", c_int, [c_vp, c_int]),
+    ("caelo_set_decoder_model", c_int, [c_vp] + [c_vp] * 10 + [c_int, c_int]),
+    ("caelo_get_decoder_activations", c_int, [c_vp, c_vp]),
+    ("caelo_host_decoder_fold", c_int, [c_vp, c_int, c_int, c_vp]),
+    ("caelo_decode_ws_bytes", c_i64, [c_i64]),
+    ("caelo_decode_ws_layout", c_int, [c_i64, c_vp]),
+    ("caelo_decode", c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_correct_pc", c_int, [c_vp, c_vp, c_i64, c_int, C.c_double, c_vp, c_vp]),
     ("caelo_set_calib_angle", c_int, [c_vp, C.c_double]),
     ("caelo_get_calib_angle", C.c_double, [c_vp]),

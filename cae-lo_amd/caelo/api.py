@@ -13,6 +13,7 @@ tuples / dtypes, served by the HIP engine.
     Match.SolveRT / RANSAC4RT             :138/:162
     Match.SolveRelativePose               :241  SolveRelativePose(PC0, F0, W0, PC1, F1, W1)
     keras.models.load_model (Match.py:313,324)  load_model(h5_path) -> object with .predict
+    autoencoder.predict   (AE4VoxelPatch.py:256) load_autoencoder(h5_path).predict; ReconstructionLoss(autoencoder, PatchesList)
     Transformations.CorrectPC             :28   CorrectPC(PC, CalibAngle)
 
 Arguments may be NumPy arrays (results come back as NumPy, like the reference) or torch tensors on
@@ -97,6 +98,44 @@ def load_model(path):
     """Replacement for keras.models.load_model on the two shipped .h5 files (Dirs.py:29-30)."""
     kind = default_engine().load_weights(path)
     return _Model(kind, path)
+
+
+class _Autoencoder:
+    """What ``load_autoencoder`` returns: ``.predict(ndarray) -> ndarray`` is ``autoencoder.predict`` (AE4VoxelPatch.py:256);
+    ``threshold`` is what ReconstructionLoss counts a rebuilt voxel by (Voxel.VoxelModel2PC keeps value > 0.1)."""
+
+    def __init__(self, path, threshold=0.1):
+        self.path, self.threshold = path, float(threshold)
+
+    def predict(self, x):
+        e = default_engine()
+        as_np = _is_np(x)
+        xd = _dev(x, torch.float32)
+        assert xd.dim() == 5 and tuple(xd.shape[1:]) == (16, 16, 16, 1), "expected [K,16,16,16,1]"
+        codes = e.encode(e.pack_patches(xd), group=1)
+        return _out(e.decode(codes, prob=True, bits=False).prob.view(-1, 16, 16, 16, 1), as_np)
+
+
+def load_autoencoder(path, encoder_h5=None):
+    """keras.models.load_model on an autoencoder file (AE4VoxelPatch.py:233): the default engine gets its encoder, as ``load_model``
+    gives it, and its decoder.  ``encoder_h5``: see ``Engine.load_autoencoder``."""
+    default_engine().load_autoencoder(path, encoder_h5=encoder_h5)
+    return _Autoencoder(path)
+
+
+def ReconstructionLoss(autoencoder, PatchesList):
+    """The reconstruction quality of ``autoencoder`` on GetPatchesList's patches [P0, P1, P2], P_s [K,16,16,16,1] in {0,1} ->
+    (loss [K,3] f32, counts [K,3,3] i32): per key point and scale Keras's binary_crossentropy (AE4VoxelPatch.py:213, the training and
+    validation loss) and the voxels set in the patch, in the reconstruction (value > autoencoder.threshold) and in both."""
+    e = default_engine()
+    as_np = _is_np(PatchesList[0])
+    loss, counts = [], []
+    for p in PatchesList:
+        bits = e.pack_patches(_dev(p, torch.float32))
+        d = e.decode(e.encode(bits, group=1), target=bits, threshold=autoencoder.threshold, bits=False)
+        loss.append(d.loss)
+        counts.append(d.counts)
+    return _out(torch.stack(loss, dim=1), as_np), _out(torch.stack(counts, dim=1), as_np)
 
 
 def GetKeyPtsByAE(SphericalRing, GridCounter, RespondImg):

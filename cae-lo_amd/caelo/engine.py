@@ -35,6 +35,8 @@ ENCODER_H5 = os.path.join(_DEFAULT_WEIGHTS, "EncoderModel4VoxelPatch.h5")
 # Keras layouts of the two networks' weights, kernel then bias per layer (Engine.set_encoder_weights / set_respond_weights)
 ENCODER_SHAPES = [(3, 3, 3, 1, 8), (8,), (3, 3, 3, 8, 16), (16,), (3, 3, 3, 16, 32), (32,), (2048, 200), (200,), (200, 20), (20,)]
 RESPOND_SHAPES = [(3, 3, 3, 32), (32,), (1, 1, 32, 8), (8,)]
+# the decoder half of an autoencoder file: dense_3, dense_4, conv3d_4 .. conv3d_6 (Engine.set_decoder_weights)
+DECODER_SHAPES = [(20, 200), (200,), (200, 2048), (2048,), (3, 3, 3, 32, 16), (16,), (3, 3, 3, 16, 8), (8,), (3, 3, 3, 8, 1), (1,)]
 
 
 def _ptr(t):
@@ -95,6 +97,9 @@ def note_ties_left(eng, st):
 
 ACTIVATION_CODES = {"tanh": _ffi.ACT_TANH, "relu": _ffi.ACT_RELU, "linear": _ffi.ACT_LINEAR}
 ACTIVATION_NAMES = {v: k for k, v in ACTIVATION_CODES.items()}
+ACTIVATION_NAMES[_ffi.ACT_SIGMOID] = "sigmoid"   # the decoder's output only (caelo_set_decoder_model)
+# Engine.decode's result: the tensors that were asked for, None for the others
+Decoded = collections.namedtuple("Decoded", "prob bits loss counts")
 ENCODER_LAYERS = ("conv3d_1", "conv3d_2", "conv3d_3", "dense_1", "dense_2")   # caelo_host_encoder_range's five bounds, in order
 
 
@@ -713,6 +718,47 @@ class Engine:
             _ffi.check(rc)
         return np.array(out, np.float64), (ENCODER_LAYERS[rc - 1] if rc > 0 else None)
 
+    def set_decoder_weights(self, ws, activations):
+        """caelo_set_decoder_model: the ten arrays of the decoder (dense_3, dense_4, conv3d_4, conv3d_5, conv3d_6: kernel, bias each) as
+        float32 arrays in Keras layout and ``activations`` = (hidden, out), hidden in ("tanh", "relu") for the four hidden layers, out
+        "sigmoid".  Work already issued is waited for first.  The encoder and everything else of the engine are untouched."""
+        ws = self._weight_arrays(ws, DECODER_SHAPES, "decoder")
+        try:
+            h, o = activations
+            h = ACTIVATION_CODES[h] if isinstance(h, str) else int(h)
+            o = _ffi.ACT_SIGMOID if o == "sigmoid" else int(o)
+        except (KeyError, TypeError, ValueError):
+            h = o = -1
+        if h not in (_ffi.ACT_TANH, _ffi.ACT_RELU) or o != _ffi.ACT_SIGMOID:
+            raise ValueError("decoder activations: (hidden, out) with hidden in ('tanh', 'relu') and out 'sigmoid', got %r" % (activations,))
+        torch.cuda.synchronize(self.device)
+        _ffi.check(self.lib.caelo_set_decoder_model(self.ctx, *([_hptr(w) for w in ws] + [h, o])))
+
+    def decoder_activations(self):
+        """caelo_get_decoder_activations -> (hidden, out) of the engine's decoder, e.g. ("relu", "sigmoid"); CaeloError when none is set."""
+        out = (C.c_int32 * 2)()
+        _ffi.check(self.lib.caelo_get_decoder_activations(self.ctx, C.cast(out, C.c_void_p)))
+        return ACTIVATION_NAMES[int(out[0])], ACTIVATION_NAMES[int(out[1])]
+
+    def load_autoencoder(self, path, encoder_h5=None):
+        """A Keras autoencoder .h5 (AE4VoxelPatch.py's AutoencoderModel4VoxelPatch.h5): sets the encoder, exactly as ``load_weights``
+        does for that file, and the decoder.  ``encoder_h5``: where the encoder's weights are when ``path`` was cut down to the
+        decoder's (the test fixtures are stored that way); by default ``path`` must hold both halves.
+        -> ((H, C), (hidden, out)).  Both layer stacks are checked before a weight is read or the engine is changed."""
+        from . import keras_config
+        enc, enc_acts, dec, dec_acts = keras_config.read_autoencoder(path)
+        if dec is None:
+            raise ValueError("%s holds no decoder weights" % path)
+        if encoder_h5 is not None:
+            kind, enc, enc_acts = read_keras_model(encoder_h5)
+            if kind != "encoder":
+                raise ValueError("%s is not a voxel-patch encoder" % encoder_h5)
+        elif enc is None:
+            raise ValueError("%s holds no encoder weights (pass encoder_h5=)" % path)
+        self.set_encoder_weights(enc, activations=enc_acts)
+        self.set_decoder_weights(dec, dec_acts)
+        return enc_acts, dec_acts
+
     def set_respond_weights(self, ws):
         """caelo_set_respond_weights: conv2d_1 and conv2d_2 of the response layer (kernel, bias each), float32 arrays in Keras layout."""
         ws = self._weight_arrays(ws, RESPOND_SHAPES, "response-layer")
@@ -1017,6 +1063,39 @@ class Engine:
         _ffi.check(self.lib.caelo_encode(self.ctx, _ptr(bits), n, group, _ptr(out), 20 * group, _ptr(ws), self.stream))
         return out
 
+    def decode(self, codes, group=1, target=None, threshold=0.1, prob=False, bits=True, loss=None, counts=None):
+        """caelo_decode: codes [m, ld] f32 (contiguous; patch p = row p // group, columns (p % group) * 20 .. + 20: ``group=1`` on
+        [n,20] codes, ``group=3`` on the [K,64] descriptor rows of ``extract`` / the pipeline) through the engine's decoder ->
+        Decoded(prob [n,4096] f32 in (x, y, z) order, bits [n,64] int64 (voxel set <=> prob > threshold), loss [n] f32 (Keras
+        binary_crossentropy against ``target`` [n,64] int64), counts [n,3] int32 (voxels set in target, in bits, in both)); a field
+        that was not asked for is None.  ``loss`` / ``counts`` default to "when a target is given".  No host sync."""
+        assert codes.dtype == torch.float32 and codes.dim() == 2 and codes.is_contiguous()
+        group, ld = int(group), int(codes.shape[1])
+        n = codes.shape[0] * group
+        if target is not None:
+            assert target.dtype == torch.int64 and target.is_contiguous() and target.numel() == n * 64, "target: [n, 64] int64"
+        loss = target is not None if loss is None else bool(loss)
+        counts = target is not None if counts is None else bool(counts)
+        out = Decoded(self.empty((n, 4096), torch.float32) if prob else None, self.empty((n, 64), torch.int64) if bits else None,
+                      self.empty((n,), torch.float32) if loss else None, self.empty((n, 3), torch.int32) if counts else None)
+        if n == 0 and any(o is not None for o in out):   # (an empty tensor has no address to hand over)
+            return out
+        ws = self._ws("decode", int(self.lib.caelo_decode_ws_bytes(n)))
+        _ffi.check(self.lib.caelo_decode(self.ctx, _ptr(codes), n, group, ld, _ptr(target), float(threshold), _ptr(out.prob), _ptr(out.bits),
+                                         _ptr(out.loss), _ptr(out.counts), _ptr(ws), self.stream))
+        return out
+
+    def decode_layers(self, codes):
+        """Test aid: decode [n,20] codes (bits only) and return what Dense(2048) left in the workspace -- G4 [n,2048] f32, activated
+        (caelo_decode_ws_layout)."""
+        n = codes.shape[0]
+        self.decode(codes)
+        ws = self._ws("decode", int(self.lib.caelo_decode_ws_bytes(n)))
+        lay = (C.c_int64 * 2)()
+        _ffi.check(self.lib.caelo_decode_ws_layout(n, C.cast(lay, C.c_void_p)))
+        off, rows = int(lay[0]), int(lay[1])
+        return ws[off:off + rows * 8192].view(torch.float32).view(rows, 2048).clone()
+
     def encode_layers(self, bits):
         """Test aid: encode (group 1, every patch) and return the activations the four encoder kernels leave in the
         workspace -- P2 [n,1024] (after pool2), F3 [n,2048] (after conv3), the Dense(200) pre-activations summed over the
@@ -1266,6 +1345,13 @@ class Engine:
         raw = ws[off:off + n * 512 + 256 + 8 * n].cpu().numpy()
         tab = raw[n * 512:].view(np.int32)
         return raw[:n * 512].view(np.uint64).reshape(n, 64), int(tab[0]), tab[64:64 + n].copy(), tab[64 + n:64 + 2 * n].copy()
+
+    def extract_patch_bits(self):
+        """The bit-packed patches the last ``extract`` on the current stream gathered -> [1024,3,64] int64 (device, a copy; rows past
+        ``n_key`` are not meaningful).  No host sync."""
+        ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
+        off, n = int(self.lib.caelo_extract_ws_frame_offset()), 3 * MAX_K
+        return ws[off:off + n * 512].view(torch.int64).view(MAX_K, 3, 64).clone()
 
     def resolve_ties(self, ff, pc):
         """The fused path (extract / Pipeline.run) builds voxel SETS; where the 496-nearest cut of Voxel.py:195-196 splits a class

@@ -302,3 +302,45 @@ def save_registration(path, row):
     io.savemat(path, {"EvaluationResults": np.asarray(row, dtype=np.float32).reshape(1, 7)})
     return path
 
+
+
+# ---- reconstruction quality of an autoencoder (AE4VoxelPatch.py:213,228,242-284) ----------------------------------------------------
+def reconstruction(engine, scans, threshold=0.1):
+    """How well the engine's autoencoder (Engine.load_autoencoder) rebuilds the patches of ``scans`` (an iterable of [N,4] f32 clouds):
+    per frame the key points, patches and descriptors of ``Engine.extract``, then ``Engine.decode`` of the resident descriptor rows
+    against the patches.  -> dict: ``n_key`` [F] i32, ``loss`` [F,3] f32 the mean binary_crossentropy per frame and scale, ``iou``
+    [F,3] f64 = both / (in + out - both) over a frame's patches of a scale (voxels set in the patch, in the reconstruction at
+    ``threshold``, in both; NaN when neither has a voxel), ``patch_loss`` [sum K,3] f32 every patch's loss, ``mean_loss`` the mean over
+    all patches in float64 -- Keras's validation-loss figure for them."""
+    import torch
+    from .engine import raise_status
+    n_key, loss, iou, per_patch = [], [], [], []
+    for pc in scans:
+        pc = pc if isinstance(pc, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(pc, dtype=np.float32))
+        ff = engine.extract(pc.to(engine.device).contiguous())
+        bits = engine.extract_patch_bits()
+        raise_status(int(ff.status[0].item()))
+        k = int(ff.n_key.item())
+        if k < 1:   # (the detector's own check, raise_status, refuses fewer than 51 key points: this guards other sources of rows)
+            raise ValueError("frame %d has no key points: nothing to reconstruct" % len(n_key))
+        d = engine.decode(ff.rows[:k].contiguous(), group=3, target=bits[:k].contiguous(), threshold=threshold, bits=False)
+        l = d.loss.view(k, 3).cpu().numpy()
+        c = d.counts.view(k, 3, 3).cpu().numpy().astype(np.int64).sum(axis=0)   # [scale][in, out, both]
+        union = c[:, 0] + c[:, 1] - c[:, 2]
+        n_key.append(k)
+        per_patch.append(l)
+        loss.append(l.mean(axis=0, dtype=np.float64).astype(np.float32))
+        iou.append(np.where(union > 0, c[:, 2] / np.maximum(union, 1), np.nan))
+    if not n_key:
+        raise ValueError("no scans to evaluate")
+    per_patch = np.concatenate(per_patch)
+    return dict(n_key=np.asarray(n_key, np.int32), loss=np.stack(loss), iou=np.stack(iou), patch_loss=per_patch,
+                mean_loss=float(per_patch.mean(dtype=np.float64)), threshold=float(threshold))
+
+
+def save_reconstruction(path, res):
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    io.savemat(path, {"n_key": res["n_key"], "loss": res["loss"], "iou": res["iou"], "patch_loss": res["patch_loss"],
+                      "mean_loss": np.float64(res["mean_loss"]), "threshold": np.float64(res["threshold"])})

@@ -36,6 +36,21 @@ ENCODER_SPEC = [
 ]
 
 
+# what decoder.hip implements: the suffix of an autoencoder behind the encoder's Dense(20) (AE4VoxelPatch.py:199-211)
+_UP = dict(size=[2, 2, 2], data_format="channels_last")
+DECODER_SPEC = [
+    ("Dense", dict(units=200, activation="relu", use_bias=True)),
+    ("Dense", dict(units=2048, activation="relu", use_bias=True)),
+    ("Reshape", dict(target_shape=[4, 4, 4, 32])),
+    ("Conv3D", dict(_C3, filters=16, activation="relu")), ("UpSampling3D", _UP),
+    ("Conv3D", dict(_C3, filters=8, activation="relu")), ("UpSampling3D", _UP),
+    ("Conv3D", dict(_C3, filters=1, activation="sigmoid")),
+]
+DECODER_OUT_ACTIVATIONS = ("sigmoid",)    # conv3d_6
+_DEC_ACTIVATED = [i for i, (c, _) in enumerate(DECODER_SPEC) if c in ("Conv3D", "Dense")]
+DECODER_SIZES = [4000, 200, 409600, 2048, 13824, 16, 3456, 8, 216, 1]   # dense_3, dense_4, conv3d_4 .. conv3d_6: kernel, bias
+
+
 HIDDEN_ACTIVATIONS = ("tanh", "relu")     # conv3d_1, conv3d_2, conv3d_3, dense_1: one of these, the same on all four
 CODE_ACTIVATIONS = ("tanh", "linear")     # dense_2
 _ACTIVATED = [i for i, (c, _) in enumerate(ENCODER_SPEC) if c in ("Conv3D", "Dense")]
@@ -122,6 +137,70 @@ def encoder_model(lys):
             if _norm(got) != _norm(val):
                 raise ValueError("unsupported encoder: %s(%s).%s = %r, the kernels implement %r" % (cls, cfg.get("name"), key, got, val))
     return cut, (hidden, code)
+
+
+def decoder_model(lys):
+    """The decoder inside a full autoencoder -> (index of its first layer, (hidden, out)).
+
+    ``lys`` is a linear Conv3D stack whose prefix is the encoder (``encoder_model``); the layers that follow its ``Dense(20)`` must be
+    ``Dense(200)``, ``Dense(2048)``, ``Reshape([4,4,4,32])``, ``Conv3D(16)``, ``UpSampling3D([2,2,2])``, ``Conv3D(8)``,
+    ``UpSampling3D([2,2,2])``, ``Conv3D(1)``.  ValueError, in ``check``'s words, for everything the kernels do not implement: a bare
+    encoder, hidden activations that differ from each other or lie outside ``HIDDEN_ACTIVATIONS``, an output activation outside
+    ``DECODER_OUT_ACTIVATIONS``, other kernel sizes, strides, paddings, units, up-sampling sizes or target shapes."""
+    cut, _ = encoder_model(lys)
+    tail = lys[cut:]
+    classes, want = [c for c, _ in tail], [c for c, _ in DECODER_SPEC]
+    if not tail:
+        raise ValueError("unsupported decoder: the file holds a bare encoder (layers: %s), the kernels implement %s behind it"
+                         % ([c for c, _ in lys], want))
+    if classes != want:
+        raise ValueError("unsupported decoder layer stack %s (kernels implement %s)" % (classes, want))
+    acts = [tail[i][1].get("activation") for i in _DEC_ACTIVATED]
+    hidden, out = acts[0], acts[-1]
+    for i, a in zip(_DEC_ACTIVATED[:-1], acts[:-1]):
+        if a not in HIDDEN_ACTIVATIONS or a != hidden:
+            raise ValueError("unsupported decoder: %s(%s).activation = %r, the kernels implement one of %r on all four hidden layers (%s has %r)"
+                             % (tail[i][0], tail[i][1].get("name"), a, HIDDEN_ACTIVATIONS, tail[_DEC_ACTIVATED[0]][1].get("name"), hidden))
+    if out not in DECODER_OUT_ACTIVATIONS:
+        raise ValueError("unsupported decoder: Conv3D(%s).activation = %r, the kernels implement %r for the output"
+                         % (tail[-1][1].get("name"), out, DECODER_OUT_ACTIVATIONS[0]))
+    for (cls, cfg), (_, spec) in zip(tail, DECODER_SPEC):
+        for key, val in spec.items():
+            if key == "activation":
+                continue
+            got = cfg.get(key, "channels_last" if key == "data_format" else None)
+            if _norm(got) != _norm(val):
+                raise ValueError("unsupported decoder: %s(%s).%s = %r, the kernels implement %r" % (cls, cfg.get("name"), key, got, val))
+    return cut, (hidden, out)
+
+
+def _layer_weights(h, names, keep):
+    ws = []
+    for ln in names:
+        if ln not in keep:
+            continue
+        for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+            ws.append(np.ascontiguousarray(h.dataset("/model_weights/%s/%s" % (ln, wn.decode())), np.float32))
+    return ws
+
+
+def read_autoencoder(path):
+    """-> (encoder ws [10], (H, C), decoder ws [10], (hidden, out)) from a Keras 2.2 autoencoder .h5.  Both halves of the layer stack
+    are compared field by field with what the kernels implement (``encoder_model``, ``decoder_model``) before a weight is read.
+    A half whose layers are all stored with an empty ``weight_names`` (a file cut down to the other half, as the test fixtures are)
+    comes back as None; a half that is there in part, or in other shapes, is a ValueError."""
+    h = H5File(path)
+    lys = layers(h)
+    cut, enc_acts = encoder_model(lys)
+    _, dec_acts = decoder_model(lys)
+    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
+    enc = _layer_weights(h, names, {cfg["name"] for _, cfg in lys[:cut]}) or None
+    dec = _layer_weights(h, names, {cfg["name"] for _, cfg in lys[cut:]}) or None
+    if enc is not None and [w.size for w in enc] != [216, 8, 3456, 16, 13824, 32, 409600, 200, 4000, 20]:
+        raise ValueError("%s: weight shapes %s do not match the encoder architecture" % (path, [w.shape for w in enc]))
+    if dec is not None and [w.size for w in dec] != DECODER_SIZES:
+        raise ValueError("%s: weight shapes %s do not match the decoder architecture" % (path, [w.shape for w in dec]))
+    return enc, enc_acts, dec, dec_acts
 
 
 def read_model(path):

@@ -66,6 +66,9 @@ struct caelo_ctx {
     int enc_hidden, enc_code;   // CAELO_ACT_*: conv3d_1..3 + dense_1 / dense_2 (caelo_set_encoder_model); tanh / tanh from caelo_create on
     bool enc_reference;   // caelo_set_encoder_reference: stage 1 = the exact-f32 k_enc_stage1 (precision reference)
     int32_t *faults;  // device counter of the pair kernels' lane-agreement checks (match.hip); 0 on healthy hardware
+    float *dec_w;     // the decoder's image (decoder.hip, DEC_O_*): dense_3, dense_4 as B fragments, conv3d_4, the folded conv3d_5 / conv3d_6; null until set
+    bool has_dec;
+    int dec_hidden, dec_out;   // CAELO_ACT_*: dense_3, dense_4, conv3d_4, conv3d_5 / conv3d_6 (caelo_set_decoder_model)
     double calib_angle;  // caelo_set_calib_angle: degrees, what CAELO_EXTRACT_CORRECT_PC rotates a scan by (correct.hip); 0 until set
 };
 
@@ -488,6 +491,18 @@ __device__ inline int caelo_brick_find(const caelo_brick_table &t, unsigned long
 }
 
 static inline hipStream_t caelo_stream(void *s) { return (hipStream_t)s; }
+
+// Per-DEVICE caches of things the runtime is asked once: function attributes and occupancy answers belong to the device that is
+// current when they are set / asked (process-wide statics would serve a second GPU the first one's answers).
+#include <mutex>
+#define CAELO_MAX_DEVICES 64
+template <typename T, typename F>
+static T per_device_once(int device, T (&slot)[CAELO_MAX_DEVICES], bool (&have)[CAELO_MAX_DEVICES], std::mutex &mu, F make) {
+    const int d = device >= 0 && device < CAELO_MAX_DEVICES ? device : 0;
+    std::lock_guard<std::mutex> lock(mu);
+    if (!have[d]) { slot[d] = make(); have[d] = true; }
+    return slot[d];
+}
 
 // ---- one global atomic per WORKGROUP ------------------------------------------------------------------
 // Device-scope atomics execute at the memory side on MI355X (8 XCDs, non-coherent L2s): ~10 ns each when

@@ -1144,18 +1144,7 @@ __global__ void __launch_bounds__(D1_THREADS, 2) k_enc_dense1p(const float *__re
         }
 }
 
-// Per-DEVICE caches of things the runtime is asked once: function attributes and occupancy answers belong to the device that is
-// current when they are set / asked (process-wide statics would serve a second GPU the first one's answers).
-#include <mutex>
-#define CAELO_MAX_DEVICES 64
-template <typename T, typename F>
-static T per_device_once(int device, T (&slot)[CAELO_MAX_DEVICES], bool (&have)[CAELO_MAX_DEVICES], std::mutex &mu, F make) {
-    const int d = device >= 0 && device < CAELO_MAX_DEVICES ? device : 0;
-    std::lock_guard<std::mutex> lock(mu);
-    if (!have[d]) { slot[d] = make(); have[d] = true; }
-    return slot[d];
-}
-
+// (per_device_once: caelo_internal.h)
 template <int KTOT>
 static int dense1_launch(int device, const float *f3, int64_t np, const void *wd1x, float *part, const caelo_enc_in &in, hipStream_t s) {
     // once per device (under a lock: the pipeline's encoder thread and the caller may race here)

@@ -5,12 +5,17 @@
                                     [--gt ... --est ... --calib ... --matchability ...] [--frame-step s] [--out EvaluationResults.mat]
     python evaluate.py keypoints --keypts-dir 00/Features --source ae --gt poses/00.txt --calib calib/00/calib_.txt \\
                                  [--frame-step s] [--inner] --out AccuracyOfKeyPts_1_0_00.mat
+    python evaluate.py reconstruction --autoencoder-h5 AutoencoderModel4VoxelPatch.h5 (--scans <seq>/velodyne | --synthetic N) \\
+                                      [--threshold 0.1] [--every k] --out recon.mat
 
 registration (EvaluationOnRegistration.py / EvalOnReg_KeyPts.py): one --gt / --est / --calib / --matchability per sequence, the
 sequences concatenated; prints RRE, stdRRE, RTE, stdRTE, success rate (RRE < 1 deg and RTE < 0.5 m), inlier ratio (both
 fractions) and average RANSAC trials; --out writes them as the 1 x 7 float32 EvaluationResults.
 keypoints (EvaluationOnKeypts.py): key point repeatability of one sequence; the nearest-neighbour search runs on the GPU
 (caelo_kp_nn_pairs); prints the counts and writes the reference's {'counts': ...} file.  --inner is the reference's mode 1.
+reconstruction (AE4VoxelPatch.py:213,228,242-284): how well an autoencoder file rebuilds the patches of scans -- per frame and scale
+the mean binary_crossentropy and the IoU of the voxels with value > threshold (Voxel.VoxelModel2PC's test), and the mean loss over all
+patches (Keras's validation-loss figure); the decoder runs on the GPU (caelo_decode).
 """
 import argparse
 import os
@@ -22,6 +27,32 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 from caelo import evaluate as ev  # noqa: E402
+
+
+def reconstruction_main(ap, a):
+    import glob
+    if not 0.0 < a.threshold < 1.0:
+        ap.error("--threshold must lie in (0, 1)")
+    if a.every < 1 or (a.synthetic is not None and a.synthetic < 1):
+        ap.error("--every and --synthetic must be >= 1")
+    import caelo
+    from caelo import synth
+    from caelo.engine import Engine
+    caelo.configure_runtime()
+    eng = Engine()
+    eng.load_autoencoder(a.autoencoder_h5, encoder_h5=a.encoder_h5)
+    if a.scans:
+        files = sorted(glob.glob(os.path.join(a.scans, "*.bin")))[::a.every]
+        if not files:
+            ap.error("no .bin files in %s" % a.scans)
+        scans = (np.fromfile(f, dtype=np.float32).reshape(-1, 4) for f in files)
+    else:
+        scans = (synth.make_scan(f, quantum=1e-3) for f in range(0, a.synthetic, a.every))
+    res = ev.reconstruction(eng, scans, a.threshold)
+    ev.save_reconstruction(a.out, res)
+    print("reconstruction: %d frames, %d patches, mean loss %.6g, mean IoU per scale %s at threshold %g -> %s" % (
+        len(res["n_key"]), res["patch_loss"].size, res["mean_loss"], np.round(np.nanmean(res["iou"], axis=0), 4).tolist(), a.threshold, a.out))
+    return 0
 
 
 def main(argv=None):
@@ -42,7 +73,18 @@ def main(argv=None):
     k.add_argument("--frame-step", type=int, default=1)
     k.add_argument("--inner", action="store_true", help="mode 1 (ComputeDispersionOfKeypoints): each frame against itself")
     k.add_argument("--out", required=True, help="the counts file (the reference names it AccuracyOfKeyPts_<step>_<source>_<seq>.mat)")
+    c = sub.add_parser("reconstruction", help="an autoencoder's reconstruction loss and IoU on the patches of scans")
+    c.add_argument("--autoencoder-h5", required=True, help="the autoencoder file (encoder and decoder)")
+    c.add_argument("--encoder-h5", help="the encoder's weights, when --autoencoder-h5 was cut down to the decoder's")
+    src = c.add_mutually_exclusive_group(required=True)
+    src.add_argument("--scans", help="directory of KITTI velodyne .bin files")
+    src.add_argument("--synthetic", type=int, help="number of synthetic 64x2000 scans (caelo.synth)")
+    c.add_argument("--threshold", type=float, default=0.1, help="a rebuilt voxel is set when its value exceeds this (0 < t < 1)")
+    c.add_argument("--every", type=int, default=1, help="evaluate every k-th scan")
+    c.add_argument("--out", required=True, help="the result file (.mat): n_key, loss, iou, patch_loss, mean_loss, threshold")
     a = ap.parse_args(argv)
+    if a.cmd == "reconstruction":
+        return reconstruction_main(ap, a)
     if a.frame_step < 1:
         ap.error("--frame-step must be >= 1")
 

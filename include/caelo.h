@@ -150,6 +150,35 @@ int caelo_host_encoder_range(const float *w1_host, const float *b1_host, const f
  * PatchEncoder.predict, Match.py:131-133, has one arithmetic). */
 int caelo_set_encoder_reference(caelo_ctx *ctx, int on);
 
+/* The decoder half of an autoencoder file (AE4VoxelPatch.py:199-211): Dense(200), Dense(2048), Reshape(4,4,4,32), Conv3D(16),
+ * UpSampling3D(2), Conv3D(8), UpSampling3D(2), Conv3D(1).  hidden in {CAELO_ACT_TANH, CAELO_ACT_RELU} on the four hidden layers,
+ * out = CAELO_ACT_SIGMOID; anything else is CAELO_ERR_ARG.  Host pointers, Keras layouts.  A context has no decoder until one is
+ * set, and everything else behaves the same with or without one.  All arithmetic is f32 (f32-input matrix instructions), so there
+ * is no range guard.
+ * caelo_host_decoder_fold (host only, no device): UpSampling3D(2) + a 3^3 `same` convolution as eight parity classes of 2^3 taps on
+ *   the source grid -- folded[p][o] = the sum, in float64 rounded once, of the taps t with ((p + t - 1) >> 1) - (p - 1) == o per axis
+ *   (p, o, t as x*4+y*2+z resp. x*9+y*3+z); output voxel 2s + p reads source cell s + o + p - 1.
+ * caelo_decode: codes[(p / group) * ld + (p % group) * 20 + j] f32 (group = 1, ld = 20: plain rows; group = 3, ld = 64: the
+ *   pipeline's resident descriptor rows) -> any of prob [n][4096] f32 (x, y, z order: autoencoder.predict, AE4VoxelPatch.py:256),
+ *   rebuilt [n][64] u64 (the packed patch layout; voxel set <=> (double)prob > threshold, Voxel.VoxelModel2PC's test),
+ *   loss [n] f32 (Keras binary_crossentropy against target_bits [n][64]: mean over the 4096 voxels of -(y log p^ + (1 - y) log(1 - p^)),
+ *   p^ = clip(p, 1e-7, 1 - 1e-7)) and counts [n][3] i32 (voxels set in the target, in rebuilt, in both; the first and the last are 0
+ *   without a target).  Every output may be NULL, not all of them.  CAELO_ERR_ARG before any launch: no decoder set, loss without
+ *   target, threshold outside (0, 1) or not finite, group * 20 > ld, n < 0, no output.  n = 0 does nothing.  ws: caelo_decode_ws_bytes(n)
+ *   bytes, no initialisation needed, one per stream.  A patch's outputs do not depend on n or on its position.
+ * caelo_decode_ws_layout (test aid): out[0] = byte offset in ws of G4 [n][2048] f32 (Dense(2048)'s activated output), out[1] = its rows. */
+#define CAELO_ACT_SIGMOID 3
+int caelo_set_decoder_model(caelo_ctx *ctx, const float *wd3_host /*[20][200]*/, const float *bd3_host, const float *wd4_host /*[200][2048]*/,
+                            const float *bd4_host, const float *w4_host /*[27][32][16]*/, const float *b4_host,
+                            const float *w5_host /*[27][16][8]*/, const float *b5_host, const float *w6_host /*[27][8][1]*/,
+                            const float *b6_host, int hidden, int out);
+int caelo_get_decoder_activations(caelo_ctx *ctx, int32_t out[2] /* hidden, out */);
+int caelo_host_decoder_fold(const float *w /*[27][cin][cout]*/, int cin, int cout, float *folded /*[8][8][cin][cout]*/);
+int64_t caelo_decode_ws_bytes(int64_t n_patches);
+int caelo_decode_ws_layout(int64_t n_patches, int64_t out[2]);
+int caelo_decode(caelo_ctx *ctx, const float *codes, int64_t n_patches, int group, int ld, const uint64_t *target_bits, double threshold,
+                 float *prob, uint64_t *rebuilt, float *loss, int32_t *counts, void *ws, void *stream);
+
 /* CorrectPC  (Transformations.py:28-39; BatchPreprocess.py:70-88 BatchCorrectPC): every point rotated by calib_angle_deg about the
  * axis p x z^, the HDL-64E's vertical-angle calibration of the KITTI scans.  pc, out [n][stride] f32 (device), stride 3 or 4; with
  * stride 4 the fourth column (intensity) is copied bit for bit.  out may not overlap pc; n = 0 does nothing; a non-finite angle is
