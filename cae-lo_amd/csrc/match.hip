@@ -60,18 +60,17 @@ typedef double mm_f64x4 __attribute__((ext_vector_type(4)));
 #define MM_TPS 2       // row tiles per wavefront and step: a step stages MM_RQ * MM_TPS tiles (128 rows), one barrier each
 #define MM_STEP_TILES (MM_RQ * MM_TPS)
 
-static inline int64_t ms_ws_bytes(int64_t kmax);
-CAELO_API int64_t caelo_match_ws_bytes(int64_t k_max) {
-    // [0] columns re-scanned exactly, [1] columns decided between two rows (statistics only), then the f16 operand images of
-    // both frames (match_screen.inc); k_max = the larger of the two frames' row capacities
-    return ms_ws_bytes(k_max > 0 ? k_max : 1);
-}
-static inline int64_t msw_ws_bytes(int64_t kmax, int nb);
+static inline int64_t ms_ws_bytes(int64_t kmax, int nb);
 __host__ __device__ inline int msw_nb(int dim);
+CAELO_API int64_t caelo_match_ws_bytes(int64_t k_max) {
+    // [0] columns re-scanned exactly, [1] columns decided between two rows (statistics only), then frame 0's f16 operand image and
+    // its rows' window shares (match_screen.inc); k_max = the larger of the two frames' row capacities
+    return ms_ws_bytes(k_max > 0 ? k_max : 1, 1);
+}
 CAELO_API int64_t caelo_match_ws_bytes_dim(int64_t k_max, int dim) {
     // descriptors wider than 64: nb = ceil((dim + 2) / 64) operand images per 16-row tile of frame 0 (match_screen_wide.inc)
     if (dim <= MT_MAXDIM) return caelo_match_ws_bytes(k_max);
-    return msw_ws_bytes(k_max > 0 ? k_max : 1, msw_nb(dim));
+    return ms_ws_bytes(k_max > 0 ? k_max : 1, msw_nb(dim));
 }
 
 __device__ inline double exact_dist(const float *a, const float *b, int dim) {
@@ -342,6 +341,39 @@ __global__ void __launch_bounds__(64 * MM_WAVES) k_match_mfma(const caelo_pair_s
 #include "match_screen.inc"
 #include "match_screen_wide.inc"
 
+// Every launch of the screen: k_match_prep* + k_match_screen* over one set or table of pairs -- the padded row count, the 16-byte row
+// test (`aligned`: every descriptor pointer of the launch is 16-byte aligned, rows16), the two grids; the kernels follow from the argument
+// (a set or a table) and the number of K = 64 blocks.  `between`: an event recorded after the prep kernel (caelo_match_profile).
+static bool rows16(const caelo_pair_set &ps) {
+    bool a = true;
+    for (int i = 0; i < ps.n; ++i) a = a && (((uintptr_t)ps.p[i].f0 | (uintptr_t)ps.p[i].f1) & 15u) == 0;
+    return a;
+}
+template <class PS>
+static int screen_launch(const PS &ps, bool aligned, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, hipStream_t s, hipEvent_t between = nullptr) {
+    constexpr bool TABLE = std::is_same<PS, caelo_pair_table>::value;   // (tables hold the pipeline's rows: 60-d, one block)
+    const int nb = dim <= 62 ? 1 : msw_nb(dim);
+    const int64_t kpad = ms_pad16(k0_max > k1_max ? k0_max : k1_max);
+    const int v4 = (aligned && dim % 4 == 0 && ld0 % 4 == 0 && ld1 % 4 == 0) ? 1 : 0;
+    const dim3 grid_prep((unsigned)((kpad / 16 + 3) / 4), 1, ps.n), grid((unsigned)((k1_max + 16 * MS_CT - 1) / (16 * MS_CT)), 1, ps.n);
+    void (*screen)(PS, int, int64_t, int, int64_t, int, int64_t, int);
+    if constexpr (TABLE) {
+        k_match_prep_tab<<<grid_prep, 256, 0, s>>>(ps, ld0, k0_max, dim, kpad, v4);
+        screen = k_match_screen_tab;
+    } else if (nb == 1) {
+        k_match_prep<<<grid_prep, 256, 0, s>>>(ps, ld0, k0_max, dim, kpad, v4);
+        screen = k_match_screen;
+    } else {
+        k_match_prep_wide<<<grid_prep, 256, 0, s>>>(ps, ld0, k0_max, dim, nb, kpad, v4);
+        screen = nb == 2 ? k_match_screen_wide<2> : nb == 3 ? k_match_screen_wide<3> : nb == 4 ? k_match_screen_wide<4> : k_match_screen_wide<5>;
+    }
+    CAELO_LAUNCH_CHECK();
+    if (between) CAELO_HIP(hipEventRecord(between, s));
+    screen<<<grid, 64 * MS_NW, 0, s>>>(ps, ld0, k0_max, ld1, k1_max, dim, kpad, v4);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
 CAELO_API int caelo_match(caelo_ctx *c, const float *f0, int ld0, int64_t k0_max, const int32_t *n0, const float *f1,
                           int ld1, int64_t k1_max, const int32_t *n1, int dim, int64_t *pair_idx, void *ws, void *stream) {
     CAELO_REQUIRE(c && f0 && f1 && pair_idx && ws, "null argument");
@@ -369,15 +401,12 @@ CAELO_API int caelo_match_profile(caelo_ctx *c, const float *const *rows, int n_
     }
     hipEvent_t ev[3];
     for (hipEvent_t &e : ev) CAELO_HIP(hipEventCreate(&e));
-    const int64_t kpad = ms_pad16(CAELO_MAX_KEYPTS);
     int rc = CAELO_OK;
     float both = 0.f, prep = 0.f;
     for (int r = 0; r < repeats && rc == CAELO_OK; ++r) {
         CAELO_HIP(hipEventRecord(ev[0], s));
-        k_match_prep<<<dim3((unsigned)((kpad / 16 + 3) / 4), 1, ps.n), 256, 0, s>>>(ps, 64, CAELO_MAX_KEYPTS, 60, kpad, 1);
-        CAELO_HIP(hipEventRecord(ev[1], s));
-        k_match_screen<<<dim3((unsigned)((CAELO_MAX_KEYPTS + 16 * MS_CT - 1) / (16 * MS_CT)), 1, ps.n), 64 * MS_NW, 0, s>>>(ps, 64, CAELO_MAX_KEYPTS, 64,
-                                                                                                                 CAELO_MAX_KEYPTS, 60, kpad, 1);
+        rc = screen_launch(ps, true, 64, CAELO_MAX_KEYPTS, 64, CAELO_MAX_KEYPTS, 60, s, ev[1]);   // (the pipeline's rows, as match_table)
+        if (rc != CAELO_OK) break;
         CAELO_HIP(hipEventRecord(ev[2], s));
         CAELO_HIP(hipEventSynchronize(ev[2]));
         float a = 0.f, b = 0.f;
@@ -399,21 +428,9 @@ int match_set(const caelo_pair_set &ps, int ld0, int64_t k0_max, int ld1, int64_
     // K = 64 (the reference's descriptors are 60 wide); wider ones: the all-f64 kernel.  Same pair_idx bit for bit
     // (tests/test_gpu_parity.py::test_match_shape_sweep_vs_oracle covers both).  Past 64 the screen again, over several K = 64
     // blocks (match_screen_wide.inc; the workspace is caelo_match_ws_bytes_dim's).
-    if (dim > MT_MAXDIM) return match_set_wide(ps, ld0, k0_max, ld1, k1_max, dim, s);
-    if (dim <= 62) {
-        const int64_t kpad = ms_pad16(k0_max > k1_max ? k0_max : k1_max);
-        bool v4 = (dim % 4 == 0) && (ld0 % 4 == 0) && (ld1 % 4 == 0);
-        for (int i = 0; i < ps.n; ++i) v4 = v4 && (((uintptr_t)ps.p[i].f0 | (uintptr_t)ps.p[i].f1) & 15u) == 0;
-        k_match_prep<<<dim3((unsigned)((kpad / 16 + 3) / 4), 1, ps.n), 256, 0, s>>>(ps, ld0, k0_max, dim, kpad, v4 ? 1 : 0);
-        CAELO_LAUNCH_CHECK();
-        k_match_screen<<<dim3((unsigned)((k1_max + 16 * MS_CT - 1) / (16 * MS_CT)), 1, ps.n), 64 * MS_NW, 0, s>>>(ps, ld0, k0_max, ld1, k1_max,
-                                                                                                            dim, kpad, v4 ? 1 : 0);
-        CAELO_LAUNCH_CHECK();
-        return CAELO_OK;
-    }
+    if (dim <= 62 || dim > MT_MAXDIM) return screen_launch(ps, rows16(ps), ld0, k0_max, ld1, k1_max, dim, s);
     const int64_t tiles = (k1_max + 16 * MM_CT - 1) / (16 * MM_CT);  // workgroups of MM_CT column tiles
-    bool vec = (dim % 4 == 0) && (ld0 % 4 == 0) && (ld1 % 4 == 0);
-    for (int i = 0; i < ps.n; ++i) vec = vec && (((uintptr_t)ps.p[i].f0 | (uintptr_t)ps.p[i].f1) & 15u) == 0;
+    const bool vec = rows16(ps) && (dim % 4 == 0) && (ld0 % 4 == 0) && (ld1 % 4 == 0);
     dim3 grid((unsigned)tiles, 1, ps.n);
     if (vec)
         k_match_mfma<true><<<grid, 64 * MM_WAVES, 0, s>>>(ps, ld0, k0_max, ld1, k1_max, dim);
@@ -1191,23 +1208,33 @@ CAELO_API int caelo_ransac(caelo_ctx *c, const float *pc0, int ld0, const float 
     return ransac_set(ps, ld0, ld1, k1_max, caelo_stream(stream));
 }
 
+// Every launch of the RANSAC kernels over one set or table of pairs.  `any_cert`: some pair leaves a certificate -- bounds for the
+// 0.8 / 1.6 m levels of the pairs whose first level failed (workgroups of the others return at once); `all_cert_only`: the host half
+// decides every pair, no finishing kernel.
+template <class PS>
+static int ransac_launch(const PS &ps, int ld0, int ld1, int64_t k1_max, bool any_cert, bool all_cert_only, hipStream_t s,
+                         void (*hyp)(PS, int, int, int64_t), void (*hyp_up)(PS, int, int, int64_t), void (*finish)(PS, int, int, int64_t)) {
+    hyp<<<dim3((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * RH_PER_WAVE - 1) / (RE_WAVES * RH_PER_WAVE), 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+    CAELO_LAUNCH_CHECK();
+    if (any_cert) {
+        hyp_up<<<dim3(RU_BLOCKS, 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+        CAELO_LAUNCH_CHECK();
+    }
+    if (all_cert_only) return CAELO_OK;
+    finish<<<dim3(1, 1, ps.n), 64 * RF_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
 int ransac_set(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, hipStream_t s) {
     CAELO_REQUIRE(ps.n >= 1 && ps.n <= CAELO_FB_MAX, "bad pair count");
     CAELO_REQUIRE(k1_max > 0 && ld0 >= 3 && ld1 >= 3, "bad shape");
-    k_ransac_hyp<<<dim3((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * RH_PER_WAVE - 1) / (RE_WAVES * RH_PER_WAVE), 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
-    CAELO_LAUNCH_CHECK();
-    bool all_cert_only = true;
-    for (int i = 0; i < ps.n; ++i) all_cert_only = all_cert_only && ps.p[i].cert && ps.p[i].cert_only;
-    bool any_cert = false;
-    for (int i = 0; i < ps.n; ++i) any_cert = any_cert || ps.p[i].cert != nullptr;
-    if (any_cert) {   // bounds for the 0.8 / 1.6 m levels of the pairs whose first level failed (workgroups of the others return at once)
-        k_ransac_hyp_up<<<dim3(RU_BLOCKS, 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
-        CAELO_LAUNCH_CHECK();
+    bool any_cert = false, all_cert_only = true;
+    for (int i = 0; i < ps.n; ++i) {
+        any_cert = any_cert || ps.p[i].cert != nullptr;
+        all_cert_only = all_cert_only && ps.p[i].cert && ps.p[i].cert_only;
     }
-    if (all_cert_only) return CAELO_OK;   // the host half decides every pair of the set: no finishing kernel
-    k_ransac_finish<<<dim3(1, 1, ps.n), 64 * RF_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, k_ransac_hyp, k_ransac_hyp_up, k_ransac_finish);
 }
 
 // The pair stage's launches over one slice of a pair table (caelo_register_pairs): the shapes of match_set / ransac_set for the
@@ -1215,27 +1242,13 @@ int ransac_set(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, hipSt
 int match_table(const caelo_pair_table &pt, hipStream_t s) {
     CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
     CAELO_REQUIRE((((uintptr_t)pt.rows) & 15u) == 0, "rows not 16-byte aligned");
-    const int64_t kpad = ms_pad16(CAELO_MAX_KEYPTS);
-    k_match_prep_tab<<<dim3((unsigned)((kpad / 16 + 3) / 4), 1, pt.n), 256, 0, s>>>(pt, 64, CAELO_MAX_KEYPTS, 60, kpad, 1);
-    CAELO_LAUNCH_CHECK();
-    k_match_screen_tab<<<dim3((unsigned)((CAELO_MAX_KEYPTS + 16 * MS_CT - 1) / (16 * MS_CT)), 1, pt.n), 64 * MS_NW, 0, s>>>(pt, 64, CAELO_MAX_KEYPTS, 64,
-                                                                                                                     CAELO_MAX_KEYPTS, 60, kpad, 1);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return screen_launch(pt, true, 64, CAELO_MAX_KEYPTS, 64, CAELO_MAX_KEYPTS, 60, s);
 }
 
 int ransac_table(const caelo_pair_table &pt, hipStream_t s) {
     CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
-    k_ransac_hyp_tab<<<dim3((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * RH_PER_WAVE - 1) / (RE_WAVES * RH_PER_WAVE), 1, pt.n), 64 * RE_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
-    CAELO_LAUNCH_CHECK();
-    if (pt.cert) {   // bounds for the 0.8 / 1.6 m levels of the pairs whose first level failed
-        k_ransac_hyp_up_tab<<<dim3(RU_BLOCKS, 2, pt.n), 64 * RE_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
-        CAELO_LAUNCH_CHECK();
-    }
-    if (pt.cert && pt.cert_only) return CAELO_OK;   // the host half decides every pair: no finishing kernel
-    k_ransac_finish_tab<<<dim3(1, 1, pt.n), 64 * RF_WAVES, 0, s>>>(pt, 64, 64, CAELO_MAX_KEYPTS);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, pt.cert != nullptr, pt.cert && pt.cert_only, s, k_ransac_hyp_tab, k_ransac_hyp_up_tab,
+                         k_ransac_finish_tab);
 }
 
 // ------------------------------------------------------------------------------------------------
