@@ -458,7 +458,14 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     if (x >= 8 && x < CAELO_NET_W - 8 && !(x >= 56 && x < 64) && ((win >> 12) & 1u)) {  // :163-167 (incl. the 56..63 quirk), :210-213
         const float4 pa = sR[2 * c], pb = sR[2 * c + 1];
         const int cnt = __popc(win & ~(1u << 12));
-        best = __builtin_inff();
+        // The window's own entry is one of the 25 norms cp.min runs over (SphericalRing.py:149-159,:179): centre - centre is 0, + 1e10
+        // for the cleared self mask, never the minimum -- unless a channel of the centre is +-inf or NaN: inf - inf and NaN - NaN are
+        // NaN, the score is NaN and the pixel no candidate.  A NaN centre gets there through its 24 differences as well; an inf
+        // centre only here (its differences are inf, which alone would make it the best-scoring pixel of the frame).  A class
+        // test on the eight values already in registers, no 25th distance: `best` starts as NaN and stays NaN below.
+        const bool self_finite = __builtin_isfinite(pa.x) && __builtin_isfinite(pa.y) && __builtin_isfinite(pa.z) && __builtin_isfinite(pa.w) &&
+                                 __builtin_isfinite(pb.x) && __builtin_isfinite(pb.y) && __builtin_isfinite(pb.z) && __builtin_isfinite(pb.w);
+        best = self_finite ? __builtin_inff() : __builtin_nanf("");
 #pragma unroll
         for (int oy = -2; oy <= 2; ++oy) {
             // one row of the window at a time: its five vectors are requested together (ten 16-byte reads in flight), unconditionally;

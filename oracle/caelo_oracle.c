@@ -157,6 +157,10 @@ ORC_EXPORT int orc_keypoints(const float *ring, int ring_w, int ring_c, const in
             int cnt = 0;
             float best = 0.0f;
             int have = 0;
+            /* :149-159,:179 the window's own entry (index 12) is part of cp.min: centre - centre is 0 (+ 1e10, never the minimum) unless
+             * a channel of the centre is not finite -- inf - inf and NaN - NaN are NaN, and the score is NaN: no candidate */
+            for (int c = 0; c < 8; ++c)
+                if (!isfinite(rp[c])) { best = NAN; have = 1; }
             for (int oy = -2; oy <= 2; ++oy) {
                 for (int ox = -2; ox <= 2; ++ox) {
                     if (oy == 0 && ox == 0) continue; /* :170 */
