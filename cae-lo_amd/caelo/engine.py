@@ -1040,6 +1040,38 @@ class Engine:
                                           _ptr(status), self.stream))
         return bits, flags
 
+    def patches_many(self, vmaps, pts, n_keys=None, statuses=None):
+        """caelo_patches_many: ``patches`` for up to eight maps / key point sets [K,3] of one length K, the kd redo of all of them
+        behind one launch of each kd kernel -> ([bits [K,3,64] int64], [flags [K,3] uint8], [status [1] int32]) per map."""
+        n, k = len(vmaps), pts[0].shape[0]
+        assert 1 <= n <= 8 and len(pts) == n
+        for p in pts:
+            assert p.dtype == torch.float32 and p.dim() == 2 and p.shape == (k, 3) and p.is_contiguous()
+        n_keys = [None] * n if n_keys is None else n_keys
+        statuses = [self.zeros((1,), torch.int32) for _ in range(n)] if statuses is None else statuses
+        bits = [self.empty((k, 3, 64), torch.int64) for _ in range(n)]
+        flags = [self.empty((k, 3), torch.uint8) for _ in range(n)]
+        arr = lambda xs: (C.c_void_p * n)(*[x.data_ptr() if x is not None else None for x in xs])
+        _ffi.check(self.lib.caelo_patches_many(self.ctx, n, (C.c_void_p * n)(*[m.h for m in vmaps]), arr(pts), k, arr(n_keys), arr(bits),
+                                               arr(flags), arr(statuses), self.stream))
+        return bits, flags, statuses
+
+    def kd_dump(self, vmap, scale):
+        """caelo_voxmap_kd_dump (diagnostic; waits for the stream): the kd-tree of one scale as the last ``patches`` on the map left it
+        -> dict(state [32] int32, n, n_nodes, top_levels, idx [n] int32, start / end [n_nodes] int32, lo / hi [n_nodes,3] int16) of NumPy arrays.
+        The tree is valid only where ``state[4 + scale] == 1`` (csrc/kdorder.hip)."""
+        state = np.zeros(32, np.int32)
+        counts = np.zeros(3, np.int64)
+        idx_cap, node_cap = int(vmap.max_points), 16384
+        idx = np.zeros(idx_cap, np.int32)
+        start, end = np.zeros(node_cap, np.int32), np.zeros(node_cap, np.int32)
+        lo, hi = np.zeros((node_cap, 3), np.int16), np.zeros((node_cap, 3), np.int16)
+        _ffi.check(self.lib.caelo_voxmap_kd_dump(self.ctx, vmap.h, int(scale), _hptr(state), _hptr(idx), idx_cap, _hptr(start), _hptr(end),
+                                                 _hptr(lo), _hptr(hi), node_cap, _hptr(counts), self.stream))
+        n, nn = int(counts[0]), int(counts[1])
+        return dict(state=state, n=n, n_nodes=nn, top_levels=int(counts[2]), idx=idx[:n].copy(), start=start[:nn].copy(), end=end[:nn].copy(), lo=lo[:nn].copy(),
+                    hi=hi[:nn].copy())
+
     def unpack_patches(self, bits):
         n = bits.numel() // 64
         dense = self.empty((n, 16, 16, 16, 1), torch.float32)

@@ -754,6 +754,40 @@ int kd_store_lists(caelo_voxmap *m, const int16_t *const lists[3], const int64_t
     return CAELO_OK;
 }
 
+// caelo_voxmap_kd_dump: the tree of one scale as the build left it, for tests and diagnostics (host buffers; waits for the stream)
+CAELO_API int caelo_voxmap_kd_dump(caelo_ctx *c, const caelo_voxmap *m, int scale, int32_t *state, int32_t *idx, int64_t idx_capacity,
+                                   int32_t *start, int32_t *end, int16_t *lo, int16_t *hi, int64_t node_capacity, int64_t *counts,
+                                   void *stream) {
+    CAELO_REQUIRE(c && m && state && idx && start && end && lo && hi && counts, "caelo_voxmap_kd_dump: null argument");
+    CAELO_REQUIRE(scale >= 0 && scale < 3, "caelo_voxmap_kd_dump: scale must be 0, 1 or 2");
+    CAELO_REQUIRE(m->kd && m->kd_lists, "caelo_voxmap_kd_dump: the map holds no ordered voxel lists (caelo_voxmap_from_lists, caelo_voxmap_order)");
+    hipStream_t s = caelo_stream(stream);
+    const caelo_kd *kd = m->kd;
+    CAELO_HIP(hipMemcpyAsync(state, kd->state, 32 * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    CAELO_HIP(hipStreamSynchronize(s));
+    const int64_t n = state[16 + scale];
+    const int n_levels = kd_levels_of(n);
+    const int64_t n_nodes = n_levels > 0 && n_levels <= 14 ? ((int64_t)1 << n_levels) - 1 : 0;   // (14 levels fill the node table)
+    counts[0] = n; counts[1] = n_nodes;
+    counts[2] = n_nodes > 0 ? min(kd_top_levels_of(n), n_levels) : 0;   // levels k_kd_build_top runs before the subtrees take over
+    if (n < 0 || n > kd->cap) { caelo_set_error("caelo_voxmap_kd_dump: the list length word holds %lld", (long long)n); return CAELO_ERR_ARG; }
+    if (n > idx_capacity || n_nodes > node_capacity) {
+        caelo_set_error("caelo_voxmap_kd_dump: %lld voxels / %lld nodes exceed the buffers (%lld / %lld)", (long long)n, (long long)n_nodes,
+                        (long long)idx_capacity, (long long)node_capacity);
+        return CAELO_ERR_CAPACITY;
+    }
+    const caelo_kd_scale &T = kd->s[scale];
+    if (n > 0) CAELO_HIP(hipMemcpyAsync(idx, T.idx, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (n_nodes > 0) {
+        CAELO_HIP(hipMemcpyAsync(start, T.start, (size_t)n_nodes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CAELO_HIP(hipMemcpyAsync(end, T.end, (size_t)n_nodes * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+        CAELO_HIP(hipMemcpyAsync(lo, T.lo, (size_t)n_nodes * 3 * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+        CAELO_HIP(hipMemcpyAsync(hi, T.hi, (size_t)n_nodes * 3 * sizeof(int16_t), hipMemcpyDeviceToHost, s));
+    }
+    CAELO_HIP(hipStreamSynchronize(s));
+    return CAELO_OK;
+}
+
 // caelo_voxmap_order: the lists are written on the device (export.hip) straight into the tree's storage -- vox_out[scale] [cap][3],
 // n_out [3] (device words the build reads); every word of the state is wiped first
 int kd_begin_device_lists(caelo_voxmap *m, int16_t *vox_out[3], int32_t **n_out, hipStream_t s) {

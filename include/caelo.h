@@ -253,6 +253,18 @@ int caelo_patches(caelo_ctx *ctx, const caelo_voxmap *map, const float *pts, int
  * millisecond or two of dependent quickselect passes, Voxel.py:195-196 in scikit-learn's order) is paid once per set, not per frame. */
 int caelo_patches_many(caelo_ctx *ctx, int n, const caelo_voxmap *const *maps, const float *const *pts, int64_t k_max,
                        const int32_t *const *n_key, uint64_t *const *bits, uint8_t *const *flags, int32_t *const *status, void *stream);
+/* The kd-tree of one scale as the last caelo_patches / caelo_patches_many on this map left it (csrc/kdorder.hip), read back into
+ * HOST buffers; waits for `stream`.  Diagnostic / test access, no hot path touches it (additive; the ABI version stays 6).
+ *   state [32] i32   the map's kd words: [0..2] tie-split patches queued per scale | [4..6] 0 no tree, 1 built, 2 not built (the build
+ *                    gave up on its work budget, or too many nodes: the canonical rule stays) | [16..18] list lengths
+ *   idx [n] i32      the tree's index array (positions in the list)          start, end [n_nodes] i32   node i owns idx[start, end)
+ *   lo, hi [n_nodes][3] i16   bounding boxes                                 counts [3] i64 = n, n_nodes (2^n_levels - 1; 0 below 994),
+ *                    the number of upper levels the build runs in one workgroup before each subtree gets its own
+ * What idx and the node tables hold is meaningful only where state[4 + scale] == 1.  CAELO_ERR_ARG for a map without ordered lists
+ * (caelo_voxmap_from_lists, caelo_voxmap_order), CAELO_ERR_CAPACITY when n > idx_capacity or n_nodes > node_capacity (counts is
+ * written, nothing else is copied). */
+int caelo_voxmap_kd_dump(caelo_ctx *ctx, const caelo_voxmap *map, int scale, int32_t *state, int32_t *idx, int64_t idx_capacity,
+                         int32_t *start, int32_t *end, int16_t *lo, int16_t *hi, int64_t node_capacity, int64_t *counts, void *stream);
 /* dense <-> packed conversion for callers that want the reference's [K,16,16,16,1] f32 arrays */
 int caelo_unpack_patches(caelo_ctx *ctx, const uint64_t *bits, int64_t n_patches, float *dense, void *stream);
 int caelo_pack_patches(caelo_ctx *ctx, const float *dense, int64_t n_patches, uint64_t *bits, void *stream);

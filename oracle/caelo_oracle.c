@@ -336,6 +336,8 @@ typedef struct {
     uint8_t *leaf;            /* [n_nodes] */
     int16_t *lo, *hi;         /* [n_nodes][3] bounding boxes */
     const int16_t *vox;       /* [n][3], not owned */
+    double work_max;          /* largest quickselect work of a node / the node's length (orc_kdtree_work) */
+    int over_budget;          /* a node's quickselect ran past the device build's budget */
 } orc_kdtree_t;
 
 static void kd_build_rec(orc_kdtree_t *t, int node, int64_t s, int64_t e) {
@@ -357,15 +359,19 @@ static void kd_build_rec(orc_kdtree_t *t, int node, int64_t s, int64_t e) {
     for (int j = 0; j < 3; ++j) if (hi[j] - lo[j] > spread) { spread = hi[j] - lo[j]; jmax = j; }
     const int64_t nmid = m / 2;
     int64_t left = 0, right = m - 1;
+    int64_t work = 0;   /* the device build's unit (csrc/kdorder.hip): elements in front of the pivot + 1 per partition pass */
     for (;;) {
         int64_t mid = left;
         const int16_t d2 = X[3 * (int64_t)a[right] + jmax];
+        work += right - left + 1;
         for (int64_t i = left; i < right; ++i)
             if (X[3 * (int64_t)a[i] + jmax] < d2) { const int32_t tmp = a[i]; a[i] = a[mid]; a[mid] = tmp; ++mid; }
         { const int32_t tmp = a[mid]; a[mid] = a[right]; a[right] = tmp; }
         if (mid == nmid) break;
+        if (work > 4096 * m + 65536) t->over_budget = 1;   /* (the device gives up after a pass that did not end the selection) */
         if (mid < nmid) left = mid + 1; else right = mid - 1;
     }
+    if ((double)work / (double)m > t->work_max) t->work_max = (double)work / (double)m;
     kd_build_rec(t, 2 * node + 1, s, s + nmid);
     kd_build_rec(t, 2 * node + 2, s + nmid, e);
 }
@@ -441,6 +447,16 @@ ORC_EXPORT int orc_kdtree_idx(const int16_t *vox, int64_t n, int32_t *idx_out) {
     const int nn = t->n_nodes;
     kd_free(t);
     return nn;
+}
+/* the device build's work budget (csrc/kdorder.hip: a node of m voxels may spend 4096 * m + 65536, a partition pass costs the
+ * elements in front of its pivot + 1), restated serially: the largest work of a node in units of its length, and whether any node
+ * runs past its budget (the device then abandons the tree).  Used only to choose and check test lists. */
+ORC_EXPORT int orc_kdtree_work(const int16_t *vox, int64_t n, double *passes_worth) {
+    orc_kdtree_t *t = kd_build(vox, n);
+    *passes_worth = t->work_max;
+    const int over = t->over_budget;
+    kd_free(t);
+    return over;
 }
 ORC_EXPORT void orc_kdtree_query(const int16_t *vox, int64_t n, const int32_t *q, int64_t nq, int32_t *out) {
     orc_kdtree_t *t = kd_build(vox, n);

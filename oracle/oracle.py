@@ -405,6 +405,16 @@ def kdtree_idx(AllVoxels):
     return idx, int(n_nodes)
 
 
+def kdtree_work(AllVoxels):
+    """The device build's work budget on this list (csrc/kdorder.hip), restated serially: (the largest quickselect work of a node in
+    passes' worth of its length -- the budget is 4096 of them plus 65536 elements --, whether any node runs past it: the device
+    would abandon the tree).  Only chooses and checks test lists."""
+    vox = np.ascontiguousarray(AllVoxels, dtype=np.int16)
+    w = C.c_double(0.0)
+    over = lib().orc_kdtree_work(_p(vox), C.c_int64(vox.shape[0]), C.byref(w))
+    return float(w.value), bool(over)
+
+
 def kdtree_query(AllVoxels, KeyVoxels):
     """kneighbors(KeyVoxels, 496) of that tree as SETS of list indices: [Q, 496] int32 (heap order, not sorted)."""
     vox = np.ascontiguousarray(AllVoxels, dtype=np.int16)
