@@ -194,6 +194,24 @@ class H5File:
             out[name] = self._decode(dtype, shape, d[off:])
         return out
 
+    def dataset_info(self, path):
+        """-> (shape, (class, size, bits0) of the datatype, file offset or None when no storage is allocated, nbytes) of a
+        contiguous dataset."""
+        obj = self._resolve(path)
+        shape = dtype = layout = None
+        for t, d in obj.msgs:
+            if t == 0x01:
+                shape = self._dataspace(d)
+            elif t == 0x03:
+                dtype = self._datatype(d)
+            elif t == 0x08:
+                if d[0] != 3 or d[1] != 1:
+                    raise H5Error("only contiguous (layout v3) datasets are supported")
+                layout = struct.unpack_from("<QQ", d, 2)
+        if shape is None or dtype is None or layout is None:
+            raise H5Error("%s is not a dataset" % path)
+        return shape, dtype, (None if layout[0] == _UNDEF else layout[0] + self.base), layout[1]
+
     def dataset(self, path):
         obj = self._resolve(path)
         shape = dtype = layout = None
@@ -213,3 +231,16 @@ class H5File:
             return np.zeros(shape, dtype="<f%d" % dtype[1])
         addr += self.base
         return self._decode(dtype, shape, self.buf[addr:addr + size])
+
+
+def dataset_span(path, name=None):
+    """Where a contiguous little-endian float32 dataset's values lie in the file: ``dataset_span(path, name)`` (or an open ``H5File``
+    as ``path``) -> (offset, nbytes).  H5Error for any other datatype, for a layout that is not contiguous, for a dataset without
+    allocated storage or one whose bytes do not match its shape -- what a writer that overwrites values in place has to refuse."""
+    h = path if isinstance(path, H5File) else H5File(path)
+    shape, (cls, size, bits0), off, nbytes = h.dataset_info(name)
+    if cls != 1 or size != 4 or bits0 & 1:
+        raise H5Error("%s is not little-endian float32" % name)
+    if off is None or nbytes != 4 * int(np.prod(shape)) or off + nbytes > len(h.buf):
+        raise H5Error("%s has no contiguous storage of its shape %s" % (name, (shape,)))
+    return off, nbytes

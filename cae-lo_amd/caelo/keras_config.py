@@ -230,3 +230,74 @@ def read_model(path):
         raise ValueError("%s: weight shapes %s do not match the %s architecture" % (path, [w.shape for w in ws], kind))
     return kind, ws, activations
 
+
+
+def autoencoder_datasets(h):
+    """-> ([(dataset path, (offset, nbytes), shape)] of the encoder half, the same of the decoder half) of an autoencoder ``H5File``, in
+    ``read_autoencoder``'s order; a half stored with empty ``weight_names`` gives an empty list."""
+    from .h5lite import dataset_span
+    lys = layers(h)
+    cut, _ = encoder_model(lys)
+    decoder_model(lys)
+    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
+    halves = []
+    for keep in ({cfg["name"] for _, cfg in lys[:cut]}, {cfg["name"] for _, cfg in lys[cut:]}):
+        sets = []
+        for ln in names:
+            if ln in keep:
+                for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+                    p = "/model_weights/%s/%s" % (ln, wn.decode())
+                    sets.append((p, dataset_span(h, p), tuple(h.dataset_info(p)[0])))
+        halves.append(sets)
+    return halves
+
+
+def write_autoencoder_like(template_h5, out_h5, ews, dws, activations=None):
+    """Write trained weights as a Keras file without an HDF5 writer: ``out_h5`` is a byte copy of ``template_h5`` with the values of its
+    weight datasets overwritten in place -- the 10 encoder arrays ``ews`` and the 10 decoder arrays ``dws`` (Keras shapes or flat; the
+    20 tensors of the network).  Nothing else in the file changes: layer names, ``model_config`` -- so the activations are the
+    template's, and a trainer's activation set must equal its template's -- and ``training_config``; the ``optimizer_weights`` group
+    of the template, if it has one, stays as it is and is STALE for the new weights (Keras reads it only to resume training).  A
+    template that was cut down to one half (empty ``weight_names`` on the other: the test fixtures) takes that half only, and the other
+    argument may be None.  Refused with ValueError BEFORE anything is written: a dataset that is not contiguous little-endian float32
+    with allocated storage, a dataset or an array of another shape, a half given for which the template has no datasets, and --
+    ``activations`` = ((H, C), (hidden, out)) of the model the weights were trained as -- a template whose ``model_config`` says
+    otherwise."""
+    from .h5lite import H5Error
+    h = H5File(template_h5)
+    try:
+        enc, dec = autoencoder_datasets(h)
+    except H5Error as e:
+        raise ValueError("%s: %s" % (template_h5, e))
+    if activations is not None:
+        lys = layers(h)
+        have = (encoder_model(lys)[1], decoder_model(lys)[1])
+        if tuple(tuple(a) for a in activations) != have:
+            raise ValueError("%s: the template's activations are %r, the weights were trained with %r" % (template_h5, have, activations))
+    from .engine import DECODER_SHAPES, ENCODER_SHAPES
+    jobs = []
+    for what, sets, ws, shapes in (("encoder", enc, ews, ENCODER_SHAPES), ("decoder", dec, dws, DECODER_SHAPES)):
+        if not sets and ws is None:
+            continue
+        if not sets or ws is None:
+            raise ValueError("%s: the template holds %s %s datasets and %s given" % (template_h5, "no" if not sets else len(sets), what,
+                                                                                      "no arrays are" if ws is None else "arrays are"))
+        # Keras stores a Conv3D kernel [3,3,3,cin,cout]; ENCODER_SHAPES / DECODER_SHAPES name those shapes
+        if [s for _, _, s in sets] != [tuple(s) for s in shapes]:
+            raise ValueError("%s: %s dataset shapes %s, the architecture has %s" % (template_h5, what, [s for _, _, s in sets], list(shapes)))
+        if len(ws) != len(shapes):
+            raise ValueError("%s weights: %d arrays wanted, got %d" % (what, len(shapes), len(ws)))
+        for (p, (off, nbytes), s), w in zip(sets, ws):
+            a = np.ascontiguousarray(w, dtype="<f4")
+            if a.shape != s and a.shape != (int(np.prod(s)),):
+                raise ValueError("%s: array of shape %s for a dataset of shape %s" % (p, a.shape, s))
+            jobs.append((off, a.tobytes()))
+            assert len(jobs[-1][1]) == nbytes
+    if not jobs:
+        raise ValueError("%s holds no weight datasets" % template_h5)
+    buf = bytearray(h.buf)
+    for off, raw in jobs:
+        buf[off:off + len(raw)] = raw
+    with open(out_h5, "wb") as f:
+        f.write(bytes(buf))
+    return out_h5

@@ -179,6 +179,32 @@ int caelo_decode_ws_layout(int64_t n_patches, int64_t out[2]);
 int caelo_decode(caelo_ctx *ctx, const float *codes, int64_t n_patches, int group, int ld, const uint64_t *target_bits, double threshold,
                  float *prob, uint64_t *rebuilt, float *loss, int32_t *counts, void *ws, void *stream);
 
+/* Training the voxel-patch autoencoder (AE4VoxelPatch.py:186-213): loss and gradient of the whole network, and Keras 2.3's Adadelta.
+ * The weights are plain Keras-layout f32 in ONE flat device buffer of 864 741 floats: the 20 tensors conv3d_1 .. dense_2, dense_3 ..
+ * conv3d_6, kernel then bias per layer (caelo_train_param_layout: out[t] = {offset, count} in floats).  Nothing here reads or
+ * changes the context's inference models.  f32 operands and accumulation (f32-input matrix instructions), no floating-point atomics.
+ * caelo_autoencoder_grad: bits [n][64] u64 (the packed patch layout) -> loss[0] (device f32) = the mean over patches of the mean over
+ *   the 4096 voxels of Keras's binary_crossentropy (caelo_decode's loss), and grads = dloss / dparams in params' layout (NULL: forward
+ *   only; the loss bits are those of the full call).  enc_hidden / dec_hidden in {CAELO_ACT_TANH, CAELO_ACT_RELU}, enc_code in
+ *   {CAELO_ACT_TANH, CAELO_ACT_LINEAR}.  relu' = (y > 0), tanh' = 1 - y^2 from the stored output; a pooling window's gradient goes to
+ *   its first maximum in ascending (dx, dy, dz) order, dz fastest; dloss/dz = (sigmoid(z) - y) / (4096 n) where |z| <= logit(1 - 1e-7),
+ *   0 beyond.  The batch is walked in chunks of `chunk` patches, whose partial gradients are added in ascending order: the same
+ *   (n, chunk) gives the same bits in every call; the loss bits depend on n alone.  ws: caelo_train_ws_bytes(chunk) bytes, no
+ *   initialisation needed, one per stream.  CAELO_ERR_ARG before any launch: n < 0, chunk outside [1, 8192], a null pointer, an
+ *   activation code outside the sets above.  n = 0 writes loss 0 and zero gradients.
+ * caelo_train_ws_layout (test aid): byte offsets in ws of what the LAST chunk left -- out[0] dloss/dz [chunk][4096], out[1]
+ *   dloss/dcode [chunk][20] (the activated code), out[2] dloss/dP1 [chunk][8^3 x 8] (the first pooling's output).
+ * caelo_adadelta_step: a = rho a + (1 - rho) g^2; u = g sqrt(d + eps) / sqrt(a + eps); p -= lr u; d = rho d + (1 - rho) u^2 over
+ *   `count` floats, every operation rounded on its own in f32, sqrt and the quotient correctly rounded (Keras 2.3's defaults: lr 1,
+ *   rho 0.95, eps 1e-7). */
+int caelo_train_param_layout(int64_t out[20][2]);
+int64_t caelo_train_ws_bytes(int64_t chunk);
+int caelo_train_ws_layout(int64_t chunk, int64_t out[3]);
+int caelo_autoencoder_grad(caelo_ctx *ctx, const float *params, int enc_hidden, int enc_code, int dec_hidden, const uint64_t *bits, int64_t n,
+                           int64_t chunk, float *grads, float *loss, void *ws, void *stream);
+int caelo_adadelta_step(caelo_ctx *ctx, float *params, const float *grads, float *acc_g, float *acc_d, int64_t count, float lr, float rho,
+                        float eps, void *stream);
+
 /* CorrectPC  (Transformations.py:28-39; BatchPreprocess.py:70-88 BatchCorrectPC): every point rotated by calib_angle_deg about the
  * axis p x z^, the HDL-64E's vertical-angle calibration of the KITTI scans.  pc, out [n][stride] f32 (device), stride 3 or 4; with
  * stride 4 the fourth column (intensity) is copied bit for bit.  out may not overlap pc; n = 0 does nothing; a non-finite angle is
