@@ -96,6 +96,11 @@ SIGNATURES = [
     ("caelo_train_ws_layout", c_int, [c_i64, c_vp]),
     ("caelo_autoencoder_grad", c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_adadelta_step", c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, c_vp]),
+    ("caelo_ring_train_param_layout", c_int, [c_vp]),
+    ("caelo_ring_train_ws_bytes", c_i64, [c_int, c_int, c_i64]),
+    ("caelo_ring_train_ws_layout", c_int, [c_int, c_int, c_i64, c_vp]),
+    ("caelo_ring_autoencoder_grad", c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_adam_step", c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, C.c_float, C.c_float, C.c_float, C.c_float, c_vp]),
     ("caelo_correct_pc", c_int, [c_vp, c_vp, c_i64, c_int, C.c_double, c_vp, c_vp]),
     ("caelo_set_calib_angle", c_int, [c_vp, C.c_double]),
     ("caelo_get_calib_angle", C.c_double, [c_vp]),

@@ -301,3 +301,122 @@ def write_autoencoder_like(template_h5, out_h5, ews, dws, activations=None):
     with open(out_h5, "wb") as f:
         f.write(bytes(buf))
     return out_h5
+
+
+# ---- the spherical-ring autoencoder (AE4SphericalRingPC.py:129-144), whose first two layers are the response layer -----------------
+_C2 = dict(_CONV, strides=[1, 1], dilation_rate=[1, 1], activation="relu")
+_POOL2 = dict(pool_size=[2, 2], strides=[2, 2], padding="same", data_format="channels_last")
+_UP2 = dict(size=[2, 2], data_format="channels_last")
+RING_AE_SPEC = [
+    ("InputLayer", dict(batch_input_shape=[None, 64, 1792, 3])),    # (or [None, None, None, 3]: the network is fully convolutional)
+    ("Conv2D", dict(_C2, filters=32, kernel_size=[3, 3])),
+    ("Conv2D", dict(_C2, filters=8, kernel_size=[1, 1])),
+    ("MaxPooling2D", _POOL2),
+    ("Conv2D", dict(_C2, filters=16, kernel_size=[3, 3])),
+    ("MaxPooling2D", _POOL2),
+    ("Conv2D", dict(_C2, filters=16, kernel_size=[3, 3])),
+    ("UpSampling2D", _UP2),
+    ("Conv2D", dict(_C2, filters=8, kernel_size=[3, 3])),
+    ("UpSampling2D", _UP2),
+    ("Conv2D", dict(_C2, filters=3, kernel_size=[1, 1], activation="linear")),
+]
+RING_AE_INPUT_SHAPES = ([None, 64, 1792, 3], [None, None, None, 3])   # what the shipped file records; what its script's Input() says
+RING_AE_SHAPES = [(3, 3, 3, 32), (32,), (1, 1, 32, 8), (8,), (3, 3, 8, 16), (16,), (3, 3, 16, 16), (16,), (3, 3, 16, 8), (8,), (1, 1, 8, 3), (3,)]
+
+
+def check_ring_autoencoder(lys):
+    """Raise ValueError unless the stack is exactly ``RING_AE_SPEC``, compared field by field as ``check`` does."""
+    if [c for c, _ in lys] != [c for c, _ in RING_AE_SPEC]:
+        raise ValueError("unsupported ring autoencoder layer stack %s (the training kernels implement %s)"
+                         % ([c for c, _ in lys], [c for c, _ in RING_AE_SPEC]))
+    for (cls, cfg), (_, want) in zip(lys, RING_AE_SPEC):
+        for key, val in want.items():
+            got = cfg.get(key, "channels_last" if key == "data_format" else None)
+            ok = _norm(got) in RING_AE_INPUT_SHAPES if key == "batch_input_shape" else _norm(got) == _norm(val)
+            if not ok:
+                raise ValueError("unsupported ring autoencoder: %s(%s).%s = %r, the training kernels implement %r" % (cls, cfg.get("name"), key, got, val))
+        if cls == "UpSampling2D" and cfg.get("interpolation", "nearest") != "nearest":
+            raise ValueError("unsupported ring autoencoder: UpSampling2D(%s).interpolation = %r, the training kernels implement 'nearest'"
+                             % (cfg.get("name"), cfg.get("interpolation")))
+
+
+def _conv2d_datasets(h, lys, spec_shapes, what, path):
+    """-> [(dataset path, (offset, nbytes), shape)] of every weight of the stack's layers, in ``layer_names`` order; ValueError for
+    storage that is not contiguous little-endian float32 or for other shapes."""
+    from .h5lite import H5Error, dataset_span
+    keep = {cfg["name"] for _, cfg in lys}
+    sets = []
+    try:
+        for ln in [n.decode() for n in h.attrs("/model_weights")["layer_names"]]:
+            if ln in keep:
+                for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+                    p = "/model_weights/%s/%s" % (ln, wn.decode())
+                    sets.append((p, dataset_span(h, p), tuple(h.dataset_info(p)[0])))
+    except H5Error as e:
+        raise ValueError("%s: %s" % (path, e))
+    if [s for _, _, s in sets] != [tuple(s) for s in spec_shapes]:
+        raise ValueError("%s: %s dataset shapes %s, the architecture has %s" % (path, what, [s for _, _, s in sets], list(spec_shapes)))
+    return sets
+
+
+def read_ring_autoencoder(path):
+    """-> the 12 arrays (conv2d_1 .. conv2d_6, kernel then bias, Keras shapes ``RING_AE_SHAPES``) of an AE4SphericalRingPC.h5.  The
+    layer stack is compared field by field with ``RING_AE_SPEC`` before a weight is read; anything else -- the response-layer file,
+    an encoder, one changed field -- is a ValueError."""
+    h = H5File(path)
+    check_ring_autoencoder(layers(h))
+    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
+    ws = []
+    for ln in names:
+        for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+            ws.append(np.ascontiguousarray(h.dataset("/model_weights/%s/%s" % (ln, wn.decode())), np.float32))
+    if [w.shape for w in ws] != RING_AE_SHAPES:
+        raise ValueError("%s: weight shapes %s do not match the ring autoencoder's %s" % (path, [w.shape for w in ws], RING_AE_SHAPES))
+    return ws
+
+
+def _default_respond_h5():
+    import os
+    return os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "weights", "SphericalRingPCRespondLayer.h5")
+
+
+def write_ring_models_like(template_ae_h5, out_ae_h5, ws12, template_respond_h5=None, out_respond_h5=None):
+    """Write a trained ring autoencoder as the reference saves it (AE4SphericalRingPC.py:169-170) without an HDF5 writer: ``out_ae_h5`` is
+    a byte copy of ``template_ae_h5`` with its 12 weight datasets overwritten in place by ``ws12`` (Keras shapes or flat), and -- when
+    ``out_respond_h5`` is given -- ``out_respond_h5`` a byte copy of ``template_respond_h5`` (default: the shipped
+    weights/SphericalRingPCRespondLayer.h5) with its four datasets overwritten by the first four arrays.  Nothing else in either file
+    changes.  Refused with ValueError BEFORE anything is written: a template of another layer stack, a dataset that is not contiguous
+    little-endian float32 with allocated storage, a dataset or an array of another shape, another number of arrays."""
+    ws12 = list(ws12)
+    if len(ws12) != 12:
+        raise ValueError("ring autoencoder weights: 12 arrays wanted, got %d" % len(ws12))
+    todo = []
+    h = H5File(template_ae_h5)
+    lys = layers(h)
+    check_ring_autoencoder(lys)
+    todo.append((h, _conv2d_datasets(h, lys, RING_AE_SHAPES, "ring autoencoder", template_ae_h5), ws12, out_ae_h5))
+    if out_respond_h5 is not None:
+        template_respond_h5 = template_respond_h5 or _default_respond_h5()
+        hr = H5File(template_respond_h5)
+        lr = layers(hr)
+        if kind_of(lr) != "respond":
+            raise ValueError("%s is not a response-layer file" % template_respond_h5)
+        check(lr, "respond")
+        todo.append((hr, _conv2d_datasets(hr, lr, RING_AE_SHAPES[:4], "response layer", template_respond_h5), ws12[:4], out_respond_h5))
+    elif template_respond_h5 is not None:
+        raise ValueError("template_respond_h5 given without out_respond_h5")
+    files = []
+    for hh, sets, ws, out in todo:
+        buf = bytearray(hh.buf)
+        for (p, (off, nbytes), s), w in zip(sets, ws):
+            a = np.ascontiguousarray(w, dtype="<f4")
+            if a.shape != s and a.shape != (int(np.prod(s)),):
+                raise ValueError("%s: array of shape %s for a dataset of shape %s" % (p, a.shape, s))
+            raw = a.tobytes()
+            assert len(raw) == nbytes
+            buf[off:off + nbytes] = raw
+        files.append((out, bytes(buf)))
+    for out, raw in files:
+        with open(out, "wb") as f:
+            f.write(raw)
+    return out_ae_h5, out_respond_h5

@@ -205,6 +205,41 @@ int caelo_autoencoder_grad(caelo_ctx *ctx, const float *params, int enc_hidden, 
 int caelo_adadelta_step(caelo_ctx *ctx, float *params, const float *grads, float *acc_g, float *acc_d, int64_t count, float lr, float rho,
                         float eps, void *stream);
 
+/* Training the spherical-ring autoencoder (AE4SphericalRingPC.py:129-144), whose conv2d_1 / conv2d_2 are the response layer: loss and
+ * gradient of the whole network, and Keras 2.2.4's Adam.  Input [n][h][w][3] -> conv2d_1 3x3 3->32 relu, conv2d_2 1x1 32->8 relu,
+ * MaxPooling2D(2), conv2d_3 3x3 8->16 relu, MaxPooling2D(2), conv2d_4 3x3 16->16 relu, UpSampling2D(2), conv2d_5 3x3 16->8 relu,
+ * UpSampling2D(2), conv2d_6 1x1 8->3 linear; loss = mean_squared_error against the input.  The weights are plain Keras-layout f32 in
+ * ONE flat device buffer of 5 835 floats: 12 tensors, kernel then bias per layer (caelo_ring_train_param_layout: out[t] = {offset,
+ * count} in floats).  Nothing here reads or changes the context's inference models.  f32 operands and accumulation (f32-input matrix
+ * instructions), no floating-point atomics.
+ * caelo_ring_autoencoder_grad: pixel (i, y, x) channel c (0..2) is images[i img_stride + y row_stride + x pix_stride + c], strides in
+ *   floats, so a batch of projected rings [n][69][1800][5] is read in place at h = 64, w = 1792 (caelo_respond's in_w / in_c idea).
+ *   loss[0] (device f32) = the mean of (r - x)^2 over all 3 n h w elements, summed in double in a fixed tree and rounded once; grads =
+ *   dloss / dparams in params' layout (NULL: forward only; the loss bits are those of the full call); recon (optional) [n][h][w][3] =
+ *   autoencoder.predict.  relu' = (y > 0) from the stored output; a pooling window's gradient goes to its first maximum in ascending
+ *   (dy, dx) order, dx fastest (torch's max_pool2d rule; TensorFlow's is unpinned); UpSampling2D's adjoint sums the four children in
+ *   that order.  The batch is walked in chunks of `chunk` images whose partial weight gradients are added in ascending order: the same
+ *   (n, h, w, chunk) gives the same bits in every call; the loss bits depend on (n, h, w) alone.  ws: caelo_ring_train_ws_bytes(h, w,
+ *   chunk) bytes (0 for a shape that is refused), no initialisation needed, one per stream.  CAELO_ERR_ARG before any launch: n < 0; h
+ *   or w not a positive multiple of 4 (Keras would pad its 'same' poolings there; not built) or h w > 2^24; strides that make pixels
+ *   overlap (pix_stride < 3, row_stride < w pix_stride, img_stride < h row_stride); chunk outside [1, 4096]; a null params, loss, ws,
+ *   or images with n > 0.  n = 0 writes loss 0 and zero gradients.
+ * caelo_ring_train_ws_layout (test aid): byte offsets in ws of what the LAST chunk left -- out[0] A2 [chunk][h][w][8] (the response
+ *   layer's activated output), out[1] r [chunk][h][w][3], out[2] dloss/dP1 [chunk][h/2][w/2][8], out[3] dloss/dr [chunk][h][w][3].
+ * caelo_adam_step: m = beta1 m + (1 - beta1) g; v = beta2 v + (1 - beta2) g^2; p -= (lr_t m) / (sqrt(v) + eps) over `count` floats,
+ *   every operation rounded on its own in f32, sqrt and the quotient correctly rounded, no fused multiply-add.  lr_t = lr sqrt(1 -
+ *   beta2^t) / (1 - beta1^t) is the CALLER's, computed in float64 and rounded to f32 once (TensorFlow's f32 pow cannot be pinned).
+ *   Keras's eps sits OUTSIDE the bias correction: torch.optim.Adam divides by sqrt(v / (1 - beta2^t)) + eps instead, a different
+ *   update, so it is not the yardstick.  Keras 2.2.4's defaults: lr 0.001, beta1 0.9, beta2 0.999, eps 1e-7. */
+int caelo_ring_train_param_layout(int64_t out[12][2]);
+int64_t caelo_ring_train_ws_bytes(int h, int w, int64_t chunk);
+int caelo_ring_train_ws_layout(int h, int w, int64_t chunk, int64_t out[4]);
+int caelo_ring_autoencoder_grad(caelo_ctx *ctx, const float *params, const float *images, int64_t n, int h, int w, int64_t img_stride,
+                                int64_t row_stride, int64_t pix_stride, int64_t chunk, float *grads, float *loss, float *recon, void *ws,
+                                void *stream);
+int caelo_adam_step(caelo_ctx *ctx, float *params, const float *grads, float *m, float *v, int64_t count, float lr_t, float beta1, float beta2,
+                    float eps, void *stream);
+
 /* CorrectPC  (Transformations.py:28-39; BatchPreprocess.py:70-88 BatchCorrectPC): every point rotated by calib_angle_deg about the
  * axis p x z^, the HDL-64E's vertical-angle calibration of the KITTI scans.  pc, out [n][stride] f32 (device), stride 3 or 4; with
  * stride 4 the fourth column (intensity) is copied bit for bit.  out may not overlap pc; n = 0 does nothing; a non-finite angle is
