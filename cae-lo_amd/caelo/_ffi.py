@@ -34,6 +34,12 @@ class IcpResult(C.Structure):
                 ("iterations", c_i32), ("success", c_i32), ("n_inliers_pts", c_i32), ("n_inliers_planar", c_i32)]
 
 
+class IssParams(C.Structure):
+    """caelo_iss_params (include/caelo.h)."""
+    _fields_ = [("salient_radius", C.c_double), ("non_max_radius", C.c_double), ("gamma_21", C.c_double), ("gamma_32", C.c_double),
+                ("min_neighbors", c_i32), ("reserved", c_i32)]
+
+
 class FrameJob(C.Structure):
     """caelo_frame_job (include/caelo.h): one frame of the pipeline, device pointers as integers."""
     _fields_ = [("pc", c_vp), ("n", c_i64), ("dist_channels", c_i32), ("mode", c_i32), ("rows", c_vp),
@@ -54,6 +60,7 @@ ABI_VERSION = 6   # include/caelo.h CAELO_ABI_VERSION
 ACT_SIGMOID = 3   # include/caelo.h CAELO_ACT_SIGMOID: the decoder's output activation (caelo_set_decoder_model)
 ACT_TANH, ACT_RELU, ACT_LINEAR = 0, 1, 2   # include/caelo.h CAELO_ACT_*: the encoder's activations (caelo_set_encoder_model)
 KP_NN_MAX_K, KP_NN_MAX_THRESHOLDS = 65536, 16   # include/caelo.h CAELO_KP_NN_MAX_K / CAELO_KP_NN_MAX_THRESHOLDS (caelo_kp_nn_pairs)
+ISS_MAX_POINTS = 32768   # include/caelo.h CAELO_ISS_MAX_POINTS (caelo_iss_keypoints)
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 
 # the same layout as a NumPy record (a run's jobs are filled column-wise and handed over in one call)
@@ -183,6 +190,8 @@ SIGNATURES = [
     ("caelo_pipeline_expect", c_int, [c_vp, c_i64]),
     ("caelo_lane_faults", c_int, [c_vp, C.POINTER(c_i64)]),
     ("caelo_kp_nn_pairs", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
+    ("caelo_iss_ws_bytes", c_i64, [c_i64, c_int]),
+    ("caelo_iss_keypoints", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(IssParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     ("caelo_register_pairs_ws_bytes", c_i64, [c_i64]),
     ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes_dim", c_i64, [c_i64, c_int]),

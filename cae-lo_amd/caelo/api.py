@@ -15,6 +15,8 @@ tuples / dtypes, served by the HIP engine.
     keras.models.load_model (Match.py:313,324)  load_model(h5_path) -> object with .predict
     autoencoder.predict   (AE4VoxelPatch.py:256) load_autoencoder(h5_path).predict; ReconstructionLoss(autoencoder, PatchesList)
     Transformations.CorrectPC             :28   CorrectPC(PC, CalibAngle)
+    PCLKeypoint.keypointIss (PclKeyPts.py:95)   KeyPtsByISS(PC, salient_radius=2, non_max_radius=2, gamma_21=0.975, gamma_32=0.975,
+                                                            min_neighbors=5)
 
 Arguments may be NumPy arrays (results come back as NumPy, like the reference) or torch tensors on
 the GPU (results stay on the GPU).  Every array-level function runs on the GPU; there is no CPU
@@ -63,6 +65,20 @@ def CorrectPC(PC, CalibAngle):
         return PC.copy()
     e = default_engine()
     return e.correct_pc(torch.from_numpy(np.ascontiguousarray(PC)).to(e.device), CalibAngle).cpu().numpy()
+
+
+def KeyPtsByISS(PC, **params):
+    """PclKeyPts.py:95-101 (PCLKeypoint.keypointIss, a PCL binding the reference does not ship) -> the ISS key points [K,3] f32 of the
+    cloud PC [N, >=3], in scan order: the detector of DESIGN.md 9h on the device (caelo_iss_keypoints), PCL 1.8's ISSKeypoint3D without
+    border estimation as its model -- not its bits.  params: caelo.iss.DEFAULTS.  N <= 32768 (an all-pairs search: downsample and
+    subsample first, caelo.iss.voxel_downsample / subsample); ValueError beyond that, for a non-finite coordinate and for bad
+    parameters.  K may be 0."""
+    if PC.ndim != 2 or PC.shape[1] < 3:
+        raise ValueError("KeyPtsByISS: PC must have shape [N, >= 3] (got %s)" % (tuple(PC.shape),))
+    e = default_engine()
+    pts = _dev(PC, torch.float32)[:, 0:3].contiguous()
+    r = e.iss_keypoints(pts, **params)
+    return _out(pts[r.key_idx[:int(r.n_key.item())].long()], _is_np(PC))
 
 
 def ProjectPC2SphericalRing(PC):

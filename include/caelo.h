@@ -574,6 +574,37 @@ int caelo_icp(caelo_ctx *ctx, const float *pc0, int64_t n0, float *pc1, int64_t 
 int caelo_kp_nn_pairs(caelo_ctx *ctx, const double *pts, int64_t n_frames, int ld, const int32_t *n_key, const int32_t *pairs,
                       int64_t n_pairs, const double *thresholds, int n_thresholds, double *dist, int64_t *counts, void *stream);
 
+/* ---- ISS key points: the hand-crafted detector of the key point comparison (PclKeyPts.py:41-46, :92-103; csrc/iss.hip) -----------
+ * (additive; the ABI version stays 6.)  The reference calls PCLKeypoint.keypointIss, a PCL binding it does not ship; the model is
+ * PCL 1.8's ISSKeypoint3D with border estimation off, the definition is the one below, and bit parity with PCL is
+ * not claimed.  pts [n_frames][ld][3] f32 (device), n_pts [n_frames] i32 (device): frame f holds rows 0 .. n_pts[f]-1 (clamped to
+ * [0, ld] by the kernels; rows past it are never read into a decision).  All arithmetic is float64, every operation rounded on its
+ * own, sums in ascending point index:
+ *   neighbours   j is a neighbour of i at radius r <=> d2 < r * r (strict; r * r one rounded product; i is its own neighbour) with
+ *                d = double(P[j]) - double(P[i]), d2 = (dx*dx + dy*dy) + dz*dz
+ *   scatter      fewer than min_neighbors neighbours at salient_radius: saliency -1, eigenvalues 0; otherwise C_ab = sum_j d_a * d_b
+ *                over the neighbours (no division by their number), e1 >= e2 >= e3 its eigenvalues by cyclic Jacobi
+ *   candidate    saliency = e3 if e3 >= 0, e2 / e1 < gamma_21 and e3 / e2 < gamma_32 (IEEE divisions, a NaN compares false), else -1
+ *   key point    saliency > 0, at least min_neighbors neighbours at non_max_radius, none of them with a larger saliency (equal
+ *                saliencies both survive)
+ * Outputs (device): saliency [n_frames][ld] f64; eig [n_frames][ld][3] f64 = e1, e2, e3 (nullable); n_neigh [n_frames][ld] i32, the
+ * neighbours at salient_radius (nullable); key_idx [n_frames][ld] i32, the key points' indices in ascending order, -1 behind them;
+ * n_key [n_frames] i32.  Rows n_pts[f] .. ld-1 get saliency -1, eigenvalues 0 and 0 neighbours.  The same input gives the same bits
+ * on every run (no atomics); a NaN coordinate only makes comparisons false.  Three kernels, each one launch for all frames (the
+ * all-pairs passes in slices of 65 535 frames); ws: caelo_iss_ws_bytes(n_frames, ld) bytes, no initialisation, one per call in flight.
+ * prm is HOST memory.  Refused before any launch (CAELO_ERR_ARG): null arguments, ld outside [1, CAELO_ISS_MAX_POINTS], radii or gammas
+ * that are not finite and positive, min_neighbors < 1, a short workspace.  n_frames == 0 is a no-op.  The call does not synchronise.
+ * The work is n_pts^2 pair distances per frame and pass: 16 384 points (the reference's input_pc_num) are the intended size. */
+#define CAELO_ISS_MAX_POINTS 32768
+typedef struct { double salient_radius, non_max_radius, gamma_21, gamma_32; int32_t min_neighbors, reserved; } caelo_iss_params;
+int64_t caelo_iss_ws_bytes(int64_t n_frames, int ld);
+int caelo_iss_keypoints(caelo_ctx *ctx, const float *pts /*[n_frames][ld][3] device*/, int64_t n_frames, int ld,
+                        const int32_t *n_pts /*[n_frames] device*/, const caelo_iss_params *prm /*host*/,
+                        double *saliency /*[n_frames][ld]*/, double *eig /*[n_frames][ld][3] e1,e2,e3; nullable*/,
+                        int32_t *n_neigh /*[n_frames][ld] at salient_radius; nullable*/,
+                        int32_t *key_idx /*[n_frames][ld]*/, int32_t *n_key /*[n_frames]*/,
+                        void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- frame pipeline: batches of frames behind single launches, three stages on three HIP streams ------------------
  * Replaces the reference's per-frame driver loops (BatchPreprocess.py:88-140 extract loop, Match.py:296-353 /
  * PoseEstimation.py pair loop) for throughput.  `batch` consecutive frames share ONE launch of every kernel of the
