@@ -231,25 +231,43 @@ def read_model(path):
     return kind, ws, activations
 
 
+def _weight_paths(h, keep=None):
+    """The dataset path of every weight of the layers named in ``keep`` (None: all of them), in the file's ``layer_names`` x
+    ``weight_names`` order."""
+    for ln in [n.decode() for n in h.attrs("/model_weights")["layer_names"]]:
+        if keep is None or ln in keep:
+            for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
+                yield "/model_weights/%s/%s" % (ln, wn.decode())
+
+
+def _weight_datasets(h, keep):
+    """-> [(dataset path, (offset, nbytes), shape)] of ``_weight_paths(h, keep)``: what a writer needs.  H5Error for storage that is
+    not contiguous little-endian float32 (``dataset_span``); the writers turn it into their ValueError."""
+    from .h5lite import dataset_span
+    return [(p, dataset_span(h, p), tuple(h.dataset_info(p)[0])) for p in _weight_paths(h, keep)]
+
+
+def _patched(h, sets, ws):
+    """-> the bytes of ``h``'s file with the datasets ``sets`` overwritten by the arrays ``ws`` (their shapes or flat); ValueError for an
+    array of another shape.  Nothing is written."""
+    buf = bytearray(h.buf)
+    for (p, (off, nbytes), s), w in zip(sets, ws):
+        a = np.ascontiguousarray(w, dtype="<f4")
+        if a.shape != s and a.shape != (int(np.prod(s)),):
+            raise ValueError("%s: array of shape %s for a dataset of shape %s" % (p, a.shape, s))
+        raw = a.tobytes()
+        assert len(raw) == nbytes
+        buf[off:off + nbytes] = raw
+    return bytes(buf)
+
 
 def autoencoder_datasets(h):
     """-> ([(dataset path, (offset, nbytes), shape)] of the encoder half, the same of the decoder half) of an autoencoder ``H5File``, in
     ``read_autoencoder``'s order; a half stored with empty ``weight_names`` gives an empty list."""
-    from .h5lite import dataset_span
     lys = layers(h)
     cut, _ = encoder_model(lys)
     decoder_model(lys)
-    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
-    halves = []
-    for keep in ({cfg["name"] for _, cfg in lys[:cut]}, {cfg["name"] for _, cfg in lys[cut:]}):
-        sets = []
-        for ln in names:
-            if ln in keep:
-                for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
-                    p = "/model_weights/%s/%s" % (ln, wn.decode())
-                    sets.append((p, dataset_span(h, p), tuple(h.dataset_info(p)[0])))
-        halves.append(sets)
-    return halves
+    return [_weight_datasets(h, {cfg["name"] for _, cfg in half}) for half in (lys[:cut], lys[cut:])]
 
 
 def write_autoencoder_like(template_h5, out_h5, ews, dws, activations=None):
@@ -275,7 +293,7 @@ def write_autoencoder_like(template_h5, out_h5, ews, dws, activations=None):
         if tuple(tuple(a) for a in activations) != have:
             raise ValueError("%s: the template's activations are %r, the weights were trained with %r" % (template_h5, have, activations))
     from .engine import DECODER_SHAPES, ENCODER_SHAPES
-    jobs = []
+    all_sets, all_ws = [], []
     for what, sets, ws, shapes in (("encoder", enc, ews, ENCODER_SHAPES), ("decoder", dec, dws, DECODER_SHAPES)):
         if not sets and ws is None:
             continue
@@ -287,19 +305,13 @@ def write_autoencoder_like(template_h5, out_h5, ews, dws, activations=None):
             raise ValueError("%s: %s dataset shapes %s, the architecture has %s" % (template_h5, what, [s for _, _, s in sets], list(shapes)))
         if len(ws) != len(shapes):
             raise ValueError("%s weights: %d arrays wanted, got %d" % (what, len(shapes), len(ws)))
-        for (p, (off, nbytes), s), w in zip(sets, ws):
-            a = np.ascontiguousarray(w, dtype="<f4")
-            if a.shape != s and a.shape != (int(np.prod(s)),):
-                raise ValueError("%s: array of shape %s for a dataset of shape %s" % (p, a.shape, s))
-            jobs.append((off, a.tobytes()))
-            assert len(jobs[-1][1]) == nbytes
-    if not jobs:
+        all_sets += sets
+        all_ws += list(ws)
+    if not all_sets:
         raise ValueError("%s holds no weight datasets" % template_h5)
-    buf = bytearray(h.buf)
-    for off, raw in jobs:
-        buf[off:off + len(raw)] = raw
+    raw = _patched(h, all_sets, all_ws)
     with open(out_h5, "wb") as f:
-        f.write(bytes(buf))
+        f.write(raw)
     return out_h5
 
 
@@ -341,17 +353,11 @@ def check_ring_autoencoder(lys):
 
 
 def _conv2d_datasets(h, lys, spec_shapes, what, path):
-    """-> [(dataset path, (offset, nbytes), shape)] of every weight of the stack's layers, in ``layer_names`` order; ValueError for
-    storage that is not contiguous little-endian float32 or for other shapes."""
-    from .h5lite import H5Error, dataset_span
-    keep = {cfg["name"] for _, cfg in lys}
-    sets = []
+    """-> ``_weight_datasets`` of the stack's layers; ValueError for storage that is not contiguous little-endian float32 or for other
+    shapes than ``spec_shapes``."""
+    from .h5lite import H5Error
     try:
-        for ln in [n.decode() for n in h.attrs("/model_weights")["layer_names"]]:
-            if ln in keep:
-                for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
-                    p = "/model_weights/%s/%s" % (ln, wn.decode())
-                    sets.append((p, dataset_span(h, p), tuple(h.dataset_info(p)[0])))
+        sets = _weight_datasets(h, {cfg["name"] for _, cfg in lys})
     except H5Error as e:
         raise ValueError("%s: %s" % (path, e))
     if [s for _, _, s in sets] != [tuple(s) for s in spec_shapes]:
@@ -365,11 +371,7 @@ def read_ring_autoencoder(path):
     an encoder, one changed field -- is a ValueError."""
     h = H5File(path)
     check_ring_autoencoder(layers(h))
-    names = [n.decode() for n in h.attrs("/model_weights")["layer_names"]]
-    ws = []
-    for ln in names:
-        for wn in h.attrs("/model_weights/" + ln).get("weight_names", []):
-            ws.append(np.ascontiguousarray(h.dataset("/model_weights/%s/%s" % (ln, wn.decode())), np.float32))
+    ws = [np.ascontiguousarray(h.dataset(p), np.float32) for p in _weight_paths(h)]
     if [w.shape for w in ws] != RING_AE_SHAPES:
         raise ValueError("%s: weight shapes %s do not match the ring autoencoder's %s" % (path, [w.shape for w in ws], RING_AE_SHAPES))
     return ws
@@ -405,18 +407,7 @@ def write_ring_models_like(template_ae_h5, out_ae_h5, ws12, template_respond_h5=
         todo.append((hr, _conv2d_datasets(hr, lr, RING_AE_SHAPES[:4], "response layer", template_respond_h5), ws12[:4], out_respond_h5))
     elif template_respond_h5 is not None:
         raise ValueError("template_respond_h5 given without out_respond_h5")
-    files = []
-    for hh, sets, ws, out in todo:
-        buf = bytearray(hh.buf)
-        for (p, (off, nbytes), s), w in zip(sets, ws):
-            a = np.ascontiguousarray(w, dtype="<f4")
-            if a.shape != s and a.shape != (int(np.prod(s)),):
-                raise ValueError("%s: array of shape %s for a dataset of shape %s" % (p, a.shape, s))
-            raw = a.tobytes()
-            assert len(raw) == nbytes
-            buf[off:off + nbytes] = raw
-        files.append((out, bytes(buf)))
-    for out, raw in files:
+    for out, raw in [(out, _patched(hh, sets, ws)) for hh, sets, ws, out in todo]:    # both refused or both written
         with open(out, "wb") as f:
             f.write(raw)
     return out_ae_h5, out_respond_h5

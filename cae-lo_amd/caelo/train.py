@@ -4,7 +4,8 @@
 loss and its gradient (caelo_autoencoder_grad) and takes Keras 2.3's Adadelta step (caelo_adadelta_step).  ``sample_training_points``
 restates the reference's choice of training points, ``fit`` its epoch loop, ``glorot_uniform`` Keras's default initialiser.  The
 result is written with ``keras_config.write_autoencoder_like``.  Single GPU: ``multi_gpu_model`` only splits a batch whose merged
-gradient is the one computed here.
+gradient is the one computed here.  What caelo.train_ring shares lives here once: ``FlatTrainer`` (the flat buffers and loss / grad /
+step / weights on them) and ``_fit`` (the epoch loop); what the two command lines share is caelo.train_cli.
 """
 import ctypes as C
 
@@ -75,10 +76,54 @@ def sample_training_points(key_pts, n_groups, rng):
     return out
 
 
-class Trainer:
-    """The autoencoder's weights on ``eng``'s device, trainable.  ``ews`` / ``dws``: the ten encoder / decoder arrays in Keras layout,
-    ``eact`` = (hidden, code), ``dact`` = (hidden, "sigmoid") -- the sets keras_config accepts, anything else is a ValueError before a
-    weight is read.  ``chunk``: patches whose activations the workspace holds at once (about 480 KB each)."""
+class FlatTrainer:
+    """What the two trainers (``Trainer`` here, ``train_ring.RingTrainer``) share: the weight tensors ``ws`` of ``shapes`` as ONE flat
+    float32 device buffer ``params`` in the library's ``layout`` of ``n_params`` floats, the gradient ``grads`` and the optimizer's two
+    ``state`` buffers in the same layout.  A subclass supplies ``_call(batch, grads)`` -- the library's loss (and, with ``grads``,
+    gradient) of a batch into ``_loss`` (and ``grads``) -- and ``_next_optimizer_step()`` -> (the step's C symbol, its hyperparameters),
+    which ``step`` calls exactly once per step: it may count (Adam's t)."""
+
+    def __init__(self, eng, ws, shapes, layout, n_params, chunk):
+        self.eng, self.chunk, self.shapes, self.layout = eng, int(chunk), shapes, layout
+        assert sum(c for _, c in layout) == n_params and [c for _, c in layout] == [w.size for w in ws]
+        self.params = torch.from_numpy(np.concatenate([w.ravel() for w in ws])).to(eng.device)
+        self.grads = eng.zeros((n_params,), torch.float32)
+        self.state = (eng.zeros((n_params,), torch.float32), eng.zeros((n_params,), torch.float32))
+        self._loss = eng.zeros((1,), torch.float32)
+
+    def _split(self, flat):
+        return [flat[o:o + c].reshape(s).copy() for (o, c), s in zip(self.layout, self.shapes)]
+
+    def loss(self, batch):
+        """The mean loss of the batch (forward only; ``Trainer``: binary_crossentropy, ``RingTrainer``: mean_squared_error against the
+        batch itself) -> float.  Synchronises."""
+        self._call(batch, False)
+        return float(self._loss.item())
+
+    def grad(self, batch):
+        """-> (loss, the gradient arrays in ``shapes``).  Synchronises."""
+        self._call(batch, True)
+        return float(self._loss.item()), self._split(self.grads.cpu().numpy())
+
+    def step(self, batch, sync=True):
+        """One optimizer step (``Trainer``: Adadelta, ``RingTrainer``: Adam) on the batch -> its loss BEFORE the step (what Keras logs); ``sync=False`` returns the device scalar."""
+        self._call(batch, True)
+        eng = self.eng
+        symbol, hyper = self._next_optimizer_step()    # once per step, here only: RingTrainer's advances t
+        _ffi.check(getattr(eng.lib, symbol)(eng.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.state[0]), _ptr(self.state[1]),
+                                            self.params.numel(), *hyper, eng.stream))
+        return float(self._loss.item()) if sync else self._loss.clone()
+
+    def weights(self):
+        """-> the current weights, float32 arrays in Keras layout."""
+        return self._split(self.params.cpu().numpy())
+
+
+class Trainer(FlatTrainer):
+    """The autoencoder's weights on ``eng``'s device, trainable with Keras 2.3's Adadelta (``acc_g``, ``acc_d``: its accumulators).
+    ``ews`` / ``dws``: the ten encoder / decoder arrays in Keras layout, ``eact`` = (hidden, code), ``dact`` = (hidden, "sigmoid") -- the
+    sets keras_config accepts, anything else is a ValueError before a weight is read.  ``chunk``: patches whose activations the
+    workspace holds at once (about 480 KB each).  ``bits`` of every method: the batch's patches, [n, 64] int64 / uint64."""
 
     def __init__(self, eng, ews, eact, dws, dact, chunk=64):
         try:
@@ -92,14 +137,9 @@ class Trainer:
         if int(chunk) < 1:
             raise ValueError("chunk must be >= 1")
         ws = eng._weight_arrays(list(ews), ENCODER_SHAPES, "encoder") + eng._weight_arrays(list(dws), DECODER_SHAPES, "decoder")
-        self.eng, self.eact, self.dact, self.chunk = eng, tuple(eact), tuple(dact), int(chunk)
-        self.layout = param_layout()
-        assert sum(c for _, c in self.layout) == N_PARAMS and [c for _, c in self.layout] == [w.size for w in ws]
-        self.params = torch.from_numpy(np.concatenate([w.ravel() for w in ws])).to(eng.device)
-        self.grads = eng.zeros((N_PARAMS,), torch.float32)
-        self.acc_g = eng.zeros((N_PARAMS,), torch.float32)
-        self.acc_d = eng.zeros((N_PARAMS,), torch.float32)
-        self._loss = eng.zeros((1,), torch.float32)
+        super().__init__(eng, ws, SHAPES, param_layout(), N_PARAMS, chunk)
+        self.eact, self.dact = tuple(eact), tuple(dact)
+        self.acc_g, self.acc_d = self.state
 
     def _bits(self, bits):
         if not isinstance(bits, torch.Tensor):
@@ -117,30 +157,12 @@ class Trainer:
                                                   ACTIVATION_CODES[self.dact[0]], _ptr(bits) if n else None, n, self.chunk,
                                                   _ptr(self.grads) if grads else None, _ptr(self._loss), _ptr(ws), eng.stream))
 
-    def _split(self, flat):
-        return [flat[o:o + c].reshape(s).copy() for (o, c), s in zip(self.layout, SHAPES)]
-
-    def loss(self, bits):
-        """The mean binary_crossentropy of the batch (forward only) -> float.  Synchronises."""
-        self._call(bits, False)
-        return float(self._loss.item())
-
-    def grad(self, bits):
-        """-> (loss, the 20 gradient arrays in ``SHAPES``).  Synchronises."""
-        self._call(bits, True)
-        return float(self._loss.item()), self._split(self.grads.cpu().numpy())
-
-    def step(self, bits, sync=True):
-        """One Adadelta step on the batch -> its loss BEFORE the step (what Keras logs); ``sync=False`` returns the device scalar."""
-        self._call(bits, True)
-        eng = self.eng
-        _ffi.check(eng.lib.caelo_adadelta_step(eng.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.acc_g), _ptr(self.acc_d), N_PARAMS,
-                                               LR, RHO, EPSILON, eng.stream))
-        return float(self._loss.item()) if sync else self._loss.clone()
+    def _next_optimizer_step(self):
+        return "caelo_adadelta_step", (LR, RHO, EPSILON)
 
     def weights(self):
         """-> (ews, dws): the current weights as float32 arrays in Keras layout."""
-        ws = self._split(self.params.cpu().numpy())
+        ws = super().weights()
         return ws[:10], ws[10:]
 
     def install(self):
@@ -174,6 +196,14 @@ def fit(trainer, scans, epochs=10, files_per_step=2, points_per_file=256, seed=0
     a step takes ``files_per_step`` scans, ``points_per_file`` key points each, three patches per key point (YieldBatchData's
     strict bound: a list of L files gives (L - 1) // files_per_step steps, at least one here).  -> dict ``loss`` / ``val_loss``
     [epochs] f64, the epoch means (``val_loss`` is NaN without validation files)."""
+    def batch_of(files, rng):    # the generator that shuffled the scans goes on to draw every step's training points
+        return torch.cat([training_patches(trainer.eng, scans[i](), points_per_file, rng) for i in files])
+    return _fit(trainer, scans, batch_of, epochs, files_per_step, seed, train_ratio, log)
+
+
+def _fit(trainer, scans, batch_of, epochs, files_per_step, seed, train_ratio, log):
+    """The epoch loop of both trainers (``fit`` here, ``train_ring.fit``).  ``batch_of(files, rng)``: the batch of one step, ``files``
+    its scans' indices, ``rng`` the RandomState(seed) that shuffled the list."""
     rng = np.random.RandomState(seed)
     order = list(range(len(scans)))
     rng.shuffle(order)
@@ -185,8 +215,7 @@ def fit(trainer, scans, epochs=10, files_per_step=2, points_per_file=256, seed=0
     def batches(part):
         steps = max((len(part) - 1) // files_per_step, 1) if part else 0
         for s in range(steps):
-            files = part[s * files_per_step:(s + 1) * files_per_step]
-            yield torch.cat([training_patches(trainer.eng, scans[i](), points_per_file, rng) for i in files])
+            yield batch_of(part[s * files_per_step:(s + 1) * files_per_step], rng)
 
     hist = dict(loss=[], val_loss=[])
     for ep in range(epochs):

@@ -16,7 +16,7 @@ import torch
 from . import _ffi
 from .engine import NET_H, NET_W, RESPOND_SHAPES, RING_C, RING_H, RING_W, _ptr
 from .keras_config import RING_AE_SHAPES
-from .train import glorot_uniform  # noqa: F401  (shape-generic: glorot_uniform(RING_AE_SHAPES, rng))
+from .train import FlatTrainer, _fit, glorot_uniform  # noqa: F401  (glorot_uniform is shape-generic: glorot_uniform(RING_AE_SHAPES, rng))
 
 N_PARAMS = 5835
 # Keras 2.2.4 Adam defaults (optimizer='Adam', AE4SphericalRingPC.py:150); epsilon = K.epsilon()
@@ -36,24 +36,18 @@ def adam_lr_t(t, lr=LR, beta_1=BETA_1, beta_2=BETA_2):
     return np.float32(float(lr) * np.sqrt(1.0 - float(beta_2) ** int(t)) / (1.0 - float(beta_1) ** int(t)))
 
 
-class RingTrainer:
-    """The ring autoencoder's weights on ``eng``'s device, trainable.  ``ws12``: the 12 arrays in Keras layout (``RING_AE_SHAPES`` or
-    flat).  ``chunk``: images whose activations the workspace holds at once (54 MB each at 64 x 1792).  ``images`` of every method:
-    a ``[n, h, w, 3]`` float32 tensor (h and w multiples of 4), or a ``[n, 69, 1800, 5]`` batch of projected rings, which is read in
-    place at h = 64, w = 1792, channels 0..2, through the strides."""
+class RingTrainer(FlatTrainer):
+    """The ring autoencoder's weights on ``eng``'s device, trainable with Keras 2.2.4's Adam (``m``, ``v``: its moments, ``t``: the steps
+    taken).  ``ws12``: the 12 arrays in Keras layout (``RING_AE_SHAPES`` or flat).  ``chunk``: images whose activations the workspace
+    holds at once (54 MB each at 64 x 1792).  ``images`` of every method: a ``[n, h, w, 3]`` float32 tensor (h and w multiples of 4),
+    or a ``[n, 69, 1800, 5]`` batch of projected rings, which is read in place at h = 64, w = 1792, channels 0..2, through the strides."""
 
     def __init__(self, eng, ws12, chunk=4):
         if not 1 <= int(chunk) <= 4096:
             raise ValueError("chunk must be in [1, 4096]")
         ws = eng._weight_arrays(list(ws12), [tuple(s) for s in RING_AE_SHAPES], "ring autoencoder")
-        self.eng, self.chunk, self.t = eng, int(chunk), 0
-        self.layout = param_layout()
-        assert sum(c for _, c in self.layout) == N_PARAMS and [c for _, c in self.layout] == [w.size for w in ws]
-        self.params = torch.from_numpy(np.concatenate([w.ravel() for w in ws])).to(eng.device)
-        self.grads = eng.zeros((N_PARAMS,), torch.float32)
-        self.m = eng.zeros((N_PARAMS,), torch.float32)
-        self.v = eng.zeros((N_PARAMS,), torch.float32)
-        self._loss = eng.zeros((1,), torch.float32)
+        super().__init__(eng, ws, RING_AE_SHAPES, param_layout(), N_PARAMS, chunk)
+        (self.m, self.v), self.t = self.state, 0
 
     def _images(self, images):
         if not isinstance(images, torch.Tensor):
@@ -85,35 +79,13 @@ class RingTrainer:
                                                        _ptr(ws), eng.stream))
         return out
 
-    def _split(self, flat):
-        return [flat[o:o + c].reshape(s).copy() for (o, c), s in zip(self.layout, RING_AE_SHAPES)]
-
-    def loss(self, images):
-        """The mean_squared_error of the batch against itself (forward only) -> float.  Synchronises."""
-        self._call(images, False)
-        return float(self._loss.item())
-
-    def grad(self, images):
-        """-> (loss, the 12 gradient arrays in ``RING_AE_SHAPES``).  Synchronises."""
-        self._call(images, True)
-        return float(self._loss.item()), self._split(self.grads.cpu().numpy())
-
-    def step(self, images, sync=True):
-        """One Adam step on the batch -> its loss BEFORE the step (what Keras logs); ``sync=False`` returns the device scalar."""
-        self._call(images, True)
-        eng = self.eng
+    def _next_optimizer_step(self):
         self.t += 1
-        _ffi.check(eng.lib.caelo_adam_step(eng.ctx, _ptr(self.params), _ptr(self.grads), _ptr(self.m), _ptr(self.v), N_PARAMS,
-                                           float(adam_lr_t(self.t)), BETA_1, BETA_2, EPSILON, eng.stream))
-        return float(self._loss.item()) if sync else self._loss.clone()
+        return "caelo_adam_step", (float(adam_lr_t(self.t)), BETA_1, BETA_2, EPSILON)
 
     def predict(self, images):
         """autoencoder.predict -> [n, h, w, 3] float32 on the device."""
         return self._call(images, False, recon=True)
-
-    def weights(self):
-        """-> the 12 current arrays, float32 in Keras layout."""
-        return self._split(self.params.cpu().numpy())
 
     def respond_weights(self):
         """-> conv2d_1 and conv2d_2 (kernel, bias each): the response layer the reference saves beside the autoencoder."""
@@ -143,25 +115,4 @@ def fit(trainer, scans, epochs=10, files_per_step=32, seed=0, train_ratio=0.9, l
     validates; a step takes ``files_per_step`` scans (YieldBatchData's strict bound: a list of L files gives (L - 1) // files_per_step
     steps per pass, at least one here).  -> dict ``loss`` / ``val_loss`` [epochs] f64, the epoch means (``val_loss`` is NaN without
     validation files)."""
-    rng = np.random.RandomState(seed)
-    order = list(range(len(scans)))
-    rng.shuffle(order)
-    n_train = int(train_ratio * len(order))
-    parts = (order[:n_train], order[n_train:])
-    if not parts[0]:
-        raise ValueError("no training scans (%d given, %g of them train)" % (len(scans), train_ratio))
-
-    def batches(part):
-        steps = max((len(part) - 1) // files_per_step, 1) if part else 0
-        for s in range(steps):
-            yield ring_batch(trainer.eng, [scans[i]() for i in part[s * files_per_step:(s + 1) * files_per_step]])
-
-    hist = dict(loss=[], val_loss=[])
-    for ep in range(epochs):
-        tl = [trainer.step(b, sync=False) for b in batches(parts[0])]
-        vl = [trainer.loss(b) for b in batches(parts[1])]
-        hist["loss"].append(float(torch.cat(tl).double().mean().item()))
-        hist["val_loss"].append(float(np.mean(vl)) if vl else float("nan"))
-        if log:
-            log("epoch %d/%d: loss %.6f, val_loss %.6f (%d + %d steps)" % (ep + 1, epochs, hist["loss"][-1], hist["val_loss"][-1], len(tl), len(vl)))
-    return {k: np.asarray(v, np.float64) for k, v in hist.items()}
+    return _fit(trainer, scans, lambda files, rng: ring_batch(trainer.eng, [scans[i]() for i in files]), epochs, files_per_step, seed, train_ratio, log)

@@ -408,6 +408,10 @@ int correct_set(const caelo_extract_args *args, int n, hipStream_t s);
 
 #define CAELO_KP_HIST_BINS 2048
 
+// v_mfma_f32_16x16x4_f32 and its accumulator: the exact-f32 matrix step of encoder.hip, decoder.hip and the two trainers
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
 // Workgroup barrier that orders LDS traffic only.  __syncthreads() also drains vmcnt, i.e. stalls the
 // whole workgroup on every global load / store / atomic still in flight (microseconds for a contended
 // atomic); kernels that hand data between waves through LDS and keep global traffic asynchronous use this.

@@ -30,9 +30,6 @@
 #include <math.h>
 #include <vector>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 #define DEC_TILE 64           // patches per workgroup of k_dec_dense
 #define DEC_H3_LD 201         // LDS leading dimension of h3 (201 = 9 mod 64 banks)
 // the decoder's device image, in floats

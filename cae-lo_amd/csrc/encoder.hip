@@ -34,10 +34,6 @@
 #include <stdlib.h>
 #include <string.h>
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
-
 // tanh x = 1 - 2 / (exp(2x) + 1) on v_exp_f32 + v_rcp_f32: 5 instructions instead of libm's ~50 (the encoder
 // evaluates 6.9 M tanh per frame; in k_enc_conv3 alone they were ~8 us).  Absolute error < 6e-7 over the whole
 // range (saturates to +-1 through exp -> inf / 0), against a parity budget of 1e-4 on the descriptors.

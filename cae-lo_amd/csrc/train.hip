@@ -5,28 +5,24 @@
 // same layout.  A layer's kernel [.., Cin, Cout] is followed by its bias [Cout], so kernel and bias together are one row-major
 // [rows + 1][Cout] matrix: every weight-gradient GEMM below carries a row of ones behind its A operand and the bias gradient falls out.
 //
-// Arithmetic: f32 operands, f32 accumulation on v_mfma_f32_16x16x4_f32 (an exact fmaf chain over ascending k, as in decoder.hip); a
-// sum over K runs as four such chains (k-step s on chain s & 3) joined as (0 + 1) + (2 + 3): shorter chains lose fewer bits, and
-// the four are independent instructions for the matrix pipe.  No floating-point atomics.  Every output element has one owner (a wavefront's accumulator) and one order of summation:
+// Arithmetic: f32 operands, f32 accumulation on v_mfma_f32_16x16x4_f32 (an exact fmaf chain over ascending k, as in decoder.hip), a sum
+// over K as four such chains.  No floating-point atomics.  Every output element has one owner (a wavefront's accumulator) and one order
+// of summation.  Shared with train_ring.hip and defined once in train_common.h: the chains (CHAINS_*), the B operand's staging
+// (tc_stage_b), k_tc_wreduce, tc_wave_sum, tc_block_sum, the workspace and parameter layout helpers, the optimizer launcher.  Here:
 //   k_tr_conv    forward convs and data gradients as implicit GEMMs, M = cells x patches (an m-tile = 16 consecutive cells), N = output
 //                channels, K = 27 x input channels over ascending (tap, channel).  The data gradient is the same kernel with the Keras
 //                kernel flipped and its channel axes swapped while it is staged in LDS.  The input is read in place: plain, through
 //                UpSampling3D(2) (cell u reads source cell u >> 1: nothing is materialised going forward), or from the bit-packed patch.
 //   k_tr_wgrad   a conv's weight gradient: M = 27 Cin + 1, N = Cout, K = cells x patches split into slices of 256 cells, one
-//                (m-tile, slice) per wavefront; k_tr_wreduce adds a chunk's slices in a fixed order in double, then that sum to the gradient.
+//                (m-tile, slice) per wavefront; k_tc_wreduce adds a chunk's slices in a fixed order in double, then that sum to the gradient.
 //   k_tr_gemm    the dense layers, their data gradients and their weight gradients (K = the chunk's patches, added to the gradient).
 //   pooling      the gradient of a window goes to its FIRST maximum in ascending (dx, dy, dz) order, dz fastest (k_tr_unpool);
 //                UpSampling3D's adjoint is the sum of the eight children in that same order (k_tr_upsum).
-//   loss         softplus(-+z) with z clipped to +-logit(1 - 1e-7), float terms summed in double per patch in a fixed tree, patches added
-//                in ascending order in double, rounded once: the loss bits depend on n alone, not on the chunk.
+//   loss         softplus(-+z) with z clipped to +-logit(1 - 1e-7), float terms summed in double per patch in a fixed tree (k_tr_loss),
+//                patches added in ascending order in double, rounded once (k_tr_loss_acc): the loss bits depend on n alone, not on the chunk.
 // The batch is walked in chunks of `chunk` patches (the workspace holds one chunk's activations and their gradients, tr_layout); chunk
 // partials are added in ascending chunk order, so the gradient bits are fixed by (n, chunk).
-#include "caelo_internal.h"
-
-#include <math.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+#include "train_common.h"
 
 #define TR_LOGIT_CLIP 16.11809555f   // logit(1 - 1e-7), decoder.hip's DEC_LOGIT_CLIP
 #define TR_SLICE 256                 // cells per K slice of a conv weight gradient
@@ -49,17 +45,15 @@ struct TrLayout {
 
 static TrLayout tr_layout(int64_t c) {
     TrLayout L;
-    int64_t o = 0;
-    auto take = [&](int64_t per) { const int64_t at = o; o += (per * c + 63) / 64 * 64; return at; };
+    TcTake take{c, 0};
     L.a1 = take(32768); L.p1 = take(4096); L.a2 = take(8192); L.p2 = take(1024); L.f3 = take(2048); L.h1 = take(200); L.code = take(20);
     L.h3 = take(200); L.g4 = take(2048); L.y4 = take(1024); L.y5 = take(4096); L.z = take(4096);
     L.dz = take(4096); L.du5 = take(32768); L.dy5 = take(4096); L.du4 = take(8192); L.dy4 = take(1024); L.dg4 = take(2048); L.dh3 = take(200);
     L.dcode = take(20); L.dcodep = take(20); L.dh1 = take(200); L.df3 = take(2048); L.dp2 = take(1024); L.da2 = take(8192); L.dp1 = take(4096);
     L.da1 = take(32768);
     // slice partials: conv2 2c x 217 x 16 is the largest per patch, conv3 ceil(c / 4) x 433 x 32 the largest per slice
-    L.part = o;
-    o += 6944 * c + 13856 * (c / 4 + 1);
-    L.total = o;
+    L.part = take.o;
+    L.total = take.o + 6944 * c + 13856 * (c / 4 + 1);
     L.base_bytes = ((1 + c) * 8 + 255) / 256 * 256;
     return L;
 }
@@ -103,29 +97,19 @@ __device__ __forceinline__ float tr_in(const void *in, int p, int x, int y, int 
 template <int CIN, int COUT, int S, int INMODE, bool FLIP>
 __global__ __launch_bounds__(256) void k_tr_conv(const void *__restrict__ in, const float *__restrict__ W, const float *__restrict__ bias,
                                                  float *__restrict__ out, int rows, int act) {
-    constexpr int K = 27 * CIN, K4 = (K + 3) / 4 * 4, NP = (COUT + 15) / 16 * 16, NT = NP / 16;
+    constexpr int K4 = (27 * CIN + 3) / 4 * 4, NP = (COUT + 15) / 16 * 16, NT = NP / 16;
     extern __shared__ float sB[];   // [K4][NP]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4;
-    for (int i = tid; i < K4 * NP; i += 256) {
-        const int k = i / NP, n = i - k * NP;
-        float v = 0.0f;
-        if (k < K && n < COUT) {
-            const int tap = k / CIN, ci = k - tap * CIN;
-            v = FLIP ? W[((26 - tap) * COUT + n) * CIN + ci] : W[k * COUT + n];
-        }
-        sB[i] = v;
-    }
+    tc_stage_b<27, CIN, COUT, FLIP>(sB, W, tid);
     __syncthreads();
     const int tiles = rows >> 4;
     for (int tile = blockIdx.x * 4 + wave; tile < tiles; tile += gridDim.x * 4) {
         const int row = tile * 16 + r;
         const int p = row / (S * S * S), cell = row - p * (S * S * S);
         const int x = cell / (S * S), y = (cell / S) % S, z = cell % S;
-        f32x4 acc[NT][4];   // k-step s goes to chain s & 3: four short chains instead of one long one, joined as (0 + 1) + (2 + 3)
+        f32x4 acc[NT][4];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[nt][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int nt = 0; nt < NT; ++nt) CHAINS_ZERO(acc[nt]);
         if (CIN >= 4) {
 #pragma unroll
             for (int tap = 0; tap < 27; ++tap) {
@@ -135,8 +119,7 @@ __global__ __launch_bounds__(256) void k_tr_conv(const void *__restrict__ in, co
                 for (int cq = 0; cq < CIN / 4; ++cq) {
                     const float a = inb ? tr_in<CIN, S, INMODE>(in, p, xx, yy, zz, cq * 4 + kq) : 0.0f;
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt)
-                        acc[nt][(tap * (CIN / 4) + cq) & 3] = MFMA16(a, sB[(tap * CIN + cq * 4 + kq) * NP + nt * 16 + r], acc[nt][(tap * (CIN / 4) + cq) & 3]);
+                    for (int nt = 0; nt < NT; ++nt) CHAINS_STEP(acc[nt], tap * (CIN / 4) + cq, a, sB[(tap * CIN + cq * 4 + kq) * NP + nt * 16 + r]);
                 }
             }
         } else {   // CIN == 1: a k-step spans four taps
@@ -147,7 +130,7 @@ __global__ __launch_bounds__(256) void k_tr_conv(const void *__restrict__ in, co
                 const bool inb = tap < 27 && (unsigned)xx < (unsigned)S && (unsigned)yy < (unsigned)S && (unsigned)zz < (unsigned)S;
                 const float a = inb ? tr_in<CIN, S, INMODE>(in, p, xx, yy, zz, 0) : 0.0f;
 #pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[nt][ks & 3] = MFMA16(a, sB[tap * NP + nt * 16 + r], acc[nt][ks & 3]);
+                for (int nt = 0; nt < NT; ++nt) CHAINS_STEP(acc[nt], ks, a, sB[tap * NP + nt * 16 + r]);
             }
         }
 #pragma unroll
@@ -155,7 +138,7 @@ __global__ __launch_bounds__(256) void k_tr_conv(const void *__restrict__ in, co
             const int col = nt * 16 + r;
             if (col < COUT) {
                 const float b = bias ? bias[col] : 0.0f;
-                const f32x4 sum = (acc[nt][0] + acc[nt][1]) + (acc[nt][2] + acc[nt][3]);
+                const f32x4 sum = CHAINS_JOIN(acc[nt]);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) out[(size_t)(tile * 16 + 4 * kq + i) * COUT + col] = tr_act(sum[i] + b, act);
             }
@@ -176,11 +159,9 @@ __global__ __launch_bounds__(256) void k_tr_wgrad(const void *__restrict__ in, c
     if (sl >= nsl) return;   // (wavefront-uniform)
     const int m = mt * 16 + r, tap = m / CIN, ci = m - tap * CIN;
     const int tx = tap / 9 - 1, ty = (tap / 3) % 3 - 1, tz = tap % 3 - 1;
-    f32x4 acc[NT][4];   // four chains, as in k_tr_conv
+    f32x4 acc[NT][4];
 #pragma unroll
-    for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[nt][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    for (int nt = 0; nt < NT; ++nt) CHAINS_ZERO(acc[nt]);
 #pragma unroll 4
     for (int ks = 0; ks < TR_SLICE / 4; ++ks) {
         const int row = sl * TR_SLICE + ks * 4 + kq;
@@ -199,32 +180,19 @@ __global__ __launch_bounds__(256) void k_tr_wgrad(const void *__restrict__ in, c
         for (int nt = 0; nt < NT; ++nt) {
             const int col = nt * 16 + r;
             const float b = live && col < COUT ? delta[(size_t)row * COUT + col] : 0.0f;
-            acc[nt][ks & 3] = MFMA16(a, b, acc[nt][ks & 3]);
+            CHAINS_STEP(acc[nt], ks, a, b);
         }
     }
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
         const int col = nt * 16 + r;
-        const f32x4 sum = (acc[nt][0] + acc[nt][1]) + (acc[nt][2] + acc[nt][3]);
+        const f32x4 sum = CHAINS_JOIN(acc[nt]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const int mrow = mt * 16 + 4 * kq + i;
             if (mrow < M1 && col < COUT) part[((size_t)sl * M1 + mrow) * COUT + col] = sum[i];
         }
     }
-}
-
-// dst[i] += the sum over the slices of part[slice][i], in double, rounded once: one wavefront per element, lane l takes slices l, l + 64,
-// ... in ascending order, the 64 lane sums meet in a fixed butterfly -- an order fixed by nsl alone
-__global__ __launch_bounds__(256) void k_tr_wreduce(const float *__restrict__ part, int nsl, int count, float *__restrict__ dst) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= count) return;   // (wavefront-uniform)
-    double s = 0.0;
-    for (int sl = lane; sl < nsl; sl += 64) s += (double)part[(size_t)sl * count + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) dst[i] += (float)s;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -302,9 +270,8 @@ __global__ __launch_bounds__(256) void k_tr_gemm(const TrGemm g) {
     const int m = (tile / tn) * 16 + r, n = (tile % tn) * 16 + r;
     const bool one = g.ones && m == g.M - 1, am = m < g.M, bn = n < g.N;
     const float *ap = g.A + (int64_t)m * g.sam, *bp = g.B + (int64_t)n * g.sbn;
-    f32x4 acc4[4];   // four chains, as in k_tr_conv
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc4[j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+    f32x4 acc4[4];
+    CHAINS_ZERO(acc4);
     for (int k0 = 0; k0 < g.K; k0 += 16) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -312,10 +279,10 @@ __global__ __launch_bounds__(256) void k_tr_gemm(const TrGemm g) {
             const bool kin = k < g.K;
             const float a = kin && am ? (one ? 1.0f : ap[(int64_t)k * g.sak]) : 0.0f;
             const float b = kin && bn ? bp[(int64_t)k * g.sbk] : 0.0f;
-            acc4[j] = MFMA16(a, b, acc4[j]);
+            CHAINS_STEP(acc4, j, a, b);
         }
     }
-    const f32x4 acc = (acc4[0] + acc4[1]) + (acc4[2] + acc4[3]);
+    const f32x4 acc = CHAINS_JOIN(acc4);
     if (!bn) return;
     const float bias = g.mode == 0 && g.bias ? g.bias[n] : 0.0f;
 #pragma unroll
@@ -330,12 +297,11 @@ __global__ __launch_bounds__(256) void k_tr_gemm(const TrGemm g) {
 }
 
 // ------------------------------------------------------------------------------------------------
-// one workgroup per patch: its 4096 loss terms summed in double (thread -> wavefront -> workgroup, a fixed tree), and
+// one workgroup per patch: its 4096 loss terms summed in double (thread, then tc_block_sum: a fixed tree), and
 // dz = (sigmoid(z) - y) scale where |z| <= the clip, 0 beyond it
 __global__ __launch_bounds__(256) void k_tr_loss(const float *__restrict__ z, const unsigned long long *__restrict__ bits, float *__restrict__ dz,
                                                  double *__restrict__ patch_loss, float scale) {
-    __shared__ double s_part[4];
-    const int p = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int p = blockIdx.x, tid = threadIdx.x;
     const unsigned long long word = bits[(size_t)p * 64 + (tid >> 2)];
     double lsum = 0.0;
 #pragma unroll
@@ -351,14 +317,10 @@ __global__ __launch_bounds__(256) void k_tr_loss(const float *__restrict__ z, co
             dz[(size_t)p * 4096 + lin] = fabsf(v) <= TR_LOGIT_CLIP ? (s - (y ? 1.0f : 0.0f)) * scale : 0.0f;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
-    if (lane == 0) s_part[wave] = lsum;
-    __syncthreads();
-    if (tid == 0) patch_loss[p] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+    tc_block_sum(lsum, patch_loss + p);
 }
 
-// the chunk's patches onto the running sum, ascending; the last chunk rounds the mean once
+// the chunk's patches onto the running sum, ascending; the last chunk rounds the mean once (k_rt_loss_acc's order at one sum per image, minus its butterflies)
 __global__ void k_tr_loss_acc(const double *__restrict__ patch_loss, int c, double *__restrict__ acc, int first, int last, double count,
                               float *__restrict__ loss) {
     if (threadIdx.x || blockIdx.x) return;
@@ -393,12 +355,7 @@ __global__ __launch_bounds__(256) void k_tr_adadelta(float *__restrict__ p, cons
 // ================================================================================================
 CAELO_API int caelo_train_param_layout(int64_t out[20][2]) {
     CAELO_REQUIRE(out != nullptr, "null argument");
-    int64_t o = 0;
-    for (int t = 0; t < 20; ++t) {
-        out[t][0] = o;
-        out[t][1] = TR_COUNT[t];
-        o += TR_COUNT[t];
-    }
+    tc_param_layout(TR_COUNT, 20, out);
     return CAELO_OK;
 }
 
@@ -431,7 +388,7 @@ static void tr_wgrad(const void *in, const float *delta, float *part, float *dst
     constexpr int M1 = 27 * CIN + 1, MT = (M1 + 15) / 16;
     const int nsl = (rows + TR_SLICE - 1) / TR_SLICE, count = M1 * COUT;
     k_tr_wgrad<CIN, COUT, S, INMODE><<<(MT * nsl + 3) / 4, 256, 0, s>>>(in, delta, part, rows, nsl);
-    k_tr_wreduce<<<(count + 3) / 4, 256, 0, s>>>(part, nsl, count, dst);
+    tc_wreduce(part, nsl, count, dst, s);
 }
 
 static void tr_gemm(const float *A, int64_t sam, int64_t sak, const float *B, int64_t sbk, int64_t sbn, float *C, int64_t ldc, int M, int N, int K,
@@ -526,11 +483,7 @@ CAELO_API int caelo_autoencoder_grad(caelo_ctx *c, const float *params, int enc_
 
 CAELO_API int caelo_adadelta_step(caelo_ctx *c, float *params, const float *grads, float *acc_g, float *acc_d, int64_t count, float lr, float rho,
                                   float eps, void *stream) {
-    CAELO_REQUIRE(c != nullptr, "null context");
-    CAELO_REQUIRE(count >= 0 && count < ((int64_t)1 << 39), "count out of range");
-    if (count == 0) return CAELO_OK;
-    CAELO_REQUIRE(params && grads && acc_g && acc_d, "null argument");
-    k_tr_adadelta<<<(unsigned)((count + 255) / 256), 256, 0, caelo_stream(stream)>>>(params, grads, acc_g, acc_d, count, lr, rho, eps);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return tc_optimizer_step(__func__, c, count, params && grads && acc_g && acc_d, stream, [&](unsigned blocks, hipStream_t s) {
+        k_tr_adadelta<<<blocks, 256, 0, s>>>(params, grads, acc_g, acc_d, count, lr, rho, eps);
+    });
 }

@@ -6,8 +6,8 @@
 // is followed by its bias [Cout], so the two are one row-major [taps Cin + 1][Cout] matrix: every weight-gradient GEMM carries a row
 // of ones behind its A operand and the bias gradient is its last row (train.hip's arrangement).
 //
-// Arithmetic as in train.hip: f32 operands and accumulation on v_mfma_f32_16x16x4_f32, a sum over K as four chains (k-step s on chain
-// s & 3) joined as (0 + 1) + (2 + 3); no floating-point atomics; every output element has one owner and one order of summation.
+// Arithmetic as in train.hip: four MFMA chains per sum over K, no floating-point atomics, one owner and one order of summation per output
+// element.  CHAINS_*, tc_stage_b, k_tc_wreduce, tc_wave_sum, tc_block_sum, the layout helpers and the optimizer launcher: train_common.h.
 //   k_rt_conv    forward convs and data gradients as implicit GEMMs.  A workgroup owns a tile of 4 rows x 64 columns of one image and
 //                stages the (4 + 2) x (64 + 2) x Cin input tile with its halo (zeros outside the image) and the layer's B operand in LDS
 //                once; a wavefront takes one row: four m-tiles of 16 consecutive pixels (columns >= w are computed on zeros and not
@@ -16,20 +16,15 @@
 //                strides (the caller's images in place) and optionally through UpSampling2D(2) (pixel u reads source pixel u >> 1).
 //   k_rt_wgrad   a layer's weight gradient: M = taps Cin + 1, N = Cout, K = pixels.  A workgroup stages the same input tile and the
 //                tile's 256 delta rows in LDS, walks up to eight tiles with its sums in registers and writes one slice of partial sums
-//                per K part; k_rt_wreduce adds a chunk's slices in a fixed order in double (one wavefront per element, train.hip's
-//                butterfly) and then adds that to the gradient.
+//                per K part; k_tc_wreduce adds a chunk's slices in a fixed order in double (one wavefront per element) and then adds
+//                that to the gradient.
 //   pooling      the gradient of a window goes to its FIRST maximum in ascending (dy, dx) order, dx fastest (k_rt_unpool);
 //                UpSampling2D's adjoint sums the four children in that order, times the source layer's relu' (k_rt_upsum).
-//   loss         (r - x)^2 in double: 4096 elements per workgroup in a fixed tree, an image's workgroups in a fixed butterfly, images in
-//                ascending order, rounded once -- the loss bits depend on (n, h, w) alone, not on the chunk.
+//   loss         (r - x)^2 in double: 4096 elements per workgroup in a fixed tree (k_rt_loss), an image's workgroups in a fixed butterfly,
+//                images in ascending order, rounded once (k_rt_loss_acc) -- the loss bits depend on (n, h, w) alone, not on the chunk.
 // A1 (32 channels at full resolution) is STORED by the forward pass, not recomputed: recomputing it is the network's largest layer
 // again (46 % of a forward pass) while storing it costs one write and two reads of 128 bytes per pixel.
-#include "caelo_internal.h"
-
-#include <math.h>
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-#define MFMA16(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+#include "train_common.h"
 
 #define RT_TR 4            // rows of a workgroup's tile: one per wavefront
 #define RT_TC 64           // its columns: four m-tiles
@@ -64,8 +59,7 @@ static inline int64_t rt_tiles(int h, int w) { return (int64_t)((h + RT_TR - 1) 
 static RtLayout rt_layout(int h, int w, int64_t c) {
     RtLayout L;
     const int64_t px = (int64_t)h * w, px2 = px / 4, px4 = px / 16;
-    int64_t o = 0;
-    auto take = [&](int64_t per) { const int64_t at = o; o += (per * c + 63) / 64 * 64; return at; };
+    TcTake take{c, 0};
     L.a1 = take(32 * px); L.a2 = take(8 * px); L.p1 = take(8 * px2); L.a3 = take(16 * px2); L.p2 = take(16 * px4); L.y4 = take(16 * px4);
     L.y5 = take(8 * px2); L.r = take(3 * px);
     L.dr = take(3 * px); L.du5 = take(8 * px); L.dy5 = take(8 * px2); L.du4 = take(16 * px2); L.dy4 = take(16 * px4); L.dp2 = take(16 * px4);
@@ -75,9 +69,8 @@ static RtLayout rt_layout(int h, int w, int64_t c) {
     int64_t part = 2 * 896 * rt_tiles(h, w);
     if (1168 * rt_tiles(h / 2, w / 2) > part) part = 1168 * rt_tiles(h / 2, w / 2);
     if (2320 * rt_tiles(h / 4, w / 4) > part) part = 2320 * rt_tiles(h / 4, w / 4);
-    L.part = o;
-    o += part * c;
-    L.total = o;
+    L.part = take.o;
+    L.total = take.o + part * c;
     L.loss_blocks = (3 * px + RT_LOSS_ELEMS - 1) / RT_LOSS_ELEMS;
     L.base_bytes = ((1 + L.loss_blocks * c) * 8 + 255) / 256 * 256;
     return L;
@@ -107,22 +100,14 @@ __device__ __forceinline__ void rt_stage_tile(float *sA, const RtIn in, int img,
 template <int CIN, int COUT, int KS, int UP, bool FLIP>
 __global__ __launch_bounds__(256) void k_rt_conv(const RtIn in, const float *__restrict__ W, const float *__restrict__ bias, float *__restrict__ out,
                                                  const float *__restrict__ gate, int H, int Wd, int tiles_x, int tiles_y, int act) {
-    constexpr int T = KS * KS, K = T * CIN, K4 = (K + 3) / 4 * 4, NP = (COUT + 15) / 16 * 16, NT = NP / 16;
+    constexpr int K = KS * KS * CIN, K4 = (K + 3) / 4 * 4, NP = (COUT + 15) / 16 * 16, NT = NP / 16;
     constexpr int HL = KS / 2, PS = CIN | 1, AW = RT_TC + 2 * HL;
     extern __shared__ float smem[];
     float *sB = smem, *sA = smem + K4 * NP;   // [K4][NP], the tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, kq = lane >> 4;
     const int tx = blockIdx.x % tiles_x, ty = (blockIdx.x / tiles_x) % tiles_y, img = blockIdx.x / (tiles_x * tiles_y);
     const int x0 = tx * RT_TC, y0 = ty * RT_TR;
-    for (int i = tid; i < K4 * NP; i += 256) {
-        const int k = i / NP, n = i - k * NP;
-        float v = 0.0f;
-        if (k < K && n < COUT) {
-            const int tap = k / CIN, ci = k - tap * CIN;
-            v = FLIP ? W[((T - 1 - tap) * COUT + n) * CIN + ci] : W[k * COUT + n];
-        }
-        sB[i] = v;
-    }
+    tc_stage_b<KS * KS, CIN, COUT, FLIP>(sB, W, tid);
     rt_stage_tile<CIN, KS, UP>(sA, in, img, y0, x0, H, Wd, tid);
     __syncthreads();
     const int y = y0 + wave;
@@ -132,23 +117,21 @@ __global__ __launch_bounds__(256) void k_rt_conv(const RtIn in, const float *__r
         if (xb >= Wd) break;
         f32x4 acc[NT][4];
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) acc[nt][j] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int nt = 0; nt < NT; ++nt) CHAINS_ZERO(acc[nt]);
 #pragma unroll
         for (int ks = 0; ks < K4 / 4; ++ks) {
             const int k = ks * 4 + kq, tap = k / CIN, ci = k - tap * CIN;
             const int dy = tap / KS, dx = tap - dy * KS;
             const float a = (K4 == K || k < K) ? sA[((wave + dy) * AW + mt * 16 + r + dx) * PS + ci] : 0.0f;
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[nt][ks & 3] = MFMA16(a, sB[k * NP + nt * 16 + r], acc[nt][ks & 3]);
+            for (int nt = 0; nt < NT; ++nt) CHAINS_STEP(acc[nt], ks, a, sB[k * NP + nt * 16 + r]);
         }
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int col = nt * 16 + r;
             if (col < COUT) {
                 const float b = bias ? bias[col] : 0.0f;
-                const f32x4 sum = (acc[nt][0] + acc[nt][1]) + (acc[nt][2] + acc[nt][3]);
+                const f32x4 sum = CHAINS_JOIN(acc[nt]);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const int x = xb + 4 * kq + i;
@@ -182,9 +165,7 @@ __global__ __launch_bounds__(256) void k_rt_wgrad(const RtIn in, const float *__
 #pragma unroll
     for (int j = 0; j < JOBS; ++j)
 #pragma unroll
-        for (int nt = 0; nt < NT; ++nt)
-#pragma unroll
-            for (int c = 0; c < 4; ++c) acc[j][nt][c] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        for (int nt = 0; nt < NT; ++nt) CHAINS_ZERO(acc[j][nt]);
     for (int g = 0; g < group; ++g) {
         const int t = blockIdx.x * group + g;
         if (t >= tiles) break;   // (workgroup-uniform)
@@ -211,7 +192,7 @@ __global__ __launch_bounds__(256) void k_rt_wgrad(const RtIn in, const float *__
                     const float v = sA[base + ((pix / RT_TC) * AW + pix % RT_TC) * PS];
                     const float a = m < M ? v : (m == M ? 1.0f : 0.0f);
 #pragma unroll
-                    for (int nt = 0; nt < NT; ++nt) acc[j][nt][ks & 3] = MFMA16(a, sD[pix * NP + nt * 16 + r], acc[j][nt][ks & 3]);
+                    for (int nt = 0; nt < NT; ++nt) CHAINS_STEP(acc[j][nt], ks, a, sD[pix * NP + nt * 16 + r]);
                 }
             }
         }
@@ -226,7 +207,7 @@ __global__ __launch_bounds__(256) void k_rt_wgrad(const RtIn in, const float *__
 #pragma unroll
         for (int nt = 0; nt < NT; ++nt) {
             const int col = nt * 16 + r;
-            const f32x4 sum = (acc[j][nt][0] + acc[j][nt][1]) + (acc[j][nt][2] + acc[j][nt][3]);
+            const f32x4 sum = CHAINS_JOIN(acc[j][nt]);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 const int mrow = mt * 16 + 4 * kq + i;
@@ -234,19 +215,6 @@ __global__ __launch_bounds__(256) void k_rt_wgrad(const RtIn in, const float *__
             }
         }
     }
-}
-
-// dst[i] += the sum over the slices of part[slice][i], in double, rounded once (train.hip's k_tr_wreduce): one wavefront per element,
-// lane l takes slices l, l + 64, ... ascending, the 64 lane sums meet in a fixed butterfly -- an order fixed by nsl alone
-__global__ __launch_bounds__(256) void k_rt_wreduce(const float *__restrict__ part, int64_t nsl, int count, float *__restrict__ dst) {
-    const int lane = threadIdx.x & 63;
-    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (i >= count) return;   // (wavefront-uniform)
-    double s = 0.0;
-    for (int64_t sl = lane; sl < nsl; sl += 64) s += (double)part[sl * count + i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) dst[i] += (float)s;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -306,11 +274,10 @@ __global__ __launch_bounds__(256) void k_rt_upsum(const float *__restrict__ dU, 
 
 // ------------------------------------------------------------------------------------------------
 // workgroup b of image i: elements e = b 4096 + j 256 + tid (e = pixel x 3 + channel) of (r - x)^2, d = r - x rounded in f32, squared and
-// summed in double (thread: ascending j, wavefront: butterfly, workgroup: ((0 + 1) + 2) + 3); dr = d scale
+// summed in double (thread: ascending j, then tc_block_sum); dr = d scale
 __global__ __launch_bounds__(256) void k_rt_loss(const float *__restrict__ rec, const RtIn in, float *__restrict__ dr, double *__restrict__ block_sums, int Wd,
                                                  int64_t per_img, int loss_blocks, float scale) {
-    __shared__ double s_part[4];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     const int b = blockIdx.x % loss_blocks, img = blockIdx.x / loss_blocks;
     double lsum = 0.0;
 #pragma unroll 4
@@ -324,11 +291,7 @@ __global__ __launch_bounds__(256) void k_rt_loss(const float *__restrict__ rec, 
             if (dr) dr[(int64_t)img * per_img + e] = d * scale;
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lsum += __shfl_xor(lsum, o);
-    if (lane == 0) s_part[wave] = lsum;
-    __syncthreads();
-    if (tid == 0) block_sums[blockIdx.x] = ((s_part[0] + s_part[1]) + s_part[2]) + s_part[3];
+    tc_block_sum(lsum, block_sums + blockIdx.x);
 }
 
 // one wavefront: each image's workgroup sums meet in a fixed order (lane l takes l, l + 64, ..., then the butterfly), the images are added
@@ -340,9 +303,7 @@ __global__ __launch_bounds__(64) void k_rt_loss_acc(const double *__restrict__ b
     for (int i = 0; i < c; ++i) {
         double s = 0.0;
         for (int b = lane; b < loss_blocks; b += 64) s += block_sums[(int64_t)i * loss_blocks + b];
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        a += s;
+        a += tc_wave_sum(s);
     }
     if (lane == 0) {
         *acc = a;
@@ -376,12 +337,7 @@ __global__ __launch_bounds__(256) void k_rt_adam(float *__restrict__ p, const fl
 // ================================================================================================
 CAELO_API int caelo_ring_train_param_layout(int64_t out[12][2]) {
     CAELO_REQUIRE(out != nullptr, "null argument");
-    int64_t o = 0;
-    for (int t = 0; t < 12; ++t) {
-        out[t][0] = o;
-        out[t][1] = RT_COUNT[t];
-        o += RT_COUNT[t];
-    }
+    tc_param_layout(RT_COUNT, 12, out);
     return CAELO_OK;
 }
 
@@ -426,7 +382,7 @@ static void rt_wgrad(const RtIn in, const float *delta, float *part, float *dst,
     const int group = tiles / 1024 < 1 ? 1 : (tiles / 1024 > 8 ? 8 : tiles / 1024);
     const int wgs = (tiles + group - 1) / group;
     k_rt_wgrad<CIN, COUT, KS, UP><<<(unsigned)wgs, 256, lds, s>>>(in, delta, part, h, w, tx, ty, tiles, group);
-    k_rt_wreduce<<<(count + 3) / 4, 256, 0, s>>>(part, (int64_t)wgs * KSPLIT, count, dst);
+    tc_wreduce(part, (int64_t)wgs * KSPLIT, count, dst, s);
 }
 
 static inline unsigned rt_blocks(int64_t total) { return (unsigned)((total + 255) / 256); }
@@ -500,11 +456,7 @@ CAELO_API int caelo_ring_autoencoder_grad(caelo_ctx *c, const float *params, con
 
 CAELO_API int caelo_adam_step(caelo_ctx *c, float *params, const float *grads, float *m, float *v, int64_t count, float lr_t, float beta1, float beta2,
                               float eps, void *stream) {
-    CAELO_REQUIRE(c != nullptr, "null context");
-    CAELO_REQUIRE(count >= 0 && count < ((int64_t)1 << 39), "count out of range");
-    if (count == 0) return CAELO_OK;
-    CAELO_REQUIRE(params && grads && m && v, "null argument");
-    k_rt_adam<<<(unsigned)((count + 255) / 256), 256, 0, caelo_stream(stream)>>>(params, grads, m, v, count, lr_t, beta1, beta2, eps);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return tc_optimizer_step(__func__, c, count, params && grads && m && v, stream, [&](unsigned blocks, hipStream_t s) {
+        k_rt_adam<<<blocks, 256, 0, s>>>(params, grads, m, v, count, lr_t, beta1, beta2, eps);
+    });
 }

@@ -14,37 +14,34 @@ point (the reference's batch of 1 536); 90 % of the shuffled scans train, 10 % v
 Single GPU: multi_gpu_model only splits a batch whose merged gradient is the one computed here.
 """
 import argparse
-import glob
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from caelo import train_cli as cli  # noqa: E402  (no torch, no library: --help stays cheap)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    src = ap.add_mutually_exclusive_group(required=True)
-    src.add_argument("--scans", help="directory of KITTI velodyne .bin files")
-    src.add_argument("--synthetic", type=int, help="number of synthetic 64x2000 scans (caelo.synth)")
+    cli.source(ap)
     ap.add_argument("--init", required=True, help="autoencoder .h5: the weights to fine-tune and the template of --out")
     ap.add_argument("--init-encoder", help="the encoder's .h5 when --init holds the decoder's weights only")
-    ap.add_argument("--glorot", type=int, metavar="SEED", help="start from fresh glorot_uniform weights (--init: shape and activations)")
-    ap.add_argument("--epochs", type=int, default=10)
-    ap.add_argument("--files-per-step", type=int, default=2)
+    cli.option(ap, "--glorot", help="start from fresh glorot_uniform weights (--init: shape and activations)")
+    cli.option(ap, "--epochs")
+    cli.option(ap, "--files-per-step", default=2)
     ap.add_argument("--chunk", type=int, default=256, help="patches whose activations are held at once (about 480 KB each)")
-    ap.add_argument("--seed", type=int, default=0, help="shuffles the scans and draws the training points")
+    cli.option(ap, "--seed", help="shuffles the scans and draws the training points")
     ap.add_argument("--out", required=True, help="the trained autoencoder .h5")
     ap.add_argument("--out-encoder", help="the trained encoder's .h5 (with --init-encoder)")
-    ap.add_argument("--log", help="per-epoch losses (.mat: loss, val_loss)")
+    cli.option(ap, "--log")
     a = ap.parse_args(argv)
-    if a.epochs < 1 or a.files_per_step < 1 or a.chunk < 1 or (a.synthetic is not None and a.synthetic < 1):
-        ap.error("--epochs, --files-per-step, --chunk and --synthetic must be >= 1")
+    cli.check(ap, a, a.chunk >= 1, "--epochs, --files-per-step, --chunk and --synthetic must be >= 1")
     if bool(a.init_encoder) != bool(a.out_encoder):
         ap.error("--init-encoder and --out-encoder go together")
     import caelo
-    from caelo import keras_config, stageio, synth, train
+    from caelo import keras_config, train
     from caelo.engine import Engine
     caelo.configure_runtime()
     ews, eact, dws, dact = keras_config.read_autoencoder(a.init)
@@ -55,13 +52,7 @@ def main(argv=None):
     if a.glorot is not None:
         fresh = train.glorot_uniform(train.SHAPES, np.random.RandomState(a.glorot))
         ews, dws = fresh[:10], fresh[10:]
-    if a.scans:
-        files = sorted(glob.glob(os.path.join(a.scans, "*.bin")))
-        if not files:
-            ap.error("no .bin files in %s" % a.scans)
-        scans = [lambda f=f: stageio.read_scan(f) for f in files]
-    else:
-        scans = [lambda f=f: synth.make_scan(f, quantum=1e-3) for f in range(a.synthetic)]
+    scans = cli.scans(ap, a)
     eng = Engine()
     tr = train.Trainer(eng, ews, eact, dws, dact, chunk=a.chunk)
     hist = train.fit(tr, scans, epochs=a.epochs, files_per_step=a.files_per_step, seed=a.seed)
@@ -71,10 +62,7 @@ def main(argv=None):
         keras_config.write_autoencoder_like(a.init, a.out, None, dws, activations=(eact, dact))
     else:
         keras_config.write_autoencoder_like(a.init, a.out, ews, dws, activations=(eact, dact))
-    if a.log:
-        from scipy import io
-        io.savemat(a.log, hist)
-    print("trained %d epochs: loss %.6f -> %.6f, val_loss %.6f -> %s" % (a.epochs, hist["loss"][0], hist["loss"][-1], hist["val_loss"][-1], a.out))
+    cli.finish(a, hist, a.out)
     return 0
 
 

@@ -15,49 +15,40 @@ validate; --log gets the per-epoch losses.  Single GPU: multi_gpu_model only spl
 here.
 """
 import argparse
-import glob
 import os
 import sys
 
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+from caelo import train_cli as cli  # noqa: E402  (no torch, no library: --help stays cheap)
 
 
 def main(argv=None):
     ap = argparse.ArgumentParser()
-    src = ap.add_mutually_exclusive_group(required=True)
-    src.add_argument("--scans", help="directory of KITTI velodyne .bin files")
-    src.add_argument("--synthetic", type=int, help="number of synthetic 64x2000 scans (caelo.synth)")
+    cli.source(ap)
     ap.add_argument("--init", required=True, help="ring autoencoder .h5: the weights to fine-tune and the template of --out")
-    ap.add_argument("--glorot", type=int, metavar="SEED", help="start from fresh glorot_uniform weights (--init: the template only)")
+    cli.option(ap, "--glorot", help="start from fresh glorot_uniform weights (--init: the template only)")
     ap.add_argument("--calib-angle", type=float, metavar="DEG", help="CorrectPC's vertical-angle calibration, applied before the projection")
-    ap.add_argument("--epochs", type=int, default=10)
-    ap.add_argument("--files-per-step", type=int, default=32)
+    cli.option(ap, "--epochs")
+    cli.option(ap, "--files-per-step", default=32)
     ap.add_argument("--chunk", type=int, default=4, help="images whose activations are held at once (54 MB each)")
-    ap.add_argument("--seed", type=int, default=0, help="shuffles the scans")
+    cli.option(ap, "--seed", help="shuffles the scans")
     ap.add_argument("--out", required=True, help="the trained autoencoder .h5")
     ap.add_argument("--out-respond", required=True, help="the trained response layer's .h5 (run_sequence.py --respond-h5)")
-    ap.add_argument("--log", help="per-epoch losses (.mat: loss, val_loss)")
+    cli.option(ap, "--log")
     a = ap.parse_args(argv)
-    if a.epochs < 1 or a.files_per_step < 1 or not 1 <= a.chunk <= 4096 or (a.synthetic is not None and a.synthetic < 1):
-        ap.error("--epochs, --files-per-step and --synthetic must be >= 1, --chunk in [1, 4096]")
+    cli.check(ap, a, 1 <= a.chunk <= 4096, "--epochs, --files-per-step and --synthetic must be >= 1, --chunk in [1, 4096]")
     if a.calib_angle is not None and not np.isfinite(a.calib_angle):
         ap.error("--calib-angle must be a finite number of degrees")
     import caelo
-    from caelo import keras_config, stageio, synth, train_ring
+    from caelo import keras_config, train_ring
     from caelo.engine import Engine
     caelo.configure_runtime()
     ws = keras_config.read_ring_autoencoder(a.init)
     if a.glorot is not None:
         ws = train_ring.glorot_uniform(keras_config.RING_AE_SHAPES, np.random.RandomState(a.glorot))
-    if a.scans:
-        files = sorted(glob.glob(os.path.join(a.scans, "*.bin")))
-        if not files:
-            ap.error("no .bin files in %s" % a.scans)
-        read = [lambda f=f: stageio.read_scan(f) for f in files]
-    else:
-        read = [lambda f=f: synth.make_scan(f, quantum=1e-3) for f in range(a.synthetic)]
+    read = cli.scans(ap, a)
     eng = Engine()
     if a.calib_angle is not None:
         import torch
@@ -67,10 +58,7 @@ def main(argv=None):
     tr = train_ring.RingTrainer(eng, ws, chunk=a.chunk)
     hist = train_ring.fit(tr, scans, epochs=a.epochs, files_per_step=a.files_per_step, seed=a.seed)
     keras_config.write_ring_models_like(a.init, a.out, tr.weights(), out_respond_h5=a.out_respond)
-    if a.log:
-        from scipy import io
-        io.savemat(a.log, hist)
-    print("trained %d epochs: loss %.6f -> %.6f, val_loss %.6f -> %s, %s" % (a.epochs, hist["loss"][0], hist["loss"][-1], hist["val_loss"][-1], a.out, a.out_respond))
+    cli.finish(a, hist, a.out, a.out_respond)
     return 0
 
 

@@ -1,9 +1,10 @@
 """CPU: what training rests on besides the kernels -- the torch reference checks itself against finite differences, Adadelta's NumPy
 restatement against torch.optim.Adadelta, ``keras_config.write_autoencoder_like`` on the fixture files, ``sample_training_points``
-against the literal loop, and the parameter layout of the C ABI."""
+against the literal loop, the parameter layout of the C ABI, and ``train.fit``'s shuffling, batching and generator with a stub trainer."""
 import ctypes as C
 import os
 import struct
+import types
 
 import numpy as np
 import pytest
@@ -211,3 +212,53 @@ def test_param_layout_is_the_shapes_cumulative_sizes():
     out = (C.c_int64 * 3)()
     assert lib.caelo_train_ws_layout(8, C.cast(out, C.c_void_p)) == 0 and 0 < out[0] < out[1] < out[2] < lib.caelo_train_ws_bytes(8)
     assert lib.caelo_train_ws_layout(0, C.cast(out, C.c_void_p)) == -1
+
+
+# ---- 6. fit ------------------------------------------------------------------------------------------------------------------------
+class _StubTrainer:
+    """Counts what ``fit`` feeds it: the stubbed ``training_patches`` marks each scan's three patches with the scan's id."""
+
+    def __init__(self):
+        self.steps, self.evals = [], []
+        self.eng = types.SimpleNamespace(device=torch.device("cpu"))
+
+    def step(self, bits, sync=True):
+        self.steps.append([int(v) for v in bits[:, 0]])
+        return torch.tensor([float(len(self.steps))])
+
+    def loss(self, bits):
+        self.evals.append([int(v) for v in bits[:, 0]])
+        return 0.5
+
+
+# the first number the shuffling generator gives a step's batch builder, recorded on the commit before the epoch loop was shared
+FIRST_DRAW = {1: 0.5507979025745755, 3: 0.7081478226181048, 5: 0.2909047389129443}
+
+
+@pytest.mark.parametrize("files,steps", [(1, 1), (3, 1), (5, 2)])
+def test_fit_takes_the_references_steps_per_pass(files, steps, monkeypatch):
+    """YieldBatchData's strict bound: L training files give (L - 1) // 2 steps per pass, at least one here; and the generator that
+    shuffled the scans is the one every step's ``training_patches`` draws from, in the state the shuffle left it in."""
+    from caelo import train
+    seen = []
+
+    def patches(eng, pc, n_groups, rng):
+        seen.append((rng, float(rng.random_sample())))
+        return torch.full((n_groups, 64), int(pc[0, 0]), dtype=torch.int64)
+
+    monkeypatch.setattr(train, "training_patches", patches)
+    tr = _StubTrainer()
+    hist = train.fit(tr, [lambda i=i: np.full((3, 4), float(i), np.float32) for i in range(files)], epochs=2, files_per_step=2, points_per_file=3,
+                     seed=3, train_ratio=1.0, log=None)
+    assert len(tr.steps) == 2 * steps and not tr.evals
+    assert np.isnan(hist["val_loss"]).all() and hist["val_loss"].shape == (2,)
+    rs = np.random.RandomState(3)
+    order = list(range(files))
+    rs.shuffle(order)
+    for s in range(steps):
+        want = [i for i in order[2 * s:2 * (s + 1)] for _ in range(3)]
+        assert tr.steps[s] == want == tr.steps[steps + s]          # shuffled once, the same pass every epoch
+    assert np.array_equal(hist["loss"], [np.mean(np.arange(e * steps, (e + 1) * steps) + 1.0) for e in range(2)])
+    assert all(r is seen[0][0] for r, _ in seen) and len(seen) == sum(len(b) // 3 for b in tr.steps)
+    assert seen[0][1] == FIRST_DRAW[files]
+    assert [d for _, d in seen] == [float(rs.random_sample()) for _ in seen]      # one generator: the shuffle, then every draw in turn
