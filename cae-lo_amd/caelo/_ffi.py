@@ -40,6 +40,11 @@ class IssParams(C.Structure):
                 ("min_neighbors", c_i32), ("reserved", c_i32)]
 
 
+class HarrisParams(C.Structure):
+    """caelo_harris_params (include/caelo.h)."""
+    _fields_ = [("radius", C.c_double), ("threshold", C.c_double)]
+
+
 class FrameJob(C.Structure):
     """caelo_frame_job (include/caelo.h): one frame of the pipeline, device pointers as integers."""
     _fields_ = [("pc", c_vp), ("n", c_i64), ("dist_channels", c_i32), ("mode", c_i32), ("rows", c_vp),
@@ -192,6 +197,8 @@ SIGNATURES = [
     ("caelo_kp_nn_pairs", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_int, c_vp, c_vp, c_vp]),
     ("caelo_iss_ws_bytes", c_i64, [c_i64, c_int]),
     ("caelo_iss_keypoints", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(IssParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    ("caelo_harris_ws_bytes", c_i64, [c_i64, c_int]),
+    ("caelo_harris_keypoints", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(HarrisParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     ("caelo_register_pairs_ws_bytes", c_i64, [c_i64]),
     ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes_dim", c_i64, [c_i64, c_int]),

@@ -17,6 +17,7 @@ tuples / dtypes, served by the HIP engine.
     Transformations.CorrectPC             :28   CorrectPC(PC, CalibAngle)
     PCLKeypoint.keypointIss (PclKeyPts.py:95)   KeyPtsByISS(PC, salient_radius=2, non_max_radius=2, gamma_21=0.975, gamma_32=0.975,
                                                             min_neighbors=5)
+    PCLKeypoint.keypointHarris (PclKeyPts.py:107) KeyPtsByHarris(PC, radius=1, threshold=0.001)
 
 Arguments may be NumPy arrays (results come back as NumPy, like the reference) or torch tensors on
 the GPU (results stay on the GPU).  Every array-level function runs on the GPU; there is no CPU
@@ -78,6 +79,20 @@ def KeyPtsByISS(PC, **params):
     e = default_engine()
     pts = _dev(PC, torch.float32)[:, 0:3].contiguous()
     r = e.iss_keypoints(pts, **params)
+    return _out(pts[r.key_idx[:int(r.n_key.item())].long()], _is_np(PC))
+
+
+def KeyPtsByHarris(PC, **params):
+    """PclKeyPts.py:105-112 (PCLKeypoint.keypointHarris, a PCL binding the reference does not ship) -> the Harris3D key points [K,3] f32
+    of the cloud PC [N, >=3], in scan order: the detector of DESIGN.md 9i on the device (caelo_harris_keypoints), PCL 1.8's
+    HarrisKeypoint3D (method HARRIS, non-maximum suppression, no refinement) as its model -- not its bits.  params:
+    caelo.harris.DEFAULTS.  N <= 32768 (an all-pairs search: downsample and subsample first, caelo.iss.voxel_downsample / subsample);
+    ValueError beyond that, for a non-finite coordinate and for bad parameters.  K may be 0."""
+    if PC.ndim != 2 or PC.shape[1] < 3:
+        raise ValueError("KeyPtsByHarris: PC must have shape [N, >= 3] (got %s)" % (tuple(PC.shape),))
+    e = default_engine()
+    pts = _dev(PC, torch.float32)[:, 0:3].contiguous()
+    r = e.harris_keypoints(pts, **params)
     return _out(pts[r.key_idx[:int(r.n_key.item())].long()], _is_np(PC))
 
 

@@ -40,6 +40,7 @@ DECODER_SHAPES = [(20, 200), (200,), (200, 2048), (2048,), (3, 3, 3, 32, 16), (1
 
 
 IssKeypoints = collections.namedtuple("IssKeypoints", "key_idx n_key saliency eig n_neigh")   # Engine.iss_keypoints
+HarrisKeypoints = collections.namedtuple("HarrisKeypoints", "key_idx n_key response n_neigh normals")   # Engine.harris_keypoints
 
 
 def _ptr(t):
@@ -977,6 +978,36 @@ class Engine:
                                               _ptr(dist), _ptr(counts), self.stream))
         return dist, counts
 
+    def _detector_frames(self, pts, n_pts, name):
+        """The input checks iss_keypoints and harris_keypoints share -> (pts [F, ld, 3] f32 contiguous, n_pts [F] i32 on the device,
+        whether pts came as one cloud [n, 3]).  ValueError for a wrong shape or dtype, ld above CAELO_ISS_MAX_POINTS, n_pts of the wrong
+        length or outside [0, ld], and -- the one read-back -- a non-finite coordinate in a frame's rows."""
+        from . import iss
+        pts = torch.as_tensor(pts, device=self.device)
+        single = pts.dim() == 2
+        if single:
+            pts = pts[None]
+        if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32:
+            raise ValueError("pts must be float32 [F, ld, 3] or [n, 3], got %s %s" % (pts.dtype, tuple(pts.shape[1:] if single else pts.shape)))
+        pts = pts.contiguous()
+        F, ld = int(pts.shape[0]), int(pts.shape[1])
+        if ld > iss.MAX_POINTS:
+            raise ValueError("ld = %d: %s takes at most %d points per frame (an all-pairs search; subsample the scan)" % (ld, name, iss.MAX_POINTS))
+        if n_pts is None:
+            np_d = torch.full((F,), ld, dtype=torch.int32, device=self.device)
+        else:
+            np_d = torch.as_tensor(n_pts, device=self.device).reshape(-1)
+            if np_d.shape[0] != F or np_d.dtype.is_floating_point:
+                raise ValueError("n_pts holds %d counts (%s) for %d frames" % (np_d.shape[0], np_d.dtype, F))
+            if F and ld and bool(((np_d < 0) | (np_d > ld)).any()):
+                raise ValueError("n_pts must lie in [0, ld = %d]" % ld)
+            np_d = np_d.to(torch.int32).contiguous()
+        if F and ld:
+            inside = torch.arange(ld, device=self.device)[None, :] < np_d[:, None]
+            if not bool(torch.isfinite(pts[inside]).all()):
+                raise ValueError("%s: a point has a non-finite coordinate" % name)
+        return pts, np_d, single
+
     def iss_keypoints(self, pts, n_pts=None, eig=False, **params):
         """ISS key points on the device (caelo_iss_keypoints, csrc/iss.hip; the definition: include/caelo.h).
 
@@ -991,34 +1022,14 @@ class Engine:
         n_pts may hold anything), ld above CAELO_ISS_MAX_POINTS, n_pts outside [0, ld], bad parameters (caelo.iss.check_params)."""
         from . import iss
         prm = iss.check_params(**params)
-        pts = torch.as_tensor(pts, device=self.device)
-        single = pts.dim() == 2
-        if single:
-            pts = pts[None]
-        if pts.dim() != 3 or pts.shape[2] != 3 or pts.dtype != torch.float32:
-            raise ValueError("pts must be float32 [F, ld, 3] or [n, 3], got %s %s" % (pts.dtype, tuple(pts.shape[1:] if single else pts.shape)))
-        pts = pts.contiguous()
+        pts, np_d, single = self._detector_frames(pts, n_pts, "ISS")
         F, ld = int(pts.shape[0]), int(pts.shape[1])
-        if ld > iss.MAX_POINTS:
-            raise ValueError("ld = %d: ISS takes at most %d points per frame (an all-pairs search; subsample the scan)" % (ld, iss.MAX_POINTS))
-        if n_pts is None:
-            np_d = torch.full((F,), ld, dtype=torch.int32, device=self.device)
-        else:
-            np_d = torch.as_tensor(n_pts, device=self.device).reshape(-1)
-            if np_d.shape[0] != F or np_d.dtype.is_floating_point:
-                raise ValueError("n_pts holds %d counts (%s) for %d frames" % (np_d.shape[0], np_d.dtype, F))
-            if F and ld and bool(((np_d < 0) | (np_d > ld)).any()):
-                raise ValueError("n_pts must lie in [0, ld = %d]" % ld)
-            np_d = np_d.to(torch.int32).contiguous()
         key_idx = self.empty((F, ld), torch.int32)
         n_key = self.zeros((F,), torch.int32)
         sal = self.empty((F, ld), torch.float64)
         ev = self.empty((F, ld, 3), torch.float64) if eig else None
         nn = self.empty((F, ld), torch.int32) if eig else None
         if F and ld:
-            inside = torch.arange(ld, device=self.device)[None, :] < np_d[:, None]
-            if not bool(torch.isfinite(pts[inside]).all()):
-                raise ValueError("ISS: a point has a non-finite coordinate")
             cp = _ffi.IssParams(prm["salient_radius"], prm["non_max_radius"], prm["gamma_21"], prm["gamma_32"], prm["min_neighbors"], 0)
             need = int(self.lib.caelo_iss_ws_bytes(F, ld))
             ws = self._ws("iss", need)
@@ -1026,6 +1037,36 @@ class Engine:
                                                     _ptr(key_idx), _ptr(n_key), _ptr(ws), need, self.stream))
         out = (key_idx, n_key, sal, ev, nn)
         return IssKeypoints(*[(t[0] if single and t is not None else t) for t in out])
+
+    def harris_keypoints(self, pts, n_pts=None, normals=False, **params):
+        """Harris3D key points on the device (caelo_harris_keypoints, csrc/harris.hip; the definition: include/caelo.h).
+
+        pts [F, ld, 3] f32 (frame f: rows 0 .. n_pts[f]-1; n_pts [F] ints or a device tensor, None = all ld rows) or one cloud
+        [n, 3]; params: radius, threshold (caelo.harris.DEFAULTS).
+        -> HarrisKeypoints(key_idx [F, ld] i32: the key points' row indices ascending, -1 behind them; n_key [F] i32; response [F, ld]
+        f64, -1 where a point has no normal; n_neigh [F, ld] i32, the neighbours within radius; normals [F, ld, 3] f64 facing the
+        origin, 0 where a point has none -- None unless ``normals``), on the device; a cloud [n, 3] gives the same without the frame
+        axis.  Three all-pairs passes (normals, response, suppression): n^2 pair distances each.
+
+        Refused with ValueError before any launch: a non-finite coordinate in a frame's rows (the one read-back of the call; rows past
+        n_pts may hold anything), ld above CAELO_ISS_MAX_POINTS, n_pts outside [0, ld], bad parameters (caelo.harris.check_params)."""
+        from . import harris
+        prm = harris.check_params(**params)
+        pts, np_d, single = self._detector_frames(pts, n_pts, "Harris3D")
+        F, ld = int(pts.shape[0]), int(pts.shape[1])
+        key_idx = self.empty((F, ld), torch.int32)
+        n_key = self.zeros((F,), torch.int32)
+        resp = self.empty((F, ld), torch.float64)
+        nn = self.empty((F, ld), torch.int32)
+        nv = self.empty((F, ld, 3), torch.float64) if normals else None
+        if F and ld:
+            cp = _ffi.HarrisParams(prm["radius"], prm["threshold"])
+            need = int(self.lib.caelo_harris_ws_bytes(F, ld))
+            ws = self._ws("harris", need)
+            _ffi.check(self.lib.caelo_harris_keypoints(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), _ptr(resp), _ptr(nv), _ptr(nn),
+                                                       _ptr(key_idx), _ptr(n_key), _ptr(ws), need, self.stream))
+        out = (key_idx, n_key, resp, nn, nv)
+        return HarrisKeypoints(*[(t[0] if single and t is not None else t) for t in out])
 
     def voxelize(self, pc, vmap=None, status=None):
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] >= 3 and pc.is_contiguous()

@@ -16,16 +16,9 @@
 // point index inside one thread, nothing is accumulated across threads and there are no atomics: a result is the same bits on
 // every run.  n_pts is clamped to [0, ld]; rows past it are never staged, so they never reach a decision; a NaN coordinate only
 // makes comparisons false, and every loop has a fixed bound.
-#include "caelo_internal.h"
-
 #pragma clang fp contract(off)
 
-#define ISS_TILE 256
-#define ISS_CHUNK 1024
-#define ISS_GROUP 4        // points per step of k_iss_scatter's inner loop
-#define ISS_SCAN 1024      // threads of k_iss_compact
-#define ISS_SWEEPS 12      // a 3 x 3 matrix is through after 5 or 6; the bound is what ends a matrix of NaNs
-#define ISS_MAX_GRID_Y 65535
+#include "iss_common.h"   // the sizes, iss_rotate, iss_stage, iss_d2: shared with harris.hip
 
 struct IssParams {
     double rs2, rn2;   // salient_radius^2, non_max_radius^2: one rounded product each
@@ -33,29 +26,6 @@ struct IssParams {
     int min_nb;
     int ld;
 };
-
-// One Jacobi rotation that annihilates a_pq; a_rp and a_rq are the other two off-diagonal entries (r the third index).
-// An entry that changes neither diagonal neighbour when added to it is set to zero without a rotation.  A zero a_pq is left alone,
-// and a row and column of zeros stay zeros: c * 0 - s * 0 and s * 0 + c * 0 are 0, and the diagonal entry is never touched.
-__device__ __forceinline__ void iss_rotate(double &app, double &aqq, double &apq, double &arp, double &arq) {
-    if (apq == 0.0) return;
-    const double g = fabs(apq);
-    if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
-        apq = 0.0;
-        return;
-    }
-    const double theta = __ddiv_rn(aqq - app, 2.0 * apq);
-    const double t = __ddiv_rn(copysign(1.0, theta), fabs(theta) + __dsqrt_rn(theta * theta + 1.0));   // (theta^2 = inf: t = 0)
-    const double c = __ddiv_rn(1.0, __dsqrt_rn(t * t + 1.0));
-    const double s = t * c;
-    const double h = t * apq;
-    app = app - h;
-    aqq = aqq + h;
-    apq = 0.0;
-    const double x = arp, y = arq;
-    arp = c * x - s * y;
-    arq = s * x + c * y;
-}
 
 // Eigenvalues e[0] >= e[1] >= e[2] of the symmetric matrix (a00 a01 a02; a01 a11 a12; a02 a12 a22): cyclic Jacobi, rotations in
 // the order (0,1), (0,2), (1,2), until the off-diagonal is exactly zero or ISS_SWEEPS sweeps are done.
@@ -71,18 +41,6 @@ __device__ __forceinline__ void iss_eigenvalues(double a00, double a01, double a
     if (a11 < a22) { t = a11; a11 = a22; a22 = t; }
     if (a00 < a11) { t = a00; a00 = a11; a11 = t; }
     e[0] = a00; e[1] = a11; e[2] = a22;
-}
-
-// stage points base .. base + m - 1 of the frame as float64 (between two barriers of the caller)
-__device__ __forceinline__ void iss_stage(const float *__restrict__ P, int base, int m, int tid, double *sx, double *sy, double *sz) {
-    for (int k = tid; k < m; k += ISS_TILE) {
-        const float *s = P + (size_t)(base + k) * 3;
-        sx[k] = (double)s[0]; sy[k] = (double)s[1]; sz[k] = (double)s[2];
-    }
-}
-
-__device__ __forceinline__ double iss_d2(double dx, double dy, double dz) {
-    return __dadd_rn(__dadd_rn(__dmul_rn(dx, dx), __dmul_rn(dy, dy)), __dmul_rn(dz, dz));
 }
 
 // acc = acc + (d_a * d_b), six sums
@@ -219,6 +177,12 @@ __global__ void __launch_bounds__(ISS_SCAN) k_iss_compact(const uint8_t *__restr
     if (tid == 0) n_key[f] = total;
 }
 
+int iss_launch_compact(const uint8_t *is_key, const int32_t *n_pts, int32_t *key_idx, int32_t *n_key, int ld, int64_t n_frames, hipStream_t s) {
+    k_iss_compact<<<dim3((unsigned)n_frames), ISS_SCAN, 0, s>>>(is_key, n_pts, key_idx, n_key, ld);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
 static bool iss_finite_positive(double v) { return v > 0.0 && v <= 1.7976931348623157e308; }
 
 CAELO_API int64_t caelo_iss_ws_bytes(int64_t n_frames, int ld) {
@@ -259,7 +223,5 @@ CAELO_API int caelo_iss_keypoints(caelo_ctx *c, const float *pts, int64_t n_fram
         k_iss_nms<<<grid, ISS_TILE, 0, s>>>(pts + o * 3, n_pts + f0, saliency + o, is_key + o, p);
         CAELO_LAUNCH_CHECK();
     }
-    k_iss_compact<<<dim3((unsigned)n_frames), ISS_SCAN, 0, s>>>(is_key, n_pts, key_idx, n_key, ld);
-    CAELO_LAUNCH_CHECK();
-    return CAELO_OK;
+    return iss_launch_compact(is_key, n_pts, key_idx, n_key, ld, n_frames, s);
 }

@@ -1,15 +1,17 @@
 #!/usr/bin/env python
-"""detect_keypoints.py -- key points of a hand-crafted detector for every scan of a directory, the rows 'iss' of the reference's key
-point comparison (PclKeyPts.py:63 lists cae-lo, 3dfeat-net, usip, iss, harris, sift; EvalOnReg_KeyPts.py:23).  The reference gets them
-from PCLKeypoint.keypointIss, a PCL binding it does not ship; here the detector runs on the GPU (caelo_iss_keypoints).
+"""detect_keypoints.py -- key points of a hand-crafted detector for every scan of a directory, the rows 'iss' and 'harris' of the
+reference's key point comparison (PclKeyPts.py:63 lists cae-lo, 3dfeat-net, usip, iss, harris, sift; EvalOnReg_KeyPts.py:23).  The
+reference gets them from PCLKeypoint.keypointIss / keypointHarris, a PCL binding it does not ship; here the detectors run on the GPU
+(caelo_iss_keypoints; caelo_harris_keypoints).
 
     python detect_keypoints.py --method iss --scans <seq>/velodyne --out iss_keypts/00
+    python detect_keypoints.py --method harris --scans <seq>/velodyne --out harris_keypts/00
     python run_sequence.py --scans <seq>/velodyne --python-loader --keypts-source 3dfeatnet --keypts-dir iss_keypts/00 --out poses_/00.txt
     python evaluate.py keypoints --keypts-dir iss_keypts/00 --source 3dfeatnet --gt poses/00.txt --calib calib_.txt --out acc.mat
 
 Per scan, as PclKeyPts.py:77-103 does it: the points are thinned to one per --leaf cell (the first in scan order), at most --max-points
 of them are kept (RandomState(--seed + frame).choice without replacement, like :81), the detector runs with the reference's parameters
-(:42-46), and the result is brought to exactly --keypoints points (ensure_keypoint_number, :20-28; the same RandomState goes on) unless
+(:42-46 for iss, :50-51 for harris), and the result is brought to exactly --keypoints points (ensure_keypoint_number, :20-28; the same RandomState goes on) unless
 --no-ensure.  --batch frames share one launch of every kernel.  Written as <frame:06d>.bin in LiDAR axes, float32, unrotated:
 --layout 3dfeatnet (default) [K,35] with zero descriptors, which run_sequence.py --keypts-source 3dfeatnet and evaluate.py keypoints
 --source 3dfeatnet read as they are; --layout xyz plain [K,3].
@@ -47,7 +49,7 @@ def prepare(eng, scan, frame, leaf, max_points, seed, calib_angle=None):
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description="hand-crafted key points over a directory of KITTI .bin scans (PclKeyPts.py)")
-    ap.add_argument("--method", required=True, choices=["iss"], help="the detector (harris and sift of the reference's list are not built)")
+    ap.add_argument("--method", required=True, choices=["iss", "harris"], help="the detector (sift of the reference's list is not built)")
     ap.add_argument("--scans", required=True, help="directory of KITTI velodyne .bin files ([N,4] float32)")
     ap.add_argument("--out", required=True, help="directory the key point files are written to (created)")
     ap.add_argument("--leaf", type=float, default=0.2, help="cell size in metres of the thinning before the detector (default 0.2)")
@@ -58,17 +60,25 @@ def main(argv=None):
     ap.add_argument("--calib-angle", type=float, default=None, metavar="DEG", help="correct raw KITTI scans first (CorrectPC; 0.22)")
     ap.add_argument("--layout", choices=["3dfeatnet", "xyz"], default="3dfeatnet")
     ap.add_argument("--batch", type=int, default=8, help="frames per launch (default 8)")
-    ap.add_argument("--salient-radius", type=float, default=2.0)
-    ap.add_argument("--non-max-radius", type=float, default=2.0)
-    ap.add_argument("--gamma-21", type=float, default=0.975)
-    ap.add_argument("--gamma-32", type=float, default=0.975)
-    ap.add_argument("--min-neighbors", type=int, default=5)
+    ap.add_argument("--salient-radius", type=float, default=None, help="iss (default 2.0)")
+    ap.add_argument("--non-max-radius", type=float, default=None, help="iss (default 2.0)")
+    ap.add_argument("--gamma-21", type=float, default=None, help="iss (default 0.975)")
+    ap.add_argument("--gamma-32", type=float, default=None, help="iss (default 0.975)")
+    ap.add_argument("--min-neighbors", type=int, default=None, help="iss (default 5)")
+    ap.add_argument("--radius", type=float, default=None, help="harris: the radius of normals, response and suppression (default 1.0)")
+    ap.add_argument("--threshold", type=float, default=None, help="harris: the least response of a key point (default 0.001)")
     args = ap.parse_args(argv)
 
-    from caelo import iss, keysources
+    from caelo import harris, iss, keysources
+    own = {"iss": ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors"), "harris": ("radius", "threshold")}
+    for method, names in own.items():
+        given = [n for n in names if getattr(args, n) is not None]
+        if method != args.method and given:
+            ap.error("%s belong%s to --method %s, not to --method %s"
+                     % (", ".join("--" + n.replace("_", "-") for n in given), "s" if len(given) == 1 else "", method, args.method))
+    given = {n: getattr(args, n) for n in own[args.method] if getattr(args, n) is not None}
     try:
-        prm = iss.check_params(salient_radius=args.salient_radius, non_max_radius=args.non_max_radius, gamma_21=args.gamma_21,
-                               gamma_32=args.gamma_32, min_neighbors=args.min_neighbors)
+        prm = (iss if args.method == "iss" else harris).check_params(**given)
     except ValueError as e:
         ap.error(str(e))
     if not (math.isfinite(args.leaf) and args.leaf > 0):
@@ -101,7 +111,8 @@ def main(argv=None):
         pts = torch.zeros((len(group), ld, 3), dtype=torch.float32, device=eng.device)
         for k, (pc, _) in enumerate(clouds):
             pts[k, :pc.shape[0]] = pc
-        r = eng.iss_keypoints(pts, n_pts=[pc.shape[0] for pc, _ in clouds], **prm)
+        detect = eng.iss_keypoints if args.method == "iss" else eng.harris_keypoints
+        r = detect(pts, n_pts=[pc.shape[0] for pc, _ in clouds], **prm)
         key_idx, n_key = r.key_idx.cpu().numpy(), r.n_key.cpu().numpy()
         for k, ((fr, _), (pc, rng)) in enumerate(zip(group, clouds)):
             cloud = pc.cpu().numpy()
@@ -114,8 +125,8 @@ def main(argv=None):
                 keysources.write_3dfeatnet(path, kp)
             else:
                 np.ascontiguousarray(kp, dtype=np.float32).tofile(path)
-    print("%d scans: ISS found %d .. %d key points per frame (mean %.1f)%s -> %s (%s layout)"
-          % (len(files), min(found), max(found), sum(found) / len(found),
+    print("%d scans: %s found %d .. %d key points per frame (mean %.1f)%s -> %s (%s layout)"
+          % (len(files), "ISS" if args.method == "iss" else "Harris3D", min(found), max(found), sum(found) / len(found),
              "" if args.no_ensure else ", brought to %d each" % args.keypoints, args.out, args.layout))
 
 

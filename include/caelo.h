@@ -605,6 +605,42 @@ int caelo_iss_keypoints(caelo_ctx *ctx, const float *pts /*[n_frames][ld][3] dev
                         int32_t *key_idx /*[n_frames][ld]*/, int32_t *n_key /*[n_frames]*/,
                         void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- Harris3D key points: the second hand-crafted detector of the key point comparison (PclKeyPts.py:50-51, :63; csrc/harris.hip) --
+ * (additive; the ABI version stays 6.)  The reference calls PCLKeypoint.keypointHarris; the model is PCL 1.8's HarrisKeypoint3D, method
+ * HARRIS, non-maximum suppression on, refinement off, normals from NormalEstimation at the same radius.  The definition is the one
+ * below, and bit parity with PCL is not claimed.  pts, n_pts: as for caelo_iss_keypoints.  All arithmetic is float64,
+ * every operation rounded on its own (IEEE division and square root), sums in ascending point index:
+ *   neighbours   as in ISS: j is a neighbour of i <=> d2 < radius * radius (strict; one rounded product; i is its own neighbour)
+ *   normal       k neighbours; k < 3: invalid.  Otherwise S_a = sum d_a and S_ab = sum d_a * d_b over the neighbours (nine sums in one
+ *                pass), C_ab = S_ab - (S_a * S_b) / double(k); the normal is the unit eigenvector of C's smallest eigenvalue: the cyclic
+ *                Jacobi of the ISS eigenvalues (same rotation order, formulas, skip rule, 12-sweep bound) with the rotations
+ *                accumulated into V from the identity, the column of the smallest diagonal entry (lowest index on a tie) divided by
+ *                sqrt((x*x + y*y) + z*z) -- a pure function of the six entries; a row and column that are exactly zero keep their
+ *                unit vector exactly.  If (n_x*p_x + n_y*p_y) + n_z*p_z > 0 the normal is negated: it faces the sensor at the origin.
+ *                Nothing below depends on the sign.
+ *   response     invalid normal: -1.  Otherwise c = the neighbours with a valid normal (>= 1: the point itself),
+ *                N_ab = (sum n_a * n_b) / double(c) over them for (xx, xy, xz, yy, yz, zz), tr = (N_xx + N_yy) + N_zz,
+ *                det = (((N_xx*N_yy)*N_zz + (2*N_xy)*N_xz*N_yz) - (N_xz*N_xz)*N_yy - (N_xy*N_xy)*N_zz) - (N_yz*N_yz)*N_xx, left to
+ *                right; response = (0.04 + det) - (0.04*tr)*tr if tr != 0, else 0 (PCL's expression; in [0, 1/27] to rounding)
+ *   key point    valid normal, response >= threshold, and no neighbour j with a valid normal has response[i] < response[j] (equal
+ *                responses both survive)
+ * Outputs (device): response [n_frames][ld] f64; normals [n_frames][ld][3] f64 (nullable); n_neigh [n_frames][ld] i32 (nullable);
+ * key_idx [n_frames][ld] i32, the key points' indices in ascending order, -1 behind them; n_key [n_frames] i32.  Rows n_pts[f] .. ld-1
+ * get response -1, normal 0 and 0 neighbours.  The same input gives the same bits on every run and in every batch composition (no
+ * atomics, no cross-thread sums); a NaN coordinate only makes comparisons false.  Four kernels, each one launch for all frames (the
+ * three all-pairs passes in slices of 65 535 frames); ws: caelo_harris_ws_bytes(n_frames, ld) bytes, no initialisation, one per call
+ * in flight.  prm is HOST memory.  Refused before any launch (CAELO_ERR_ARG): null arguments, ld outside [1, CAELO_ISS_MAX_POINTS],
+ * n_frames < 0, a radius that is not finite and positive, a threshold that is not finite or is negative, a short workspace.
+ * n_frames == 0 is a no-op.  The call does not synchronise.  The work is n_pts^2 pair distances per frame and pass. */
+typedef struct { double radius, threshold; } caelo_harris_params;
+int64_t caelo_harris_ws_bytes(int64_t n_frames, int ld);
+int caelo_harris_keypoints(caelo_ctx *ctx, const float *pts /*[n_frames][ld][3] device*/, int64_t n_frames, int ld,
+                           const int32_t *n_pts /*[n_frames] device*/, const caelo_harris_params *prm /*host*/,
+                           double *response /*[n_frames][ld]*/, double *normals /*[n_frames][ld][3]; nullable*/,
+                           int32_t *n_neigh /*[n_frames][ld]; nullable*/,
+                           int32_t *key_idx /*[n_frames][ld]*/, int32_t *n_key /*[n_frames]*/,
+                           void *ws, int64_t ws_bytes, void *stream);
+
 /* ---- frame pipeline: batches of frames behind single launches, three stages on three HIP streams ------------------
  * Replaces the reference's per-frame driver loops (BatchPreprocess.py:88-140 extract loop, Match.py:296-353 /
  * PoseEstimation.py pair loop) for throughput.  `batch` consecutive frames share ONE launch of every kernel of the
