@@ -1008,6 +1008,20 @@ class Engine:
                 raise ValueError("%s: a point has a non-finite coordinate" % name)
         return pts, np_d, single
 
+    def _detect(self, sym, name, pts, n_pts, cp, outputs):
+        """What iss_keypoints and harris_keypoints share round caelo_<sym>_keypoints: the frames checked (_detector_frames), key_idx and
+        n_key allocated beside the detector's three ``outputs(F, ld)`` (in the C order; None = not wanted), the workspace fetched, the
+        call -> [key_idx, n_key, *outputs], without the frame axis for a single cloud."""
+        pts, np_d, single = self._detector_frames(pts, n_pts, name)
+        F, ld = int(pts.shape[0]), int(pts.shape[1])
+        out = [self.empty((F, ld), torch.int32), self.zeros((F,), torch.int32), *outputs(F, ld)]
+        if F and ld:
+            need = int(getattr(self.lib, "caelo_%s_ws_bytes" % sym)(F, ld))
+            ws = self._ws(sym, need)
+            _ffi.check(getattr(self.lib, "caelo_%s_keypoints" % sym)(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), *[_ptr(t) for t in out[2:]],
+                                                                      _ptr(out[0]), _ptr(out[1]), _ptr(ws), need, self.stream))
+        return [(t[0] if single and t is not None else t) for t in out]
+
     def iss_keypoints(self, pts, n_pts=None, eig=False, **params):
         """ISS key points on the device (caelo_iss_keypoints, csrc/iss.hip; the definition: include/caelo.h).
 
@@ -1022,21 +1036,10 @@ class Engine:
         n_pts may hold anything), ld above CAELO_ISS_MAX_POINTS, n_pts outside [0, ld], bad parameters (caelo.iss.check_params)."""
         from . import iss
         prm = iss.check_params(**params)
-        pts, np_d, single = self._detector_frames(pts, n_pts, "ISS")
-        F, ld = int(pts.shape[0]), int(pts.shape[1])
-        key_idx = self.empty((F, ld), torch.int32)
-        n_key = self.zeros((F,), torch.int32)
-        sal = self.empty((F, ld), torch.float64)
-        ev = self.empty((F, ld, 3), torch.float64) if eig else None
-        nn = self.empty((F, ld), torch.int32) if eig else None
-        if F and ld:
-            cp = _ffi.IssParams(prm["salient_radius"], prm["non_max_radius"], prm["gamma_21"], prm["gamma_32"], prm["min_neighbors"], 0)
-            need = int(self.lib.caelo_iss_ws_bytes(F, ld))
-            ws = self._ws("iss", need)
-            _ffi.check(self.lib.caelo_iss_keypoints(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), _ptr(sal), _ptr(ev), _ptr(nn),
-                                                    _ptr(key_idx), _ptr(n_key), _ptr(ws), need, self.stream))
-        out = (key_idx, n_key, sal, ev, nn)
-        return IssKeypoints(*[(t[0] if single and t is not None else t) for t in out])
+        cp = _ffi.IssParams(prm["salient_radius"], prm["non_max_radius"], prm["gamma_21"], prm["gamma_32"], prm["min_neighbors"], 0)
+        return IssKeypoints(*self._detect("iss", "ISS", pts, n_pts, cp, lambda F, ld: (
+            self.empty((F, ld), torch.float64), self.empty((F, ld, 3), torch.float64) if eig else None,
+            self.empty((F, ld), torch.int32) if eig else None)))
 
     def harris_keypoints(self, pts, n_pts=None, normals=False, **params):
         """Harris3D key points on the device (caelo_harris_keypoints, csrc/harris.hip; the definition: include/caelo.h).
@@ -1052,21 +1055,11 @@ class Engine:
         n_pts may hold anything), ld above CAELO_ISS_MAX_POINTS, n_pts outside [0, ld], bad parameters (caelo.harris.check_params)."""
         from . import harris
         prm = harris.check_params(**params)
-        pts, np_d, single = self._detector_frames(pts, n_pts, "Harris3D")
-        F, ld = int(pts.shape[0]), int(pts.shape[1])
-        key_idx = self.empty((F, ld), torch.int32)
-        n_key = self.zeros((F,), torch.int32)
-        resp = self.empty((F, ld), torch.float64)
-        nn = self.empty((F, ld), torch.int32)
-        nv = self.empty((F, ld, 3), torch.float64) if normals else None
-        if F and ld:
-            cp = _ffi.HarrisParams(prm["radius"], prm["threshold"])
-            need = int(self.lib.caelo_harris_ws_bytes(F, ld))
-            ws = self._ws("harris", need)
-            _ffi.check(self.lib.caelo_harris_keypoints(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), _ptr(resp), _ptr(nv), _ptr(nn),
-                                                       _ptr(key_idx), _ptr(n_key), _ptr(ws), need, self.stream))
-        out = (key_idx, n_key, resp, nn, nv)
-        return HarrisKeypoints(*[(t[0] if single and t is not None else t) for t in out])
+        cp = _ffi.HarrisParams(prm["radius"], prm["threshold"])
+        key_idx, n_key, resp, nv, nn = self._detect("harris", "Harris3D", pts, n_pts, cp, lambda F, ld: (
+            self.empty((F, ld), torch.float64), self.empty((F, ld, 3), torch.float64) if normals else None,
+            self.empty((F, ld), torch.int32)))
+        return HarrisKeypoints(key_idx, n_key, resp, nn, nv)
 
     def voxelize(self, pc, vmap=None, status=None):
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] >= 3 and pc.is_contiguous()

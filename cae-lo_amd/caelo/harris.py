@@ -2,20 +2,10 @@
 checks of the C ABI.  The plumbing round the detector call (thinning, subsampling, ensure_keypoint_number) is caelo.iss's, shared by
 both detectors.  Importable without a GPU.  The detector itself runs on the device only; nothing here computes a key point.
 """
-import math
-
-from .iss import MAX_POINTS, ensure_keypoint_number, subsample, voxel_downsample  # noqa: F401  (one copy for both detectors)
+from .iss import MAX_POINTS, _finite, ensure_keypoint_number, subsample, voxel_downsample  # noqa: F401  (one copy for both detectors)
 
 # PclKeyPts.py:50-51
 DEFAULTS = dict(radius=1.0, threshold=0.001)
-
-
-def _finite(v):
-    try:
-        v = float(v)
-    except (TypeError, ValueError):
-        return False
-    return math.isfinite(v)
 
 
 def check_params(**params):

@@ -11,12 +11,16 @@ DEFAULTS = dict(salient_radius=2.0, non_max_radius=2.0, gamma_21=0.975, gamma_32
 MAX_POINTS = 32768   # include/caelo.h CAELO_ISS_MAX_POINTS
 
 
-def _finite_positive(v):
+def _finite(v):
+    """Whether v is a number with a finite float value (caelo.harris checks its parameters with it too)."""
     try:
-        v = float(v)
+        return math.isfinite(float(v))
     except (TypeError, ValueError):
         return False
-    return math.isfinite(v) and v > 0.0
+
+
+def _finite_positive(v):
+    return _finite(v) and float(v) > 0.0
 
 
 def check_params(**params):

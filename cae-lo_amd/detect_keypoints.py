@@ -70,15 +70,16 @@ def main(argv=None):
     args = ap.parse_args(argv)
 
     from caelo import harris, iss, keysources
-    own = {"iss": ("salient_radius", "non_max_radius", "gamma_21", "gamma_32", "min_neighbors"), "harris": ("radius", "threshold")}
-    for method, names in own.items():
-        given = [n for n in names if getattr(args, n) is not None]
+    # per method: the module whose DEFAULTS name its options and whose check_params checks them, and its printed name
+    methods = {"iss": (iss, "ISS"), "harris": (harris, "Harris3D")}
+    for method, (mod, _) in methods.items():
+        given = [n for n in mod.DEFAULTS if getattr(args, n) is not None]
         if method != args.method and given:
             ap.error("%s belong%s to --method %s, not to --method %s"
                      % (", ".join("--" + n.replace("_", "-") for n in given), "s" if len(given) == 1 else "", method, args.method))
-    given = {n: getattr(args, n) for n in own[args.method] if getattr(args, n) is not None}
+    mod, shown = methods[args.method]
     try:
-        prm = (iss if args.method == "iss" else harris).check_params(**given)
+        prm = mod.check_params(**{n: getattr(args, n) for n in mod.DEFAULTS if getattr(args, n) is not None})
     except ValueError as e:
         ap.error(str(e))
     if not (math.isfinite(args.leaf) and args.leaf > 0):
@@ -111,8 +112,7 @@ def main(argv=None):
         pts = torch.zeros((len(group), ld, 3), dtype=torch.float32, device=eng.device)
         for k, (pc, _) in enumerate(clouds):
             pts[k, :pc.shape[0]] = pc
-        detect = eng.iss_keypoints if args.method == "iss" else eng.harris_keypoints
-        r = detect(pts, n_pts=[pc.shape[0] for pc, _ in clouds], **prm)
+        r = getattr(eng, args.method + "_keypoints")(pts, n_pts=[pc.shape[0] for pc, _ in clouds], **prm)
         key_idx, n_key = r.key_idx.cpu().numpy(), r.n_key.cpu().numpy()
         for k, ((fr, _), (pc, rng)) in enumerate(zip(group, clouds)):
             cloud = pc.cpu().numpy()
@@ -126,7 +126,7 @@ def main(argv=None):
             else:
                 np.ascontiguousarray(kp, dtype=np.float32).tofile(path)
     print("%d scans: %s found %d .. %d key points per frame (mean %.1f)%s -> %s (%s layout)"
-          % (len(files), "ISS" if args.method == "iss" else "Harris3D", min(found), max(found), sum(found) / len(found),
+          % (len(files), shown, min(found), max(found), sum(found) / len(found),
              "" if args.no_ensure else ", brought to %d each" % args.keypoints, args.out, args.layout))
 
 

@@ -146,3 +146,31 @@ def exact_plane():
     rs = np.random.RandomState(11)
     xy = rs.randint(0, 8 * 64, size=(200, 2)).astype(np.float64) / 64.0
     return np.ascontiguousarray(np.c_[xy, np.zeros(200)], dtype=np.float32)
+
+
+MANY_FRAMES = 65537   # two more than one launch takes as its grid's y (65 535): the entry points slice the frames
+
+
+def many_frames():
+    """-> (pts [65 537, 4, 3] f32, n_pts [65 537] i32): frame f holds f % 5 points of a bent line, k = 0 .. 3 at
+    (k, k^2 / 4, (k % 3) / 2) * (0.25 + (f % 7) / 8) + ((f % 64) / 4, 0, 0); the rows past n_pts are NaN.  At radius 1 the spacings give
+    every neighbour count from 1 to 4."""
+    f = np.arange(MANY_FRAMES)
+    k = np.arange(4, dtype=np.float64)
+    pts = np.stack([k, k * k / 4.0, (k % 3) / 2.0], axis=-1)[None] * (0.25 + (f % 7) / 8.0)[:, None, None]
+    pts[:, :, 0] += ((f % 64) / 4.0)[:, None]
+    n_pts = (f % 5).astype(np.int32)
+    pts[k[None, :] >= n_pts[:, None]] = np.nan
+    return np.ascontiguousarray(pts, dtype=np.float32), n_pts
+
+
+def neighbour_counts(pts, n_pts, radius):
+    """pts [F, ld, 3] f32, n_pts [F] -> [F, ld] i32: per point the points of its frame with d2 < radius * radius, as the device rounds
+    them (itself included); 0 in the rows past n_pts."""
+    P = pts.astype(np.float64)
+    d = P[:, None, :, :] - P[:, :, None, :]   # [F, i, j, 3]
+    d2 = (d[..., 0] * d[..., 0] + d[..., 1] * d[..., 1]) + d[..., 2] * d[..., 2]
+    inside = np.arange(pts.shape[1])[None, :] < np.asarray(n_pts)[:, None]
+    with np.errstate(invalid="ignore"):
+        near = (d2 < np.float64(radius) * np.float64(radius)) & inside[:, :, None] & inside[:, None, :]
+    return near.sum(axis=2).astype(np.int32)

@@ -133,6 +133,29 @@ def test_a_padded_batch_equals_single_calls_and_repeats_itself(eng):
             assert same_bits(np.ascontiguousarray(batch[k][f, :n]), one[k]), (f, k)
 
 
+def test_more_frames_than_one_launch_takes(eng):
+    """65 537 frames of 0 .. 4 points under ld = 4: the entry point slices them at 65 535.  Every output is the bits of two calls on
+    the frames before and from the cut, the frames at both ends of both slices are their single-cloud calls, and the neighbour counts
+    are NumPy's over all frames."""
+    kw = dict(salient_radius=1.0, non_max_radius=1.0, min_neighbors=3)
+    pts, n_pts = iss_ref.many_frames()
+    cut = 65535
+    assert pts.shape == (cut + 2, 4, 3)
+    whole = run(eng, pts, n_pts=n_pts, **kw)
+    head, tail = run(eng, pts[:cut], n_pts=n_pts[:cut], **kw), run(eng, pts[cut:], n_pts=n_pts[cut:], **kw)
+    for k in whole:
+        assert same_bits(whole[k], np.concatenate([head[k], tail[k]])), k
+    assert np.array_equal(whole["n_neigh"], iss_ref.neighbour_counts(pts, n_pts, 1.0))
+    assert whole["n_key"].sum() > 0 and whole["n_neigh"][cut + 1].tolist() == [1, 0, 0, 0]
+    for f in (0, cut - 1, cut, cut + 1):
+        n = int(n_pts[f])
+        one = run(eng, pts[f, :n], **kw)
+        nk = int(one["n_key"])
+        assert int(whole["n_key"][f]) == nk and same_bits(whole["key_idx"][f, :nk], one["key_idx"][:nk]) and (whole["key_idx"][f, nk:] == -1).all()
+        for k in ("saliency", "eig", "n_neigh"):
+            assert same_bits(np.ascontiguousarray(whole[k][f, :n]), one[k]), (f, k)
+
+
 def test_refusals_leave_the_context_usable(eng):
     P = iss_ref.reference(*iss_ref.SCENES[3])[0]
     bad = P.copy()
