@@ -161,6 +161,7 @@ SIGNATURES = [
     ("caelo_host_certify", c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_int]),
     ("caelo_extract_ws_bytes", c_i64, []),
     ("caelo_extract_ws_frame_offset", c_i64, []),
+    ("caelo_extract_ws_kp_eligible_offset", c_i64, []),
     ("caelo_extract", c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp]),
     ("caelo_extend_ws_bytes", c_i64, [c_int, c_int]),

@@ -1465,6 +1465,15 @@ class Engine:
         tab = raw[n * 512:].view(np.int32)
         return raw[:n * 512].view(np.uint64).reshape(n, 64), int(tab[0]), tab[64:64 + n].copy(), tab[64 + n:64 + 2 * n].copy()
 
+    def extract_kp_eligible(self):
+        """Test aid: the key point eligibility map the last ``extract`` on the current stream left in its workspace
+        (caelo_extract_ws_kp_eligible_offset) -> host array [64] uint64, bit b of word y = some pixel of columns 32 b .. 32 b + 31
+        of ring row y passes the rule's range gate.  Synchronises."""
+        ws = self._ws("extract", int(self.lib.caelo_extract_ws_bytes()))
+        off = int(self.lib.caelo_extract_ws_kp_eligible_offset())
+        torch.cuda.current_stream(self.device).synchronize()
+        return ws[off:off + 512].cpu().numpy().view(np.uint64).copy()
+
     def extract_patch_bits(self):
         """The bit-packed patches the last ``extract`` on the current stream gathered -> [1024,3,64] int64 (device, a copy; rows past
         ``n_key`` are not meaningful).  No host sync."""

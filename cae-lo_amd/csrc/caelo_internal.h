@@ -174,6 +174,7 @@ struct caelo_frame_dev {
     float *resp;                  // [64][1792][8]
     unsigned long long *cand;
     int32_t *cand_count;
+    unsigned long long *kp_elig;  // [64] eligibility map (k_ring_fill; null: the staged entry points, everything is computed)
     int64_t *key_pixels;
     float *key_pts, *valid;
     int32_t *n_key;

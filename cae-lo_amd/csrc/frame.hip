@@ -113,7 +113,7 @@ int caelo_clear_many_set(const caelo_clear_list *lists, int n_frames, hipStream_
 // fused extract
 // ------------------------------------------------------------------------------------------------
 struct ExtractLayout {
-    size_t ring, winner, resp, cand, cand_count, bits, dd, enc, total;
+    size_t ring, winner, resp, cand, cand_count, kp_elig, bits, dd, enc, total;
 };
 
 static inline size_t align256(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -122,9 +122,10 @@ static ExtractLayout extract_layout() {
     ExtractLayout L;
     size_t off = 0;
     const size_t npix = (size_t)CAELO_RING_H * CAELO_RING_W;
-    // winner | cand_count are cleared together: keep them adjacent
+    // winner | cand_count | eligibility map are cleared together: keep them adjacent
     L.winner = off; off += align256(npix * 4);
     L.cand_count = off; off += 256;
+    L.kp_elig = off; off += CAELO_NET_H * 8;   // (behind cand_count: wiped by its clear item)
     L.ring = off; off += align256(npix * CAELO_RING_C * 4);
     L.resp = off; off += align256((size_t)CAELO_NET_H * CAELO_NET_W * 8 * 4);
     L.cand = off; off += align256((size_t)CAELO_NET_H * CAELO_NET_W * 8);
@@ -138,6 +139,8 @@ static ExtractLayout extract_layout() {
 CAELO_API int64_t caelo_extract_ws_bytes(void) { return (int64_t)extract_layout().total; }
 // (read-only, for tests of the de-duplication tables: where the last frame's patch bits and caelo_dedup_tables lie in the workspace)
 CAELO_API int64_t caelo_extract_ws_frame_offset(void) { return (int64_t)extract_layout().bits; }
+// (read-only, for tests of the key point eligibility map: k_ring_fill's 64 row words)
+CAELO_API int64_t caelo_extract_ws_kp_eligible_offset(void) { return (int64_t)extract_layout().kp_elig; }
 
 // The fused path in two halves so that the frame pipeline can put an event edge between them:
 // front = clear + ring image + response + keypoints + voxel map + patch gather (latency-bound kernels),
@@ -222,6 +225,7 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
         d.pc = correct ? a.map->corr : a.pc; d.n = a.n; d.pc_stride = 4; d.dist_c = a.dist_channels;
         d.ring = (float *)(ws + L.ring); d.counter = nullptr; d.winner = (int32_t *)(ws + L.winner);  // (occupied = has a winner)
         d.resp = (float *)(ws + L.resp); d.cand = (unsigned long long *)(ws + L.cand); d.cand_count = (int32_t *)(ws + L.cand_count);
+        d.kp_elig = (unsigned long long *)(ws + L.kp_elig);
         d.key_pixels = a.key_pixels; d.key_pts = a.key_pts; d.kp_ld = a.kp_ld; d.valid = a.valid; d.valid_ld = a.valid_ld;
         d.n_key = a.n_key; d.flags = a.flags; d.status = a.status;
         d.bits = (unsigned long long *)(a.bits ? a.bits : (uint64_t *)(ws + L.bits));

@@ -136,9 +136,10 @@ __global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) {
     if (pix >= CAELO_RING_H * CAELO_RING_W) return;
     const int w = winner[pix];
     float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float s = 0.f;
     if (w >= 0) {
         const float4 p = pc[w];
-        float s = __fmul_rn(p.x, p.x);
+        s = __fmul_rn(p.x, p.x);
         s = __fadd_rn(s, __fmul_rn(p.y, p.y));
         s = __fadd_rn(s, __fmul_rn(p.z, p.z));
         v[0] = p.x; v[1] = p.y; v[2] = p.z; v[3] = p.w; v[4] = sqrtf(s);         // :91-92
@@ -146,6 +147,49 @@ __global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) {
     float *o = ring + (int64_t)pix * CAELO_RING_C;
 #pragma unroll
     for (int c = 0; c < 5; ++c) o[c] = v[c];
+    // The key point rule's range gate (SphericalRing.py:197-198) as a map for the two kernels behind: bit b of word y = some pixel of
+    // columns 32 b .. 32 b + 31 of net row y is occupied and far enough.  The gate is k_kp_score's, `sqrtf(d2) >= 10.0f` with d2 the
+    // squares of channels 0 .. dist_c - 1 summed in channel order -- its first three terms are `s` above, operation for operation --
+    // written as d2 >= 99.99999237 (0x42C7FFFF): the correctly rounded square root is monotone and that is the smallest float whose
+    // root rounds to 10 (the one below gives 9.999999; tests/test_kp_eligible_host.py walks the floats around it).  NaN fails, +inf
+    // passes, as there.  Everything after the ballot is wave-uniform: the wave's 64 pixels are lanes [0, n0) of its first lane's row
+    // (up to three blocks) and, past the row's end (1800 is no multiple of 64), columns 0 .. of the next row (two blocks).  The
+    // workgroup's 256 pixels lie in two rows: its waves meet in LDS and two lanes issue one atomic per row word (a frame's 64 words
+    // are four cache lines; one atomic per wave and word, ~2000 per frame, cost the kernel 3 us of 9.5).
+    // (The image's last workgroup is cut short by the return above; it lies below the net rows and leaves here before the barriers.)
+    unsigned long long *const kmap = F.kp_elig;
+    const int wg0 = blockIdx.x * blockDim.x;
+    if (!kmap || wg0 >= CAELO_NET_H * CAELO_RING_W) return;
+    __shared__ unsigned long long s_rows[2];
+    if (threadIdx.x < 2) s_rows[threadIdx.x] = 0ull;
+    caelo_lds_barrier();
+    const int rw = wg0 / CAELO_RING_W;
+    float d2 = s;
+    if (F.dist_c > 3) d2 = __fadd_rn(d2, __fmul_rn(v[3], v[3]));
+    if (F.dist_c > 4) d2 = __fadd_rn(d2, __fmul_rn(v[4], v[4]));
+    const unsigned long long E = __ballot(w >= 0 && d2 >= __uint_as_float(0x42C7FFFFu));
+    const int pix0 = __builtin_amdgcn_readfirstlane(pix);
+    const int r0 = pix0 / CAELO_RING_W, c0 = pix0 - r0 * CAELO_RING_W;
+    if (E != 0ull && r0 < CAELO_NET_H) {
+        const int n0 = CAELO_RING_W - c0 < 64 ? CAELO_RING_W - c0 : 64;                    // lanes of row r0
+        const int in0 = CAELO_NET_W - c0 < n0 ? (CAELO_NET_W - c0 > 0 ? CAELO_NET_W - c0 : 0) : n0;   // ... of its net columns
+        const unsigned long long E0 = in0 < 64 ? E & ((1ull << in0) - 1ull) : E;
+        const unsigned long long E1 = n0 < 64 && r0 + 1 < CAELO_NET_H ? E >> n0 : 0ull;  // lane n0 + j = column j of row r0 + 1
+        const int b0 = c0 >> 5, l1 = 32 - (c0 & 31);                                       // lanes [0, l1) lie in block b0
+        const unsigned long long rest = E0 >> l1;                                          // (1 <= l1 <= 32)
+        // (32-bit pieces through readfirstlane: scalar work, and a convergent operation is not sunk under the one-lane branch below)
+        const unsigned int hit0 = __builtin_amdgcn_readfirstlane((E0 & ((1ull << l1) - 1ull)) != 0ull ? 1u : 0u) |
+                                  __builtin_amdgcn_readfirstlane((unsigned int)rest != 0u ? 2u : 0u) |
+                                  __builtin_amdgcn_readfirstlane((unsigned int)(rest >> 32) != 0u ? 4u : 0u);
+        const unsigned int hit1 = __builtin_amdgcn_readfirstlane((unsigned int)E1 != 0u ? 1u : 0u) |
+                                  __builtin_amdgcn_readfirstlane((unsigned int)(E1 >> 32) != 0u ? 2u : 0u);
+        if ((threadIdx.x & 63) == 0) {
+            if (hit0) atomicOr(&s_rows[r0 - rw], (unsigned long long)hit0 << b0);   // (b0 <= 56; a set bit: block < 56)
+            if (hit1) atomicOr(&s_rows[1], (unsigned long long)hit1);               // (a wave that crosses the row's end began in row rw)
+        }
+    }
+    caelo_lds_barrier();
+    if (threadIdx.x < 2 && s_rows[threadIdx.x] != 0ull) atomicOr(&kmap[rw + threadIdx.x], s_rows[threadIdx.x]);   // (a set bit: a net row)
 }
 
 static int64_t set_max_points(const caelo_frame_set &fs) {
@@ -248,6 +292,21 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
     const int lane = threadIdx.x, g = lane >> 4, n = lane & 15;
     const int y = blockIdx.y + row0;
     constexpr int NBLK = CAELO_NET_W / RESP_BPX, NLD = (RESP_STAGE + 63) / 64;
+    // The blocks of this row that some key point centre can read (the fused path; a null map: all of them).  k_ring_fill's map has
+    // a bit per (row, block) holding a pixel that passes the rule's range gate; a response value is read only in the 5 x 5 window of
+    // such a centre, so block (y, b) is needed iff a bit is set in rows y - 2 .. y + 2, blocks b - 1 .. b + 1 (a block either side
+    // covers the two columns either side).  Wave-uniform: five scalar loads and a few scalar ops; a wave with nothing to do
+    // leaves before its first load.  The blocks it skips keep whatever an earlier frame left in the response image.
+    static_assert(NBLK <= 64 && CAELO_NET_H <= 64, "one map word per row, one bit per block");
+    unsigned long long todo = 0ull;
+    for (int b = blockIdx.x; b < NBLK; b += gridDim.x) todo |= 1ull << b;
+    if (const unsigned long long *__restrict__ kmap = fs.f[blockIdx.z].kp_elig) {
+        unsigned long long m = 0ull;
+#pragma unroll
+        for (int dy = -2; dy <= 2; ++dy) m |= (unsigned)(y + dy) < (unsigned)CAELO_NET_H ? kmap[y + dy] : 0ull;
+        todo &= m | m << 1 | m >> 1;
+    }
+    if (todo == 0ull) return;
     __shared__ float s_in[2][((RESP_STAGE + 63) / 64) * 64];  // (padded: every lane stores NLD elements)
     // staging: element i = lane + 64 q of [row 3][pixel RESP_BPX + 2][channel 3]; everything but the block's column is loop-invariant
     int goff[NLD];
@@ -275,7 +334,8 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
     }
 #define RESP_STORE(BUF)                                                                                           \
     _Pragma("unroll") for (int q = 0; q < NLD; ++q) s_in[BUF][lane + 64 * q] = v[q];
-    int blk = blockIdx.x, buf = 0;
+    int blk = __builtin_ctzll(todo), buf = 0;
+    todo &= todo - 1ull;
     RESP_LOAD(blk)  // (in flight under the fragment loads below)
     const float *fr = wts + RESP_FRAG_OFF + lane;
     float a1[2][7], a2[8];
@@ -312,9 +372,11 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
     for (int s = 0; s < 8; ++s) __asm__ volatile("" : "+v"(a2[s]));
     __asm__ volatile("" : "+v"(c2));
     RESP_STORE(0)
-    for (; blk < NBLK; blk += gridDim.x, buf ^= 1) {
-        const bool more = blk + (int)gridDim.x < NBLK;
-        if (more) RESP_LOAD(blk + gridDim.x)
+    for (;; buf ^= 1) {
+        const bool more = todo != 0ull;
+        const int next = more ? __builtin_ctzll(todo) : 0;   // the next needed block: its rows are in flight under this one's MFMAs
+        todo &= todo - 1ull;
+        if (more) RESP_LOAD(next)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");  // the staged block is complete (one wave: program order + this)
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -352,7 +414,9 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
                                 o[pt][3] > 0.0f ? o[pt][3] : 0.0f);
             }
         }
-        if (more) RESP_STORE(buf ^ 1)  // (this wave read that buffer an iteration ago: program order)
+        if (!more) break;
+        RESP_STORE(buf ^ 1)  // (this wave read that buffer an iteration ago: program order)
+        blk = next;
     }
 #undef RESP_LOAD
 #undef RESP_STORE
@@ -374,7 +438,12 @@ int ring_respond_set(caelo_ctx *c, const caelo_frame_set &fs, int in_w, int in_c
         // should come close to a multiple of 1024 waves with equal work each: 8 frames x 64 rows x 8 = 4096 waves of 7 blocks (2048
         // waves of 64-pixel blocks left 109 SIMDs with three waves and 109 with one: the matrix pipe of the former set the time).
         // For the fused path's 52 rows, measured: 4 / 7 / 8 / 14 / 28 waves per row = 40.5 / 32.7 / 30.3 / 28.0 / 29.4 us
-        const unsigned gx = fs.n >= 4 ? (rows == CAELO_NET_H ? 8u : 14u) : (fs.n >= 2 ? 28u : 56u);
+        // (every block computed); with the blocks no key point centre reads skipped (the bench's scenes keep about 70 %):
+        // 7 / 8 / 14 / 28 = 29.2 / 27.7 / 24.3 / 24.1 us -- 14 and 28 inside each other's spread, 14 launches half the workgroups
+#ifndef RESP_WPR_FUSED
+#define RESP_WPR_FUSED 14u   // (`make EXTRA=-DRESP_WPR_FUSED=...`: the sweep above)
+#endif
+        const unsigned gx = fs.n >= 4 ? (rows == CAELO_NET_H ? 8u : RESP_WPR_FUSED) : (fs.n >= 2 ? 28u : 56u);
         k_respond_mfma<<<dim3(gx, rows, fs.n), 64, 0, s>>>(fs, in_w, in_c, c->resp_w, row0);
     }
     CAELO_LAUNCH_CHECK();
@@ -422,6 +491,23 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     __shared__ unsigned int sBits[KS_HR][4];   // occupancy of a halo row as bits (68 columns: three words)
     const int tid = threadIdx.x;
     const int x0 = blockIdx.x * KS_COLS, y0 = 8 + blockIdx.y * KS_ROWS;  // rows 8..55 only
+    // The rule's conditions are ANDed and the range gate (:197-198) needs nothing but the centre's own ring pixel: it comes first.
+    // A tile none of whose centres passes it (k_ring_fill's map: the tile's four rows, its two 32-column blocks; the staged entry
+    // points have no map) is left before its halo is staged, and a centre that fails it skips its 24 distances below.  In the fused
+    // path only the response blocks such centres read have been computed for this frame (k_respond_mfma): no other centre may
+    // look at its window.
+    static_assert(KS_COLS == 64 && 8 + 48 <= CAELO_NET_H, "a tile spans two map bits of four row words");
+    if (const unsigned long long *__restrict__ kmap = F.kp_elig) {
+        const unsigned long long m = kmap[y0] | kmap[y0 + 1] | kmap[y0 + 2] | kmap[y0 + 3];
+        if (((m >> (2 * blockIdx.x)) & 3ull) == 0ull) return;
+    }
+    // (the centre's ring pixel is requested here, ahead of the halo, and used behind it)
+    float pxv[5];
+    {
+        const float *px = ring + ((int64_t)(y0 + tid / KS_COLS) * ring_w + x0 + (tid & (KS_COLS - 1))) * ring_c;
+#pragma unroll
+        for (int ch = 0; ch < 5; ++ch) pxv[ch] = ch < dist_c ? px[ch] : 0.0f;
+    }
     if (tid < KS_HR * 4) (&sBits[0][0])[tid] = 0u;
     __syncthreads();
     for (int i = tid; i < KS_HR * KS_HC; i += 256) {
@@ -442,6 +528,11 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     __syncthreads();
     const int lx = tid & (KS_COLS - 1), ly = tid / KS_COLS;
     const int x = x0 + lx, y = y0 + ly;
+    float d2 = __fmul_rn(pxv[0], pxv[0]);
+#pragma unroll
+    for (int ch = 1; ch < 5; ++ch)
+        if (ch < dist_c) d2 = __fadd_rn(d2, __fmul_rn(pxv[ch], pxv[ch]));  // :197
+    const bool far = sqrtf(d2) >= 10.0f;                                   // :198 VisibleBottom
     float best = 0.0f;
     bool is_cand = false;
     const int c = (ly + 2) * KS_HC + lx + 2;
@@ -455,7 +546,7 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
         const unsigned long long two = (unsigned long long)w[k] | ((unsigned long long)w[k + 1] << 32);
         win |= ((unsigned int)(two >> sh) & 31u) << (5 * r);
     }
-    if (x >= 8 && x < CAELO_NET_W - 8 && !(x >= 56 && x < 64) && ((win >> 12) & 1u)) {  // :163-167 (incl. the 56..63 quirk), :210-213
+    if (x >= 8 && x < CAELO_NET_W - 8 && !(x >= 56 && x < 64) && ((win >> 12) & 1u) && far) {  // :163-167 (incl. the 56..63 quirk), :210-213, :197-198
         const float4 pa = sR[2 * c], pb = sR[2 * c + 1];
         const int cnt = __popc(win & ~(1u << 12));
         // The window's own entry is one of the 25 norms cp.min runs over (SphericalRing.py:149-159,:179): centre - centre is 0, + 1e10
@@ -501,12 +592,7 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
             }
         }
         best = cnt > 0 ? sqrtf(best) : 0.0f;
-        if (cnt >= 5 && (double)best > 0.2) {  // :186, :126,:199
-            const float *px = ring + ((int64_t)y * ring_w + x) * ring_c;
-            float d2 = __fmul_rn(px[0], px[0]);
-            for (int ch = 1; ch < dist_c; ++ch) d2 = __fadd_rn(d2, __fmul_rn(px[ch], px[ch]));  // :197
-            is_cand = sqrtf(d2) >= 10.0f;                                                       // :198 VisibleBottom
-        }
+        is_cand = cnt >= 5 && (double)best > 0.2;  // :186, :126,:199
     }
     // one returning global atomic per WORKGROUP reserves the slots of all its candidates
     __shared__ int s_tmp[2];

@@ -500,6 +500,10 @@ int64_t caelo_extract_ws_bytes(void);
  * that were encoded, coarsest scale first), int32 slot_of[3072] (a listed patch: its position in list; a copy: -(representative + 1)).
  * Read-only; meant for tests of the de-duplication. */
 int64_t caelo_extract_ws_frame_offset(void);
+/* Byte offset, inside the caelo_extract workspace, of the key point eligibility map the last call left: 64 u64 words, one per ring row
+ * 0..63; bit b of word y is set iff some pixel of columns 32 b .. 32 b + 31 of row y holds a point whose norm over the first
+ * dist_channels ring channels is >= 10 (the range gate of SphericalRing.py:197-198).  Read-only; meant for tests. */
+int64_t caelo_extract_ws_kp_eligible_offset(void);
 int caelo_extract(caelo_ctx *ctx, caelo_voxmap *map, const float *pc, int64_t n, int dist_channels, int mode, float *key_pts,
                   int kp_ld, float *features, int feat_ld, float *valid, int valid_ld, int64_t *key_pixels,
                   int32_t *n_key, uint8_t *flags, int32_t *status, void *ws, void *stream);
