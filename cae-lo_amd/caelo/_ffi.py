@@ -45,6 +45,11 @@ class HarrisParams(C.Structure):
     _fields_ = [("radius", C.c_double), ("threshold", C.c_double)]
 
 
+class SiftParams(C.Structure):
+    """caelo_sift_params (include/caelo.h)."""
+    _fields_ = [("n_scales", c_i32), ("reserved", c_i32), ("min_contrast", C.c_double), ("sigma", C.c_double * 19)]
+
+
 class FrameJob(C.Structure):
     """caelo_frame_job (include/caelo.h): one frame of the pipeline, device pointers as integers."""
     _fields_ = [("pc", c_vp), ("n", c_i64), ("dist_channels", c_i32), ("mode", c_i32), ("rows", c_vp),
@@ -66,6 +71,7 @@ ACT_SIGMOID = 3   # include/caelo.h CAELO_ACT_SIGMOID: the decoder's output acti
 ACT_TANH, ACT_RELU, ACT_LINEAR = 0, 1, 2   # include/caelo.h CAELO_ACT_*: the encoder's activations (caelo_set_encoder_model)
 KP_NN_MAX_K, KP_NN_MAX_THRESHOLDS = 65536, 16   # include/caelo.h CAELO_KP_NN_MAX_K / CAELO_KP_NN_MAX_THRESHOLDS (caelo_kp_nn_pairs)
 ISS_MAX_POINTS = 32768   # include/caelo.h CAELO_ISS_MAX_POINTS (caelo_iss_keypoints)
+SIFT_K, SIFT_MAX_SCALES = 25, 19   # include/caelo.h CAELO_SIFT_K / CAELO_SIFT_MAX_SCALES (caelo_sift_octave)
 BUILD_PACKED_F32, BUILD_PROF, BUILD_STAMPED = 1, 2, 256   # caelo_build_flags() bits (include/caelo.h)
 
 # the same layout as a NumPy record (a run's jobs are filled column-wise and handed over in one call)
@@ -200,6 +206,9 @@ SIGNATURES = [
     ("caelo_iss_keypoints", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(IssParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     ("caelo_harris_ws_bytes", c_i64, [c_i64, c_int]),
     ("caelo_harris_keypoints", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(HarrisParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    ("caelo_sift_ws_bytes", c_i64, [c_i64, c_int]),
+    ("caelo_sift_octave", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, C.POINTER(SiftParams), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    ("caelo_voxel_centroids", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes", c_i64, [c_i64]),
     ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes_dim", c_i64, [c_i64, c_int]),

@@ -18,6 +18,7 @@ tuples / dtypes, served by the HIP engine.
     PCLKeypoint.keypointIss (PclKeyPts.py:95)   KeyPtsByISS(PC, salient_radius=2, non_max_radius=2, gamma_21=0.975, gamma_32=0.975,
                                                             min_neighbors=5)
     PCLKeypoint.keypointHarris (PclKeyPts.py:107) KeyPtsByHarris(PC, radius=1, threshold=0.001)
+    PCLKeypoint.keypointSift (PclKeyPts.py:116) KeyPtsBySIFT(PC, min_scale=0.5, n_octaves=4, n_scales_per_octave=8, min_contrast=0.1)
 
 Arguments may be NumPy arrays (results come back as NumPy, like the reference) or torch tensors on
 the GPU (results stay on the GPU).  Every array-level function runs on the GPU; there is no CPU
@@ -94,6 +95,20 @@ def KeyPtsByHarris(PC, **params):
     pts = _dev(PC, torch.float32)[:, 0:3].contiguous()
     r = e.harris_keypoints(pts, **params)
     return _out(pts[r.key_idx[:int(r.n_key.item())].long()], _is_np(PC))
+
+
+def KeyPtsBySIFT(PC, **params):
+    """PclKeyPts.py:114-122 (PCLKeypoint.keypointSift, a PCL binding the reference does not ship) -> the SIFT3D key points [K,3] f32 of
+    the cloud PC [N, >=3], in the order octave, point, scale: the detector of DESIGN.md 9j on the device (caelo_sift_octave under
+    Engine.sift_keypoints), PCL 1.8's SIFTKeypoint on the z coordinate as its model -- not its bits.  The rows are centroids of the
+    detector's voxel pyramid, not points of PC, and a point that is a key at two scales appears twice.  params: caelo.sift.DEFAULTS.
+    N <= 32768; ValueError beyond that, for a non-finite coordinate and for bad parameters.  K may be 0."""
+    if PC.ndim != 2 or PC.shape[1] < 3:
+        raise ValueError("KeyPtsBySIFT: PC must have shape [N, >= 3] (got %s)" % (tuple(PC.shape),))
+    e = default_engine()
+    pts = _dev(PC, torch.float32)[:, 0:3].contiguous()
+    r = e.sift_keypoints(pts, **params)
+    return _out(r.xyz[:int(r.n_key.item())], _is_np(PC))
 
 
 def ProjectPC2SphericalRing(PC):

@@ -41,6 +41,8 @@ DECODER_SHAPES = [(20, 200), (200,), (200, 2048), (2048,), (3, 3, 3, 32, 16), (1
 
 IssKeypoints = collections.namedtuple("IssKeypoints", "key_idx n_key saliency eig n_neigh")   # Engine.iss_keypoints
 HarrisKeypoints = collections.namedtuple("HarrisKeypoints", "key_idx n_key response n_neigh normals")   # Engine.harris_keypoints
+SiftOctave = collections.namedtuple("SiftOctave", "key_idx n_key dog knn key_mask")   # Engine.sift_octave
+SiftKeypoints = collections.namedtuple("SiftKeypoints", "xyz scale octave n_key")   # Engine.sift_keypoints
 
 
 def _ptr(t):
@@ -1008,17 +1010,17 @@ class Engine:
                 raise ValueError("%s: a point has a non-finite coordinate" % name)
         return pts, np_d, single
 
-    def _detect(self, sym, name, pts, n_pts, cp, outputs):
-        """What iss_keypoints and harris_keypoints share round caelo_<sym>_keypoints: the frames checked (_detector_frames), key_idx and
-        n_key allocated beside the detector's three ``outputs(F, ld)`` (in the C order; None = not wanted), the workspace fetched, the
-        call -> [key_idx, n_key, *outputs], without the frame axis for a single cloud."""
+    def _detect(self, sym, name, pts, n_pts, cp, outputs, entry="keypoints"):
+        """What iss_keypoints, harris_keypoints and sift_octave share round caelo_<sym>_<entry>: the frames checked (_detector_frames),
+        key_idx and n_key allocated beside the detector's three ``outputs(F, ld)`` (in the C order; None = not wanted), the workspace
+        fetched, the call -> [key_idx, n_key, *outputs], without the frame axis for a single cloud."""
         pts, np_d, single = self._detector_frames(pts, n_pts, name)
         F, ld = int(pts.shape[0]), int(pts.shape[1])
         out = [self.empty((F, ld), torch.int32), self.zeros((F,), torch.int32), *outputs(F, ld)]
         if F and ld:
             need = int(getattr(self.lib, "caelo_%s_ws_bytes" % sym)(F, ld))
             ws = self._ws(sym, need)
-            _ffi.check(getattr(self.lib, "caelo_%s_keypoints" % sym)(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), *[_ptr(t) for t in out[2:]],
+            _ffi.check(getattr(self.lib, "caelo_%s_%s" % (sym, entry))(self.ctx, _ptr(pts), F, ld, _ptr(np_d), C.byref(cp), *[_ptr(t) for t in out[2:]],
                                                                       _ptr(out[0]), _ptr(out[1]), _ptr(ws), need, self.stream))
         return [(t[0] if single and t is not None else t) for t in out]
 
@@ -1060,6 +1062,140 @@ class Engine:
             self.empty((F, ld), torch.float64), self.empty((F, ld, 3), torch.float64) if normals else None,
             self.empty((F, ld), torch.int32)))
         return HarrisKeypoints(key_idx, n_key, resp, nn, nv)
+
+    def sift_octave(self, pts, n_pts=None, sigma=None, min_contrast=0.1, knn=False):
+        """One octave of the SIFT3D detector on the device (caelo_sift_octave, csrc/sift.hip; the definition: include/caelo.h,
+        DESIGN.md 9j): the difference-of-Gaussians of the points' z over the ascending scales ``sigma`` (3 to 19 of them, float64,
+        handed to the kernel as they are), the 25 nearest neighbours, the extremum rule.
+
+        pts [F, ld, 3] f32 (frame f: rows 0 .. n_pts[f]-1; n_pts [F] ints or a device tensor, None = all ld rows) or one cloud [n, 3].
+        -> SiftOctave(key_idx [F, ld] i32: the rows with a key at some scale, ascending, -1 behind them; n_key [F] i32; dog [F, ld, S-1]
+        f64; knn [F, ld, 25] i32 in (d2, index) order -- None unless ``knn``; key_mask [F, ld] i32, bit s set for a key at sigma[s]),
+        on the device; a cloud [n, 3] gives the same without the frame axis.  Two all-pairs passes: n^2 pair distances each.
+
+        Refused with ValueError before any launch: what _detector_frames refuses (a non-finite coordinate in a frame's rows, ld above
+        CAELO_ISS_MAX_POINTS, n_pts outside [0, ld]), scales that are not 3 to 19 finite, positive, increasing numbers, a min_contrast
+        that is not finite or is negative."""
+        from . import sift
+        if sigma is None:
+            raise ValueError("sift_octave: sigma, the octave's scales, must be given (caelo.sift.octave_scales)")
+        sg = sift.check_scales(sigma)
+        if isinstance(min_contrast, bool) or not sift._finite(min_contrast) or float(min_contrast) < 0.0:
+            raise ValueError("SIFT min_contrast must be finite and not negative (got %r)" % (min_contrast,))
+        cp = _ffi.SiftParams(int(sg.shape[0]), 0, float(min_contrast), (C.c_double * _ffi.SIFT_MAX_SCALES)(*sg.tolist()))
+        D = int(sg.shape[0]) - 1
+        key_idx, n_key, dog, nn, mask = self._detect("sift", "SIFT3D", pts, n_pts, cp, lambda F, ld: (
+            self.empty((F, ld, D), torch.float64), self.empty((F, ld, _ffi.SIFT_K), torch.int32) if knn else None,
+            self.empty((F, ld), torch.int32)), entry="octave")
+        return SiftOctave(key_idx, n_key, dog, nn, mask)
+
+    def voxel_centroids(self, pc, leaf):
+        """pc [N, 3] f32 on the device -> [M, 3] f32: the centroids of the occupied ``leaf``-sized cells, cell = floor(double(p) / leaf)
+        per component, in (cz, cy, cx) order with x fastest (PCL's VoxelGrid order).  Each coordinate is the float64 sum of the cell's
+        points in ascending input row divided by double(count), rounded to float32 (caelo_voxel_centroids: the sort and the run
+        detection are torch's, the sums are not -- a scatter-add has no fixed order)."""
+        from . import sift
+        if not sift._finite(leaf) or not float(leaf) > 0.0:
+            raise ValueError("leaf must be finite and positive (got %r)" % (leaf,))
+        pc = torch.as_tensor(pc, device=self.device)
+        if pc.dim() != 2 or pc.shape[1] != 3 or pc.dtype != torch.float32:
+            raise ValueError("pc must be float32 [N, 3], got %s %s" % (pc.dtype, tuple(pc.shape)))
+        if not bool(torch.isfinite(pc).all()):
+            raise ValueError("voxel_centroids: the cloud holds a non-finite coordinate")
+        return self._voxel_centroids_many([pc], float(leaf))[0]
+
+    def _voxel_centroids_many(self, clouds, leaf):
+        """voxel_centroids of several clouds ([n_k, 3] f32 on the device, finite) at one leaf -> a list of [m_k, 3] f32: the frame is the
+        leading digit of the sort key, so one stable sort, one run detection, one launch and two read-backs serve all of them, and
+        every cloud gets what it gets alone (its cells in the same order, each cell's rows in ascending input row)."""
+        sizes = [int(c.shape[0]) for c in clouds]
+        n = sum(sizes)
+        if n == 0:
+            return [c.contiguous() for c in clouds]
+        pc = (torch.cat(clouds) if len(clouds) > 1 else clouds[0]).contiguous()
+        frame = torch.repeat_interleave(torch.arange(len(clouds), device=self.device), torch.tensor(sizes, device=self.device))
+        # a device tensor as the divisor: an IEEE division per element (a Python number may be turned into a multiplication)
+        cell = torch.floor(pc.to(torch.float64) / torch.tensor(leaf, dtype=torch.float64, device=self.device))
+        cell = cell - cell.min(dim=0).values
+        ext = cell.max(dim=0).values + 1
+        ex, ey, ez = ext.tolist()
+        if len(clouds) * ex * ey * ez >= 2.0 ** 62:
+            raise ValueError("voxel_centroids: %g-sized cells over this cloud's extent do not fit a 64-bit key" % leaf)
+        c, e = cell.to(torch.int64), ext.to(torch.int64)
+        key = ((frame * e[2] + c[:, 2]) * e[1] + c[:, 1]) * e[0] + c[:, 0]
+        order = torch.argsort(key, stable=True)   # stable: a cell's rows stay in ascending input row
+        sk = key[order]
+        first = torch.ones_like(sk, dtype=torch.bool)
+        first[1:] = sk[1:] != sk[:-1]
+        firsts = torch.nonzero(first).reshape(-1)
+        starts = torch.cat([firsts, torch.tensor([n], device=self.device)]).to(torch.int32).contiguous()
+        m = int(starts.shape[0]) - 1
+        out = self.empty((m, 3), torch.float32)
+        order32 = order.to(torch.int32).contiguous()
+        _ffi.check(self.lib.caelo_voxel_centroids(self.ctx, _ptr(pc), n, _ptr(order32), _ptr(starts), m, _ptr(out), self.stream))
+        per = torch.bincount(frame[order[firsts]], minlength=len(clouds)).tolist()   # cells per cloud
+        return list(torch.split(out, per))
+
+    def sift_keypoints(self, pts, n_pts=None, details=False, **params):
+        """SIFT3D key points on the device: the pyramid of DESIGN.md 9j over sift_octave.  For octave o = 0 .. n_octaves-1 the frame's
+        cloud becomes the voxel-grid centroids (voxel_centroids; all frames in one launch) of the previous octave's cloud at leaf min_scale * 2^o (octave 0 starts
+        from the given cloud); under 25 points the frame stops; otherwise the octave runs at caelo.sift.octave_scales(min_scale * 2^o,
+        n_scales_per_octave), all frames still alive in one call.
+
+        pts [F, ld, 3] f32 with n_pts, or one cloud [n, 3]; params: min_scale, n_octaves, n_scales_per_octave, min_contrast
+        (caelo.sift.DEFAULTS).  -> SiftKeypoints(xyz [F, cap, 3] f32: the points of the octave clouds that are a key, in the order
+        octave, point index, scale index -- a point may appear more than once; scale [F, cap] f64, the key's sigma; octave [F, cap] i32;
+        n_key [F] i32; cap = the largest n_key, rows behind n_key are 0, -1 for octave), on the device, without the frame axis for a
+        single cloud.  ``details``: -> (SiftKeypoints, a list per octave of dict(octave, scale, sigma, frames: the frames that ran,
+        clouds: their octave clouds, result: the SiftOctave of the batch with knn))."""
+        from . import sift
+        prm = sift.check_params(**params)
+        pts, np_d, single = self._detector_frames(pts, n_pts, "SIFT3D")
+        F = int(pts.shape[0])
+        counts = np_d.cpu().tolist() if F else []
+        clouds = {f: pts[f, :counts[f]] for f in range(F)}
+        rows = [[] for _ in range(F)]   # per frame: (xyz [k,3], scale [k], octave [k]) per octave
+        octaves = []
+        for o in range(prm["n_octaves"]):
+            scale = prm["min_scale"] * 2.0 ** o
+            alive = sorted(clouds)
+            clouds = dict(zip(alive, self._voxel_centroids_many([clouds[f] for f in alive], scale)))   # (finite: _detector_frames checked)
+            clouds = {f: c for f, c in clouds.items() if c.shape[0] >= sift.K}
+            if not clouds:
+                break
+            sg = sift.octave_scales(scale, prm["n_scales_per_octave"])
+            frames = sorted(clouds)
+            sizes = [int(clouds[f].shape[0]) for f in frames]
+            ld = max(sizes)
+            if ld > sift.MAX_POINTS:
+                raise ValueError("SIFT3D: octave %d holds %d points, above the %d an all-pairs search takes (thin the scan first)" % (o, ld, sift.MAX_POINTS))
+            batch = self.zeros((len(frames), ld, 3), torch.float32)
+            for k, f in enumerate(frames):
+                batch[k, :sizes[k]] = clouds[f]
+            r = self.sift_octave(batch, n_pts=sizes, sigma=sg, min_contrast=prm["min_contrast"], knn=details)
+            sg_d = torch.from_numpy(sg).to(self.device)
+            bits = (r.key_mask[:, :, None] >> torch.arange(sg.shape[0], device=self.device, dtype=torch.int32)[None, None, :]) & 1
+            hit = torch.nonzero(bits)   # row-major: frame, then point index, then scale index (rows past n_pts have no bit set)
+            per = torch.bincount(hit[:, 0], minlength=len(frames)).tolist()
+            xyz_o, sc_o, at = batch[hit[:, 0], hit[:, 1]], sg_d[hit[:, 2]], 0
+            for k, f in enumerate(frames):
+                rows[f].append((xyz_o[at:at + per[k]], sc_o[at:at + per[k]], torch.full((per[k],), o, dtype=torch.int32, device=self.device)))
+                at += per[k]
+            if details:
+                octaves.append(dict(octave=o, scale=scale, sigma=sg, frames=frames, clouds=[clouds[f] for f in frames], result=r))
+        n_key = [sum(int(x.shape[0]) for x, _, _ in rows[f]) for f in range(F)]
+        cap = max(n_key) if n_key else 0
+        xyz = self.zeros((F, cap, 3), torch.float32)
+        sc = self.zeros((F, cap), torch.float64)
+        oc = torch.full((F, cap), -1, dtype=torch.int32, device=self.device)
+        for f in range(F):
+            if n_key[f]:
+                xyz[f, :n_key[f]] = torch.cat([x for x, _, _ in rows[f]])
+                sc[f, :n_key[f]] = torch.cat([s for _, s, _ in rows[f]])
+                oc[f, :n_key[f]] = torch.cat([q for _, _, q in rows[f]])
+        nk = torch.tensor(n_key, dtype=torch.int32, device=self.device)
+        out = SiftKeypoints(xyz[0], sc[0], oc[0], nk[0]) if single else SiftKeypoints(xyz, sc, oc, nk)
+        return (out, octaves) if details else out
 
     def voxelize(self, pc, vmap=None, status=None):
         assert pc.dtype == torch.float32 and pc.dim() == 2 and pc.shape[1] >= 3 and pc.is_contiguous()

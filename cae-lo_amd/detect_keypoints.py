@@ -1,20 +1,25 @@
 #!/usr/bin/env python
-"""detect_keypoints.py -- key points of a hand-crafted detector for every scan of a directory, the rows 'iss' and 'harris' of the
-reference's key point comparison (PclKeyPts.py:63 lists cae-lo, 3dfeat-net, usip, iss, harris, sift; EvalOnReg_KeyPts.py:23).  The
-reference gets them from PCLKeypoint.keypointIss / keypointHarris, a PCL binding it does not ship; here the detectors run on the GPU
-(caelo_iss_keypoints; caelo_harris_keypoints).
+"""detect_keypoints.py -- key points of a hand-crafted detector for every scan of a directory, the rows 'iss', 'harris' and 'sift' of
+the reference's key point comparison (PclKeyPts.py:63 lists cae-lo, 3dfeat-net, usip, iss, harris, sift; EvalOnReg_KeyPts.py:23).  The
+reference gets them from PCLKeypoint.keypointIss / keypointHarris / keypointSift, a PCL binding it does not ship; here the detectors
+run on the GPU (caelo_iss_keypoints; caelo_harris_keypoints; caelo_sift_octave).
 
     python detect_keypoints.py --method iss --scans <seq>/velodyne --out iss_keypts/00
     python detect_keypoints.py --method harris --scans <seq>/velodyne --out harris_keypts/00
+    python detect_sift_keypoints.py --scans <seq>/velodyne --out sift_keypts/00
     python run_sequence.py --scans <seq>/velodyne --python-loader --keypts-source 3dfeatnet --keypts-dir iss_keypts/00 --out poses_/00.txt
     python evaluate.py keypoints --keypts-dir iss_keypts/00 --source 3dfeatnet --gt poses/00.txt --calib calib_.txt --out acc.mat
 
 Per scan, as PclKeyPts.py:77-103 does it: the points are thinned to one per --leaf cell (the first in scan order), at most --max-points
 of them are kept (RandomState(--seed + frame).choice without replacement, like :81), the detector runs with the reference's parameters
-(:42-46 for iss, :50-51 for harris), and the result is brought to exactly --keypoints points (ensure_keypoint_number, :20-28; the same RandomState goes on) unless
+(:42-46 for iss, :50-51 for harris, :55-58 for sift, whose key points are centroids of its own voxel pyramid, not scan points), and the result is brought to exactly --keypoints points (ensure_keypoint_number, :20-28; the same RandomState goes on) unless
 --no-ensure.  --batch frames share one launch of every kernel.  Written as <frame:06d>.bin in LiDAR axes, float32, unrotated:
 --layout 3dfeatnet (default) [K,35] with zero descriptors, which run_sequence.py --keypts-source 3dfeatnet and evaluate.py keypoints
 --source 3dfeatnet read as they are; --layout xyz plain [K,3].
+
+This script's own command line is what it was before SIFT3D was built: --method takes iss and harris, and sift stays an invalid
+choice here.  The sift row is detect_sift_keypoints.py beside it: the same main() with sift among the methods (and as the default)
+and sift's four options, everything else shared.
 """
 import argparse
 import glob
@@ -47,9 +52,13 @@ def prepare(eng, scan, frame, leaf, max_points, seed, calib_angle=None):
     return pc.contiguous(), rng
 
 
-def main(argv=None):
+def main(argv=None, with_sift=False):
+    """with_sift: detect_sift_keypoints.py's command line -- sift is a method, the default one, and its four options exist."""
     ap = argparse.ArgumentParser(description="hand-crafted key points over a directory of KITTI .bin scans (PclKeyPts.py)")
-    ap.add_argument("--method", required=True, choices=["iss", "harris"], help="the detector (sift of the reference's list is not built)")
+    if with_sift:
+        ap.add_argument("--method", default="sift", choices=["iss", "harris", "sift"], help="the detector (default sift)")
+    else:
+        ap.add_argument("--method", required=True, choices=["iss", "harris"], help="the detector (sift of the reference's list: detect_sift_keypoints.py)")
     ap.add_argument("--scans", required=True, help="directory of KITTI velodyne .bin files ([N,4] float32)")
     ap.add_argument("--out", required=True, help="directory the key point files are written to (created)")
     ap.add_argument("--leaf", type=float, default=0.2, help="cell size in metres of the thinning before the detector (default 0.2)")
@@ -67,11 +76,18 @@ def main(argv=None):
     ap.add_argument("--min-neighbors", type=int, default=None, help="iss (default 5)")
     ap.add_argument("--radius", type=float, default=None, help="harris: the radius of normals, response and suppression (default 1.0)")
     ap.add_argument("--threshold", type=float, default=None, help="harris: the least response of a key point (default 0.001)")
+    if with_sift:
+        ap.add_argument("--min-scale", type=float, default=None, help="sift: the scale of the first octave in metres (default 0.5)")
+        ap.add_argument("--n-octaves", type=int, default=None, help="sift: octaves, each at twice the scale of the one before (default 4)")
+        ap.add_argument("--n-scales-per-octave", type=int, default=None, help="sift (default 8)")
+        ap.add_argument("--min-contrast", type=float, default=None, help="sift: the least |difference of Gaussians| of a key point (default 0.1)")
     args = ap.parse_args(argv)
 
-    from caelo import harris, iss, keysources
+    from caelo import harris, iss, keysources, sift
     # per method: the module whose DEFAULTS name its options and whose check_params checks them, and its printed name
     methods = {"iss": (iss, "ISS"), "harris": (harris, "Harris3D")}
+    if with_sift:
+        methods["sift"] = (sift, "SIFT3D")
     for method, (mod, _) in methods.items():
         given = [n for n in mod.DEFAULTS if getattr(args, n) is not None]
         if method != args.method and given:
@@ -113,10 +129,11 @@ def main(argv=None):
         for k, (pc, _) in enumerate(clouds):
             pts[k, :pc.shape[0]] = pc
         r = getattr(eng, args.method + "_keypoints")(pts, n_pts=[pc.shape[0] for pc, _ in clouds], **prm)
-        key_idx, n_key = r.key_idx.cpu().numpy(), r.n_key.cpu().numpy()
+        n_key = r.n_key.cpu().numpy()
+        found_rows = (r.xyz if args.method == "sift" else r.key_idx).cpu().numpy()   # sift: the key points themselves; else row indices
         for k, ((fr, _), (pc, rng)) in enumerate(zip(group, clouds)):
             cloud = pc.cpu().numpy()
-            kp = cloud[key_idx[k, :n_key[k]]]
+            kp = found_rows[k, :n_key[k]] if args.method == "sift" else cloud[found_rows[k, :n_key[k]]]
             found.append(int(n_key[k]))
             if not args.no_ensure:
                 kp = iss.ensure_keypoint_number(kp, cloud, args.keypoints, rng)

@@ -645,6 +645,49 @@ int caelo_harris_keypoints(caelo_ctx *ctx, const float *pts /*[n_frames][ld][3] 
                            int32_t *key_idx /*[n_frames][ld]*/, int32_t *n_key /*[n_frames]*/,
                            void *ws, int64_t ws_bytes, void *stream);
 
+/* ---- SIFT3D key points: the third hand-crafted detector of the key point comparison (PclKeyPts.py:55-58, :63; csrc/sift.hip) -------
+ * (additive; the ABI version stays 6.)  The reference calls PCLKeypoint.keypointSift; the model is PCL 1.8's SIFTKeypoint on PointXYZ
+ * with the point's z coordinate as the filtered field.  The definition is the one below, and bit parity with PCL is not
+ * claimed.  caelo_sift_octave is ONE octave: a cloud per frame and a list of scales; the pyramid over the octaves (voxel-grid
+ * centroids at leaf min_scale * 2^o, the scales of an octave, the stop under 25 points) is the caller's (caelo.Engine.sift_keypoints).
+ * pts, n_pts: as for caelo_iss_keypoints.  All arithmetic is float64, every operation rounded on its own (IEEE division), sums in
+ * ascending point index; the one exception is exp, the device's float64 exp, which is not correctly rounded:
+ *   scale space  value_j = double(P[j].z); d = double(P[j]) - double(P[i]), d2 = (dx*dx + dy*dy) + dz*dz.  For every scale s:
+ *                j counts <=> d2 <= 9.0 * (sigma[s]*sigma[s]) (not strict; two rounded products; i counts itself with w = 1),
+ *                w = exp((-0.5 * d2) / (sigma[s]*sigma[s])), num_s = sum value_j * w, den_s = sum w, resp_s = num_s / den_s,
+ *                dog[i][s] = resp_{s+1} - resp_s for s = 0 .. D-1, D = n_scales - 1
+ *   neighbours   the CAELO_SIFT_K points with the smallest (d2, j) in lexicographic order, the point itself included (ties in
+ *                distance go to the lower index); a frame of fewer than CAELO_SIFT_K points has no key points, its dog is still written
+ *   key point    for s = 1 .. D-2, v = dog[i][s], mn[t] / mx[t] the minimum / maximum of dog[j][t] over the neighbours: (i, s) is a key
+ *                <=> |v| >= min_contrast and (v == mn[s] && v < mn[s-1] && v < mn[s+1]  ||  v == mx[s] && v > mx[s-1] && v > mx[s+1])
+ *                (equal values at the same level both survive)
+ * Outputs (device): dog [n_frames][ld][D] f64; knn [n_frames][ld][CAELO_SIFT_K] i32 in (d2, j) order, -1 behind a frame's points when
+ * it has fewer (nullable); key_mask [n_frames][ld] u32, bit s set for every key (i, s); key_idx [n_frames][ld] i32, the points with a
+ * non-zero mask in ascending order, -1 behind them; n_key [n_frames] i32.  Rows n_pts[f] .. ld-1 get dog 0, knn -1 and mask 0.  The
+ * same input gives the same bits on every run and in every batch composition (no atomics, no cross-thread sums); a NaN coordinate only
+ * makes comparisons false.  Four kernels, each one launch for all frames (the three per-point passes in slices of 65 535 frames); ws:
+ * caelo_sift_ws_bytes(n_frames, ld) bytes, no initialisation, one per call in flight.  prm is HOST memory.  Refused before any launch
+ * (CAELO_ERR_ARG): null arguments, ld outside [1, CAELO_ISS_MAX_POINTS], n_frames < 0, n_scales outside [3, CAELO_SIFT_MAX_SCALES],
+ * scales that are not finite, positive and increasing, a min_contrast that is not finite or is negative, a short workspace.
+ * n_frames == 0 is a no-op.  The call does not synchronise.  The work is n_pts^2 pair distances per frame in each all-pairs pass.
+ *
+ * caelo_voxel_centroids: the centroids of a voxel grid's cells, which the pyramid is built from.  pts [n_pts][3] f32; order [n_pts]
+ * i32, the rows stably sorted by cell; starts [n_cells + 1] i32, where each cell's run of `order` begins (all device; the caller sorts:
+ * caelo.Engine.voxel_centroids, cells = floor(double(p) / leaf) ordered by (cz, cy, cx)).  Each coordinate of centroids [n_cells][3]
+ * f32 is the float64 sum over the cell's run in the order given (ascending input row under a stable sort) divided by double(count),
+ * rounded to float32.  An index outside [0, n_pts) is skipped and a run is clamped to the list, so bad lists never read out of bounds. */
+#define CAELO_SIFT_K 25
+#define CAELO_SIFT_MAX_SCALES 19
+typedef struct { int32_t n_scales, reserved; double min_contrast; double sigma[CAELO_SIFT_MAX_SCALES]; } caelo_sift_params;
+int64_t caelo_sift_ws_bytes(int64_t n_frames, int ld);
+int caelo_sift_octave(caelo_ctx *ctx, const float *pts /*[n_frames][ld][3] device*/, int64_t n_frames, int ld,
+                      const int32_t *n_pts /*[n_frames] device*/, const caelo_sift_params *prm /*host*/,
+                      double *dog /*[n_frames][ld][n_scales-1]*/, int32_t *knn /*[n_frames][ld][CAELO_SIFT_K]; nullable*/,
+                      uint32_t *key_mask /*[n_frames][ld]*/, int32_t *key_idx /*[n_frames][ld]*/, int32_t *n_key /*[n_frames]*/,
+                      void *ws, int64_t ws_bytes, void *stream);
+int caelo_voxel_centroids(caelo_ctx *ctx, const float *pts /*[n_pts][3]*/, int64_t n_pts, const int32_t *order /*[n_pts]*/,
+                          const int32_t *starts /*[n_cells + 1]*/, int64_t n_cells, float *centroids /*[n_cells][3]*/, void *stream);
+
 /* ---- frame pipeline: batches of frames behind single launches, three stages on three HIP streams ------------------
  * Replaces the reference's per-frame driver loops (BatchPreprocess.py:88-140 extract loop, Match.py:296-353 /
  * PoseEstimation.py pair loop) for throughput.  `batch` consecutive frames share ONE launch of every kernel of the
