@@ -1403,6 +1403,23 @@ class Engine:
         _ffi.check(self.lib.caelo_encode32(self.ctx, _ptr(bits), n, group, _ptr(out), 20 * group, _ptr(ws), self.stream))
         return out
 
+    def encode32_layers(self, bits):
+        """Test aid, the counterpart of ``encode_layers``: encode32 (group 1, every patch) and return what its kernels leave in
+        the workspace -- P1 [n,16,16,16,8] (after conv1 + pool), P2 [n,8192] (after conv2 + pool), F3 [n,16384] (after conv3), the
+        Dense(200) pre-activations summed over the k slices [n,200] (bias not added) -- and the descriptors [n,20].  Workspace
+        layout: caelo_encode32_ws_layout."""
+        n = bits.numel() // 512
+        out = self.encode32(bits, 1)
+        ws = self._ws("encode32", int(self.lib.caelo_encode32_ws_bytes(n)))
+        lay = (C.c_int64 * 7)()
+        _ffi.check(self.lib.caelo_encode32_ws_layout(n, C.cast(lay, C.c_void_p)))
+        o_p1, o_p2, o_f3, o_part, np_, used, sized = (int(v) for v in lay)
+        p1 = ws[o_p1:o_p1 + n * 32768 * 4].view(torch.float32).view(n, 16, 16, 16, 8)
+        p2 = ws[o_p2:o_p2 + n * 8192 * 4].view(torch.float32).view(n, 8192)
+        f3 = ws[o_f3:o_f3 + np_ * 16384 * 4].view(torch.float32).view(np_, 16384)[:n]
+        part = ws[o_part:o_part + sized * np_ * 208 * 4].view(torch.float32).view(sized, np_, 208)[:used, :n, :200].sum(dim=0)
+        return p1.clone(), p2.clone(), f3.clone(), part, out
+
     def encode32_profile(self, bits, group=1):
         """encode32 + per-launch HIP-event timings (ms): conv1+pool, conv2+pool, conv3, Dense(200)+head.  Synchronises."""
         n = bits.numel() // 512

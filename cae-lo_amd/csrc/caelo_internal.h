@@ -365,6 +365,7 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
 int64_t enc_dense_pad(int64_t n);  // rows padded to whole dense-1 tiles
 int enc_upload_dense1(const float *wd1, const float *bd1, int K, void **wx_dev, float **bd_dev);
 int64_t enc_dense32_part_bytes(int64_t np);
+void enc_dense32_slices(int64_t *used, int64_t *sized);  // k slices Dense(200) of the 32^3 case writes / the buffer is sized for
 int enc_dense32_head_launch(caelo_ctx *c, const float *f3, int64_t n_patches, int64_t np, float *part, int group, float *out,
                             int out_stride, hipStream_t s);
 int encode_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int group, float *out, int out_stride, void *ws,

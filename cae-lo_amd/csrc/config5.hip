@@ -10,7 +10,8 @@
 //   * Conv3D(1->8) tanh, MaxPool2 (16^3), Conv3D(8->16) tanh, MaxPool2 (8^3), Conv3D(16->32) tanh, Flatten
 //     (16384), Dense(200) tanh, Dense(20) tanh; conv kernels, biases and dense_2 from the .h5, dense_1 a caller
 //     supplied [16384][200] matrix (no trained weights exist at this size).
-// Parity is against oracle/caelo_oracle.c (orc_patches32, orc_encode32) only.
+// Parity is against oracle/caelo_oracle.c (orc_patches32, orc_encode32) and, layer by layer and on edge inputs, against the float64
+// network and the set-membership rule of tests/test_config5_gpu.py.
 //
 // Data layout: a patch is 512 u64 words, voxel (ix,iy,iz) at bit (lin & 63) of word (lin >> 6),
 // lin = (ix*32 + iy)*32 + iz; activations are channels-last f32 ([x][y][z][c]) like the 16^3 path.
@@ -432,6 +433,19 @@ CAELO_API int64_t caelo_encode32_ws_bytes(int64_t n_patches) {
     if (n_patches <= 0) return 0;
     const int64_t np = c5_pad(n_patches);
     return (n_patches * (32768 + 8192) + np * 16384) * (int64_t)sizeof(float) + enc_dense32_part_bytes(np);
+}
+
+// test aid: where encode32_impl below puts what its kernels leave behind
+CAELO_API int caelo_encode32_ws_layout(int64_t n_patches, int64_t out[7]) {
+    CAELO_REQUIRE(out && n_patches > 0, "caelo_encode32_ws_layout: bad argument");
+    const int64_t np = c5_pad(n_patches);
+    out[0] = 0;
+    out[1] = out[0] + n_patches * 32768 * (int64_t)sizeof(float);
+    out[2] = out[1] + n_patches * 8192 * (int64_t)sizeof(float);
+    out[3] = out[2] + np * 16384 * (int64_t)sizeof(float);
+    out[4] = np;
+    enc_dense32_slices(&out[5], &out[6]);
+    return CAELO_OK;
 }
 
 static int encode32_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int group, float *out, int out_stride,

@@ -1468,6 +1468,10 @@ int encode_batch_impl(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int
 // Dense(200) + Dense(20) of the 32^3 stress case (config5.hip): the same two kernels over K = 16384
 int64_t enc_dense_pad(int64_t n) { return pad64(n); }
 int64_t enc_dense32_part_bytes(int64_t np) { return (int64_t)D1_SPLIT * np * DENSE_NP * (int64_t)sizeof(float); }
+void enc_dense32_slices(int64_t *used, int64_t *sized) {
+    *used = D1_SPLIT_OF(16384);
+    *sized = D1_SPLIT;
+}
 int enc_dense32_head_launch(caelo_ctx *c, const float *f3, int64_t n_patches, int64_t np, float *part, int group, float *out,
                             int out_stride, hipStream_t s) {
     const caelo_enc_in plain = {nullptr, 0, (int32_t)n_patches, 1, 0, 0};

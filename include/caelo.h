@@ -351,11 +351,16 @@ int caelo_encode(caelo_ctx *ctx, const uint64_t *bits, int64_t n_patches, int gr
  * and dense_2 are the ones already set).
  * bits [k_max][3][512] u64: voxel (ix,iy,iz) at bit (lin & 63) of word (lin >> 6), lin = (ix*32 + iy)*32 + iz.
  * caelo_encode32: bits [n_patches][512] -> out[(p / group) * out_stride + (p % group) * 20 + j]; ws of
- * caelo_encode32_ws_bytes(n_patches) bytes (no initialisation needed). */
+ * caelo_encode32_ws_bytes(n_patches) bytes (no initialisation needed).
+ * caelo_encode32_ws_layout (test aid): byte offsets in ws of what the kernels leave behind -- out[0] P1 [n_patches][16^3][8] f32
+ * (after conv1 + pool), out[1] P2 [n_patches][8^3][16] (after conv2 + pool), out[2] F3 [np][16384] (after conv3), out[3] Dense(200)
+ * partial sums [slices][np][208]; out[4] = np (rows padded to whole row tiles), out[5] = k slices in use, out[6] = k slices the
+ * buffer is sized for. */
 int caelo_patches32(caelo_ctx *ctx, const caelo_voxmap *map, const float *pts, int pts_ld, int64_t k_max,
                     const int32_t *n_key, uint64_t *bits, void *stream);
 int caelo_set_encoder32_dense(caelo_ctx *ctx, const float *wd1, const float *bd1);
 int64_t caelo_encode32_ws_bytes(int64_t n_patches);
+int caelo_encode32_ws_layout(int64_t n_patches, int64_t out[7]);
 int caelo_encode32(caelo_ctx *ctx, const uint64_t *bits, int64_t n_patches, int group, float *out, int out_stride,
                    void *ws, void *stream);
 

@@ -85,19 +85,33 @@ def _encoder(ws, dense1, bias1, bits, size):
     f3 = np.tanh(conv_same(p2, k[4], k[5])).reshape(n, -1)        # Flatten: (x, y, z, c) == memory order
     hidden = np.tanh(f3 @ np.asarray(dense1, np.float64).reshape(f3.shape[1], 200) + np.asarray(bias1, np.float64))
     out = np.tanh(hidden @ k[8].reshape(200, 20) + k[9])
-    return p2.reshape(n, -1), f3, hidden, out
+    return p1, p2.reshape(n, -1), f3, hidden, out
 
 
 def encoder_layers(ws, bits):
     """Bit-packed 16^3 patches [n,64] u64 -> (P2 [n,1024] after the second pooling, F3 [n,2048] after conv3d_3's tanh, hidden [n,200]
     after Dense(200)'s tanh, out [n,20]), all f64."""
-    return _encoder(ws, ws[6], ws[7], bits, 16)
+    return _encoder(ws, ws[6], ws[7], bits, 16)[1:]
 
 
 def encoder32(ws, dense1, bias1, bits):
     """The same stack on bit-packed 32^3 patches [n,512] u64 with ``dense1`` [16384,200] / ``bias1`` [200] as the first dense
     layer -> descriptors [n,20] f64."""
-    return _encoder(ws, dense1, bias1, bits, 32)[3]
+    return _encoder(ws, dense1, bias1, bits, 32)[4]
+
+
+def encoder32_layers(ws, dense1, bias1, bits):
+    """encoder32 with every layer -> (P1 [n,16,16,16,8] after the first pooling, P2 [n,8192], F3 [n,16384], hidden [n,200], out [n,20]),
+    all f64."""
+    return _encoder(ws, dense1, bias1, bits, 32)
+
+
+def dense1_32(seed=5):
+    """The stand-in dense_1 of the 32^3 encoder WITH a bias: N(0, 1/16384) [16384,200] f32 (the same draw as
+    Engine.seeded_dense1_32) and, from the same stream, a bias U(-0.5, 0.5) [200] f32."""
+    rs = np.random.RandomState(seed)
+    wd1 = (rs.standard_normal((16384, 200)) / 128.0).astype(np.float32)
+    return wd1, rs.uniform(-0.5, 0.5, 200).astype(np.float32)
 
 
 def respond(ws, img, with_magnitude=False):
@@ -140,6 +154,33 @@ def random_patches32(n, seed=11):
         dense = rs.uniform(size=32768) < (0.002, 0.02, 0.2)[i % 3]
         bits[i] = np.packbits(dense, bitorder="little").view(np.uint64)
     return bits
+
+
+def pack32(dense):
+    """bool [n,32,32,32] -> [n,512] u64 (the layout of ``unpack(bits, 32)``)."""
+    dense = np.asarray(dense, bool)
+    return np.packbits(dense.reshape(len(dense), 32768), axis=1, bitorder="little").view(np.uint64)
+
+
+def edge_patches32(n):
+    """[n,512] u64, n >= 16, deterministic: 0 the empty patch, 1 the full patch, 2 / 3 the single voxels at (0,0,0) / (31,31,31), 4 the
+    pair (0,31,0) + (31,0,31), 5..10 the full face planes x = 0, x = 31, y = 0, y = 31, z = 0, z = 31, 11 the full cube minus its outer
+    shell, 12 the single voxel at (15,16,16), then random fill at 0.002 / 0.02 / 0.2 in turn (seed 13)."""
+    assert n >= 16
+    d = np.zeros((n, 32, 32, 32), bool)
+    d[1] = True
+    d[2, 0, 0, 0] = True
+    d[3, 31, 31, 31] = True
+    d[4, 0, 31, 0] = d[4, 31, 0, 31] = True
+    d[5, 0], d[6, 31] = True, True
+    d[7, :, 0], d[8, :, 31] = True, True
+    d[9, :, :, 0], d[10, :, :, 31] = True, True
+    d[11, 1:31, 1:31, 1:31] = True
+    d[12, 15, 16, 16] = True
+    rs = np.random.RandomState(13)
+    for i in range(13, n):
+        d[i] = rs.uniform(size=(32, 32, 32)) < (0.002, 0.02, 0.2)[(i - 13) % 3]
+    return pack32(d)
 
 
 # ---- weight families ------------------------------------------------------------------------------------------------------

@@ -50,6 +50,14 @@ def test_host_only_entry_points_without_a_gpu():
         assert 0 < o_p2 < o_f3 < o_part and o_f3 - o_p2 == np_ * 1024 * 4 and o_part - o_f3 == np_ * 2048 * 4
         assert o_part + sized * np_ * 208 * 4 == lib.caelo_encode_ws_bytes(n)
     assert lib.caelo_encode_ws_layout(0, None) != 0
+    for n in (1, 63, 64, 65, 257, 3072):     # the 32^3 encoder's: P1 and P2 hold n rows, F3 and the partial sums whole row tiles
+        lay = (ctypes.c_int64 * 7)()
+        assert lib.caelo_encode32_ws_layout(n, ctypes.cast(lay, ctypes.c_void_p)) == 0
+        o_p1, o_p2, o_f3, o_part, np_, used, sized = (int(v) for v in lay)
+        assert n <= np_ < n + 64 and np_ % 64 == 0 and 0 < used <= sized
+        assert o_p1 == 0 and o_p2 - o_p1 == n * 32768 * 4 and o_f3 - o_p2 == n * 8192 * 4 and o_part - o_f3 == np_ * 16384 * 4
+        assert o_part + sized * np_ * 208 * 4 == lib.caelo_encode32_ws_bytes(n)
+    assert lib.caelo_encode32_ws_layout(0, None) != 0 and lib.caelo_encode32_ws_layout(4, None) != 0
     assert lib.caelo_upload_many(None, None, None, 0, None) == 0
     assert lib.caelo_upload_many(None, None, None, 1, None) != 0 and lib.caelo_last_error()
 

@@ -91,6 +91,111 @@ def test_oracle_encoder32_against_float64(orc):
     assert (ref.max(axis=0) - ref.min(axis=0)).min() >= 1e-3
 
 
+ENCODER32_FAMILIES = ("shipped", "biased", "sat_conv1")     # the families of tests/test_config5_gpu.py
+
+
+@functools.lru_cache(maxsize=None)
+def _family32(name):
+    ws = nr.encoder_family(name)
+    wd1, bd1 = nr.dense1_32()
+    return ws, wd1, bd1, nr.encoder32_layers(ws, wd1, bd1, nr.edge_patches32(24))
+
+
+def test_edge_patches32_are_the_named_patches():
+    bits = nr.edge_patches32(24)
+    d = nr.unpack(bits, 32)[..., 0].astype(bool)
+    assert bits.shape == (24, 512) and np.array_equal(bits, nr.edge_patches32(24)) and np.array_equal(bits[:16], nr.edge_patches32(16))
+    assert not d[0].any() and d[1].all()
+    assert [int(x.sum()) for x in d[2:5]] == [1, 1, 2] and d[2, 0, 0, 0] and d[3, 31, 31, 31] and d[4, 0, 31, 0] and d[4, 31, 0, 31]
+    planes = [d[5, 0], d[6, 31], d[7, :, 0], d[8, :, 31], d[9, :, :, 0], d[10, :, :, 31]]
+    assert all(p.all() for p in planes) and all(int(d[i].sum()) == 1024 for i in range(5, 11))
+    assert d[11, 1:31, 1:31, 1:31].all() and int(d[11].sum()) == 30 ** 3
+    assert int(d[12].sum()) == 1 and d[12, 15, 16, 16]
+    fill = d[13:].reshape(11, -1).mean(axis=1)
+    assert np.all(np.abs(fill / np.tile([0.002, 0.02, 0.2], 4)[:11] - 1) < 0.5)     # (65 voxels expected at 0.002: 4 sigma = 0.5)
+    wd1, bd1 = nr.dense1_32()
+    from caelo.engine import Engine
+    assert np.array_equal(wd1, Engine.seeded_dense1_32()[0]) and bd1.dtype == np.float32 and np.abs(bd1).min() > 0 and np.abs(bd1).max() < 0.5
+
+
+def test_oracle_encoder32_on_edge_patches_with_a_dense1_bias(orc):
+    """The f32 oracle and the float64 network agree on the 24 edge patches under `biased` with a NON-ZERO dense_1 bias, and the
+    bias matters: the same network without it gives other descriptors."""
+    ws, wd1, bd1, ref = _family32("biased")
+    bits = nr.edge_patches32(24)
+    got = orc.PatchEncoder32(ws, wd1, bd1).predict_bits(bits)
+    rel = _rel(got, ref[4])
+    print("encoder32, edge patches, bias: rel %.2e" % rel)
+    assert [a.shape for a in ref] == [(24, 16, 16, 16, 8), (24, 8192), (24, 16384), (24, 200), (24, 20)]
+    assert got.shape == (24, 20) and rel <= ORACLE_REL, rel
+    assert np.array_equal(ref[4], nr.encoder32(ws, wd1, bd1, bits))
+    assert np.abs(nr.encoder32(ws, wd1, np.zeros(200), bits[:4]) - ref[4][:4]).max() > 1e-2
+
+
+@pytest.mark.parametrize("family", ENCODER32_FAMILIES)
+def test_encoder32_families_discriminate(family):
+    out = _family32(family)[3][4]
+    spread = out.max(axis=0) - out.min(axis=0)
+    print(family, "smallest column spread %.3f" % spread.min())
+    assert spread.min() >= 1e-3 and np.abs(out).max() < 1.0, (family, spread.min())
+
+
+def test_patches32_reference_and_its_case(orc):
+    """tests/patches32_ref.py against the oracle's gather, bit for bit, on the hand-made voxel sets and key points of the GPU gather
+    tests -- and the properties those key points were chosen for, stated from the reference's own output."""
+    import patches32_ref as pr
+    lists, pts, tags = pr.gather_case()
+    ref = pr.gather_reference()
+    assert ref.shape == (len(pts), 3, 512) and all(len(a) >= 496 for a in lists)
+    for s in range(3):
+        assert np.array_equal(orc.patches32_bits(pts, lists[s], s), ref[:, s]), s
+    dense = np.stack([nr.unpack(ref[:, s], 32)[..., 0] for s in range(3)], axis=1).astype(bool)      # [k, 3, 32, 32, 32]
+    kind = np.array([t[0] for t in tags])
+    made_for = np.array([-1 if t[1] is None else t[1] for t in tags])
+    for s in range(3):
+        keys = pr.key_voxels(pts, s)
+        mine = made_for == s
+        solid = keys[mine & (kind == "solid")]
+        assert all(sorted(solid[:, a] % 8) == list(range(8)) for a in range(3))                    # every brick phase on every axis
+        assert dense[mine & (kind == "solid"), s].all()                                              # 512 all-ones words
+        below = keys[mine & (kind == "below")] - 16
+        assert [tuple(r) for r in (below < 0)] == [(True, False, False), (False, True, False), (False, False, True), (True, True, True)]
+        above = keys[mine & (kind == "above")] + 15 >= np.array(pr.GRID[s])
+        assert [tuple(r) for r in above] == [(True, False, False), (False, True, False), (False, False, True), (True, True, True)]
+        assert dense[mine & np.isin(kind, ("below", "above")), s].reshape(8, -1).sum(axis=1).min() >= 20
+        for i in np.nonzero(mine & (kind == "single"))[0]:
+            axis, off = tags[i][2]
+            want = np.zeros((32, 32, 32), bool)
+            if -16 <= off < 16:
+                idx = [0, 0, 0]
+                idx[axis] = off % 32
+                want[tuple(idx)] = True
+            assert np.array_equal(dense[i, s], want), (s, axis, off)
+        # a point on a voxel face: the float64 quotient is the integer itself, a float64 spacing below it is the voxel before
+        face = {t[2]: i for i, t in enumerate(tags) if t[0] == "face"}
+        q = (pts[face["hit"]].astype(np.float64) + pr.VISIBLE) / pr.SIZES[s]
+        m = np.array([4992, 4992, 736]) >> (0, 3, 5)[s]
+        assert np.array_equal(q, m.astype(np.float64)) and np.array_equal(keys[face["hit"]], m) and np.array_equal(keys[face["next"]], m)
+        assert np.array_equal(keys[face["low"]], m - 1)
+        for a in range(3):
+            assert np.array_equal(keys[face["low%d" % a]], m - np.eye(3, dtype=int)[a])
+        assert dense[face["hit"], s].sum() >= 20 and not np.array_equal(dense[face["hit"], s], dense[face["low"], s])
+        # the far point: 20 m from every voxel of every scale
+        far = int(np.nonzero(kind == "far")[0][0])
+        centres = (lists[s].astype(np.float64) + 0.5) * pr.SIZES[s] - pr.VISIBLE
+        assert np.linalg.norm(centres - pts[far].astype(np.float64), axis=1).min() > 20.0 and not dense[far, s].any()
+
+
+def test_patches32_reference_on_the_builders_case(orc):
+    import patches32_ref as pr
+    pc, lists, keys = pr.both_ways_case()
+    vox = orc.Voxelization(pc[:, 0:3])[6:9]
+    for s in range(3):
+        assert np.array_equal(np.unique(np.asarray(vox[s], np.int16), axis=0), lists[s]), s
+        bits = pr.patches32(keys, lists[s], s)
+        assert np.array_equal(orc.patches32_bits(keys, lists[s], s), bits) and nr.unpack(bits, 32).sum(axis=(1, 2, 3, 4)).min() >= 8
+
+
 @pytest.fixture(scope="module")
 def ring_image(orc, scans):
     import hashlib

@@ -11,7 +11,11 @@ sixth patch of the golden frame.  FAMILY_BUDGET of tests/test_weight_families_gp
 `--activations`: the models of tests/test_encoder_activations_gpu.py (tests/netref64_act.py MODELS: the trained relu / linear fixture
 and seeded families under relu / linear, relu / tanh and tanh / linear) on that test's 582 patches, for both stage-1 kernels, against
 the FLOAT64 network -- and, first, what the plain float32 NumPy restatement costs on the same patches: the test's per-layer bars are
-4 x those lines, its descriptor bar is 1e-4 relative.  profiles/enc_layer_errors_activations.txt is this output."""
+4 x those lines, its descriptor bar is 1e-4 relative.  profiles/enc_layer_errors_activations.txt is this output.
+
+`--config5`: the 32^3 encoder (csrc/config5.hip) layer by layer -- P1, P2, F3, tanh(Dense(200)), descriptors -- under the `shipped`,
+`biased` and `sat_conv1` families with the seeded dense_1 and a non-zero bias, on the 24 edge patches of tests/test_config5_gpu.py,
+against the FLOAT64 network.  LAYER32_BUDGET of that test is 3 x these lines; profiles/enc32_layer_errors_families.txt is this output."""
 import argparse, os, sys
 import numpy as np
 import torch
@@ -24,6 +28,7 @@ from caelo.engine import Engine
 ap = argparse.ArgumentParser()
 ap.add_argument("--family", action="append", default=[])
 ap.add_argument("--activations", action="store_true")
+ap.add_argument("--config5", action="store_true")
 args = ap.parse_args()
 eng = Engine(device=0)
 golden_bits = np.ascontiguousarray(np.load(os.path.join(REPO, "tests", "golden", "frame_q0.npz"))["patch_bits"].reshape(-1, 64))
@@ -61,6 +66,27 @@ if args.activations:
                 report(layers, ws[7], ref, na.ACTS[acts[0]], acts[0])
                 sys.stdout.flush()
             eng.set_encoder_reference(False)
+    print("lane_faults %d" % eng.lane_faults())
+    sys.exit(0)
+
+if args.config5:
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import netref64 as nr
+    bits = nr.edge_patches32(24)
+    t = torch.from_numpy(bits.view(np.int64)).to(eng.device)
+    wd1, bd1 = nr.dense1_32()
+    for fam in ("shipped", "biased", "sat_conv1"):
+        ws = nr.encoder_family(fam)
+        ref = nr.encoder32_layers(ws, wd1, bd1, bits)
+        eng.set_encoder_weights(ws)
+        eng.set_encoder32_dense(wd1, bd1)
+        p1, p2, f3, pre, out = (x.cpu().numpy() for x in eng.encode32_layers(t))
+        print("32^3 encoder, family %s, %d edge patches, dense_1 bias U(-0.5, 0.5), against float64" % (fam, len(bits)))
+        h = np.tanh(pre.astype(np.float64) + bd1.astype(np.float64))
+        for name, a, b in (("P1", p1, ref[0]), ("P2", p2, ref[1]), ("F3", f3, ref[2]), ("tanh(Dense(200))", h, ref[3]), ("descriptors", out, ref[4])):
+            d = np.abs(a.astype(np.float64) - b)
+            print("%-18s max abs %.3e   mean abs %.3e   element-wise rel (floor 0.1) %.3e" % (name, d.max(), d.mean(), (d / np.maximum(np.abs(b), 0.1)).max()))
+        sys.stdout.flush()
     print("lane_faults %d" % eng.lane_faults())
     sys.exit(0)
 
