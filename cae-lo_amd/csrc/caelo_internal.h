@@ -65,7 +65,7 @@ struct caelo_ctx {
     bool has_enc;
     int enc_hidden, enc_code;   // CAELO_ACT_*: conv3d_1..3 + dense_1 / dense_2 (caelo_set_encoder_model); tanh / tanh from caelo_create on
     bool enc_reference;   // caelo_set_encoder_reference: stage 1 = the exact-f32 k_enc_stage1 (precision reference)
-    int32_t *faults;  // device counter of the pair kernels' lane-agreement checks (match.hip); 0 on healthy hardware
+    int32_t *faults;  // device counter of the pair kernels' lane-agreement checks (ransac.hip); 0 on healthy hardware
     float *dec_w;     // the decoder's image (decoder.hip, DEC_O_*): dense_3, dense_4 as B fragments, conv3d_4, the folded conv3d_5 / conv3d_6; null until set
     bool has_dec;
     int dec_hidden, dec_out;   // CAELO_ACT_*: dense_3, dense_4, conv3d_4, conv3d_5 / conv3d_6 (caelo_set_decoder_model)

@@ -1,4 +1,4 @@
-// caelo_rigid.h -- 3x3 rigid fit (SolveRT, Match.py:138-158) shared by match.hip and icp.hip.  Device code only.
+// caelo_rigid.h -- 3x3 rigid fit (SolveRT, Match.py:138-158) shared by ransac.hip and icp.hip.  Device code only.
 #pragma once
 #include "caelo_internal.h"
 
@@ -36,7 +36,7 @@
     }
 #define JAC_SWAP(X, Y) { const double t_ = X; X = Y; Y = t_; }
 // SIGN3 = false: the rank-2 completion is right-handed whatever the sign of det H (the RANSAC hypothesis kernels: three live doubles
-// at their register peak; every rank-2 sample is a kind-1 hypothesis of the certificate there, both poses scored -- match.hip)
+// at their register peak; every rank-2 sample is a kind-1 hypothesis of the certificate there, both poses scored -- ransac.hip)
 template <bool SIGN3 = true>
 __device__ inline int rigid_from_H_jacobi(const double Hin[9], const double m0[3], const double m1[3], float R[9], float T[3]) {
     // A = H (columns 0, 1, 2 as a*0, a*1, a*2), V = I
@@ -198,3 +198,59 @@ __device__ inline int rigid_from_H(const double H[9], const double m0[3], const 
     return det0 < 0 ? -1 : 1;
 }
 
+// SolveRT over many pairs by one workgroup: every thread adds its pairs' count, sums and raw cross moments in f64 (RigidSums),
+// H = sum p1 p0^T - n m1 m0^T and the fit on one thread (rigid_from_sums), then P <- R P + T (rigid_move): k_solve_rt (ransac.hip)
+// and the ICP kernels (icp.hip).  The RANSAC kernels keep their own forms: sample_hypothesis, k_ransac_finish's refit (ransac.hip).
+#define RIGID_TERMS 16
+struct RigidSums {
+    double a[RIGID_TERMS] = {};  // [0] count, [1:4] sum p0, [4:7] sum p1, [7:16] sum p1 p0^T (row = p1's axis)
+    __device__ void add(double x0, double y0, double z0, double x1, double y1, double z1) {
+        a[0] += 1.0;
+        a[1] += x0; a[2] += y0; a[3] += z0;
+        a[4] += x1; a[5] += y1; a[6] += z1;
+        a[7] += x1 * x0; a[8] += x1 * y0; a[9] += x1 * z0;   // P1^T P0  (:146)
+        a[10] += y1 * x0; a[11] += y1 * y0; a[12] += y1 * z0;
+        a[13] += z1 * x0; a[14] += z1 * y0; a[15] += z1 * z0;
+    }
+    // the sums of the wavefront on each of its lanes; lane 0 leaves them in row `wave` of the caller's LDS array.  The caller
+    // owns the array and the barriers around it (k_icp_update reduces twice in one launch)
+    __device__ void reduce_wave(double (*red)[RIGID_TERMS], int lane, int wave) {
+#pragma unroll
+        for (int t = 0; t < RIGID_TERMS; ++t)
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
+        if (lane == 0)
+#pragma unroll
+            for (int t = 0; t < RIGID_TERMS; ++t) red[wave][t] = a[t];
+    }
+    // term t of the workgroup: the wavefronts' rows added in ascending order
+    static __device__ double combine(const double (*red)[RIGID_TERMS], int waves, int t) {
+        double s = red[0][t];
+        for (int w = 1; w < waves; ++w) s += red[w][t];
+        return s;
+    }
+};
+
+// the fit from the sixteen sums s (s[0] >= 1); returns isCredible like rigid_from_H
+__device__ inline int rigid_from_sums(const double s[RIGID_TERMS], float R[9], float T[3]) {
+    const double cnt = s[0];
+    const double m0[3] = {s[1] / cnt, s[2] / cnt, s[3] / cnt}, m1[3] = {s[4] / cnt, s[5] / cnt, s[6] / cnt};
+    double H[9];
+    for (int i = 0; i < 3; ++i)
+        for (int j = 0; j < 3; ++j) H[3 * i + j] = s[7 + 3 * i + j] - cnt * m1[i] * m0[j];
+    return rigid_from_H(H, m0, m1, R, T);
+}
+
+// p[ld j + 0:3] <- R p + T for the n points of a [n][ld] array, rt = (R | T), by the whole workgroup; float32 multiplies
+// and adds in this order like the reference's arrays:  PC1 = (np.dot(R, PC1.T) + T).T  (MyICP.py:49-50)
+__device__ inline void rigid_move(float *p, int ld, int n, const float rt[12]) {
+    const float r0 = rt[0], r1 = rt[1], r2 = rt[2], r3 = rt[3], r4 = rt[4], r5 = rt[5], r6 = rt[6], r7 = rt[7], r8 = rt[8];
+    const float t0 = rt[9], t1 = rt[10], t2 = rt[11];
+    for (int j = threadIdx.x; j < n; j += blockDim.x) {
+        float *q = p + (size_t)ld * j;
+        const float x = q[0], y = q[1], z = q[2];
+        q[0] = r0 * x + r1 * y + r2 * z + t0;
+        q[1] = r3 * x + r4 * y + r5 * z + t1;
+        q[2] = r6 * x + r7 * y + r8 * z + t2;
+    }
+}

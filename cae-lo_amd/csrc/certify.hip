@@ -5,7 +5,7 @@
 // float32), R = np.dot(V.T, U.T) (sgemm), T through sgemv, residuals through sgemm -- Match.py:141-157,:190-193.  The bits of
 // R and T therefore depend on the BLAS that NumPy was built with (accumulation order, fused or unfused multiply-adds: an
 // OpenBLAS Haswell kernel and a reference BLAS differ in the last bit of a third of the residuals), and a residual within
-// ~1e-5 m of the threshold falls on either side of it.  The kernels of match.hip fit in float64 and score all 500
+// ~1e-5 m of the threshold falls on either side of it.  The kernels of ransac.hip fit in float64 and score all 500
 // hypotheses; beside each count they give a rigorous UPPER BOUND on the count the reference's arithmetic can reach
 // (k_ransac_hyp, `hi`).  This file replays the sequential accept / exit rules of Match.py:181-214 over those bounds and
 // re-evaluates, through the very cblas_sgemm / cblas_sgemv / dgesdd entry points the process's NumPy calls (handed over by
@@ -245,7 +245,7 @@ int ransac_host(const float *P0, const float *P1, int64_t n, const double *rnd, 
                 if (!hypothesis(P0, P1, n, idx, thr, S, &f, S.m_best.data(), &cnt)) return -1;
                 ++out.evals;
                 // The argument above stands on hi[t] >= the reference's count.  The bound's constant is calibrated, not proven
-                // (match.hip, hypothesis_bound): every exact count this loop sees is checked against it, and ONE count above its bound
+                // (ransac.hip, hypothesis_bound): every exact count this loop sees is checked against it, and ONE count above its bound
                 // discards the bounds of the pair -- the level is redone as the reference's loop stands -- and is counted
                 // (caelo_host_bound_violations; the parity soak and bench.py print the counter).
                 if (cnt > hi[w]) { violated = true; break; }

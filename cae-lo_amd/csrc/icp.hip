@@ -11,11 +11,11 @@
 // Euler-angle stop rule and the threshold decay of the reference's loop).  Every launch starts by reading a `done`
 // word of the state record, so after the loop has ended the remaining launches fall through; the host reads the
 // record once.  Round 1 synchronised twice per iteration (Python loop around caelo_icp_step).
+// At the end: caelo_icp_step, one iteration on its own (k_icp_nn, k_icp_fit_apply) with the loop's walk, fit and move.
 #include "caelo_internal.h"
 #include "caelo_rigid.h"
 
 #define ICP_TILE 1024
-#define ICP_TERMS 16
 #define ICP_STATE_BYTES 512  // the state record's share of the workspace
 
 struct IcpState {
@@ -29,23 +29,18 @@ struct IcpState {
     int32_t pad;
     // ICP_Pt2PtAndPt2Plane from iteration 100 on (:151-153): the pair count and the fifteen sums over the planar pairs of
     // iteration 99.  Both arrays of those pairs are fitted again as they were then, so their sums are all that is needed
-    double stale[ICP_TERMS];
+    double stale[RIGID_TERMS];
 };
 static_assert(sizeof(IcpState) <= ICP_STATE_BYTES, "the state record outgrew its share of the workspace");
 
-// nearest neighbour in set 0 (stride ld0) of every point of set 1 (stride ld1); pairs closer than the threshold of the
-// state record (which = 0: thr0, 1: thr1).  Exact f64 distance, first minimum, like sklearn's kd-tree on these inputs.
-__global__ void __launch_bounds__(256) k_icp_nn2(const float *__restrict__ p0, int ld0, int n0, const float *__restrict__ p1, int ld1, int n1,
-                                                 IcpState *st, int which, int64_t *__restrict__ idx0, uint8_t *__restrict__ mask) {
-    if (st->done || (which && st->iter >= 100)) return;  // from iteration 100 on the planar pairs are not searched again (:151-153)
-    __shared__ float tile[ICP_TILE * 3];
+// The brute-force walk of both nearest-neighbour kernels, by a whole 256-thread workgroup: set 0 (stride ld0, n0 points) passes
+// through the LDS tile and every thread returns the index of the point nearest to its query q, `best` the squared distance.
+// Exact f64 distance, first minimum, like sklearn's kd-tree on these inputs.
+__device__ inline int icp_nn_walk(const float *__restrict__ p0, int ld0, int n0, double qx, double qy, double qz, float *tile,
+                                  double &best) {
     const int tid = threadIdx.x;
-    const int j = blockIdx.x * blockDim.x + tid;
-    const double thr = which ? st->thr1 : st->thr0;
-    double qx = 0.0, qy = 0.0, qz = 0.0;
-    if (j < n1) { qx = p1[(size_t)ld1 * j]; qy = p1[(size_t)ld1 * j + 1]; qz = p1[(size_t)ld1 * j + 2]; }
-    double best = 1.0e300;
-    int besti = 0;
+    double b = 1.0e300;
+    int bi = 0;
     for (int base = 0; base < n0; base += ICP_TILE) {
         const int m = min(ICP_TILE, n0 - base);
         __syncthreads();
@@ -56,10 +51,26 @@ __global__ void __launch_bounds__(256) k_icp_nn2(const float *__restrict__ p0, i
         __syncthreads();
         for (int i = 0; i < m; ++i) {  // all lanes read the same address: LDS broadcast
             const double dx = (double)tile[3 * i] - qx, dy = (double)tile[3 * i + 1] - qy, dz = (double)tile[3 * i + 2] - qz;
-            const double d2 = dx * dx + dy * dy + dz * dz;
-            if (d2 < best) { best = d2; besti = base + i; }
+            const double d2 = dx * dx + dy * dy + dz * dz;  // sequential x, y, z like the kd-tree's reduced distance
+            if (d2 < b) { b = d2; bi = base + i; }
         }
     }
+    best = b;  // (updated through the reference inside the loop, the minimum was kept twice there: caelo_icp 8 % slower)
+    return bi;
+}
+
+// nearest neighbour in set 0 (stride ld0) of every point of set 1 (stride ld1); pairs closer than the threshold of the
+// state record (which = 0: thr0, 1: thr1).
+__global__ void __launch_bounds__(256) k_icp_nn2(const float *__restrict__ p0, int ld0, int n0, const float *__restrict__ p1, int ld1, int n1,
+                                                 IcpState *st, int which, int64_t *__restrict__ idx0, uint8_t *__restrict__ mask) {
+    if (st->done || (which && st->iter >= 100)) return;  // from iteration 100 on the planar pairs are not searched again (:151-153)
+    __shared__ float tile[ICP_TILE * 3];
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    const double thr = which ? st->thr1 : st->thr0;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (j < n1) { qx = p1[(size_t)ld1 * j]; qy = p1[(size_t)ld1 * j + 1]; qz = p1[(size_t)ld1 * j + 2]; }
+    double best;
+    const int besti = icp_nn_walk(p0, ld0, n0, qx, qy, qz, tile, best);
     if (j < n1) {
         idx0[j] = besti;
         mask[j] = (n0 > 0 && sqrt(best) < thr) ? 1 : 0;  // distances < inlierThreshold (:80, :100)
@@ -92,7 +103,7 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
                                                     const uint8_t *__restrict__ mask_p, const float *__restrict__ pn0, float *__restrict__ pn1, int m1,
                                                     const int64_t *__restrict__ idx_q, const uint8_t *__restrict__ mask_q, IcpState *st, IcpParams prm) {
     if (st->done) return;
-    __shared__ double red[4][ICP_TERMS + 2];
+    __shared__ double red[4][RIGID_TERMS], red_n[4][2];
     __shared__ float s_rt[12];
     __shared__ int s_stop;
     const int tid = threadIdx.x;
@@ -102,80 +113,56 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
     // there; ICP has no such branch)
     const int iter0 = st->iter;
     const bool stale = prm.planar && iter0 >= 100;
-    double a[ICP_TERMS + 2];
-#pragma unroll
-    for (int t = 0; t < ICP_TERMS + 2; ++t) a[t] = 0.0;
-#define ICP_ACC(X0, Y0, Z0, X1, Y1, Z1)                                               \
-    {                                                                                 \
-        const double x0 = X0, y0 = Y0, z0 = Z0, x1 = X1, y1 = Y1, z1 = Z1;            \
-        a[0] += 1.0;                                                                  \
-        a[1] += x0; a[2] += y0; a[3] += z0; a[4] += x1; a[5] += y1; a[6] += z1;       \
-        a[7] += x1 * x0; a[8] += x1 * y0; a[9] += x1 * z0;                            \
-        a[10] += y1 * x0; a[11] += y1 * y0; a[12] += y1 * z0;                         \
-        a[13] += z1 * x0; a[14] += z1 * y0; a[15] += z1 * z0;                         \
-    }
+    const int lane = tid & 63, wave = tid >> 6;
+    RigidSums sums;
+    double n_pts = 0.0, n_planar = 0.0;  // point pairs (counted from iteration 100 on as well) and planar pairs of this iteration
     if (prm.planar && iter0 == 99) {  // the planar pairs on their own, kept for the iterations that follow
         for (int j = tid; j < m1; j += 256) {
             float pedal[3], in1[3];
             if (!planar_pair(pn0, pn1, idx_q, mask_q, j, thr0, pedal, in1)) continue;
-            ICP_ACC(pedal[0], pedal[1], pedal[2], in1[0], in1[1], in1[2])
+            sums.add(pedal[0], pedal[1], pedal[2], in1[0], in1[1], in1[2]);
         }
-#pragma unroll
-        for (int t = 0; t < ICP_TERMS; ++t) {
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
-            if ((tid & 63) == 0) red[tid >> 6][t] = a[t];
-            a[t] = 0.0;
-        }
+        sums.reduce_wave(red, lane, wave);
+        sums = RigidSums();
         __syncthreads();
-        if (tid < ICP_TERMS) st->stale[tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
+        if (tid < RIGID_TERMS) st->stale[tid] = RigidSums::combine(red, 4, tid);
         __syncthreads();
     }
     for (int i = tid; i < n1; i += 256) {
         if (!mask_p[i]) continue;
-        a[16] += 1.0;
+        n_pts += 1.0;
         if (stale) continue;
         const float *u = pc0 + 3 * (size_t)idx_p[i], *v = pc1 + 3 * (size_t)i;
-        ICP_ACC(u[0], u[1], u[2], v[0], v[1], v[2])
+        sums.add(u[0], u[1], u[2], v[0], v[1], v[2]);
     }
     if (prm.planar && !stale) {
         for (int j = tid; j < m1; j += 256) {
             float pedal[3], in1[3];
             if (!planar_pair(pn0, pn1, idx_q, mask_q, j, thr0, pedal, in1)) continue;
-            a[17] += 1.0;
-            ICP_ACC(pedal[0], pedal[1], pedal[2], in1[0], in1[1], in1[2])
+            n_planar += 1.0;
+            sums.add(pedal[0], pedal[1], pedal[2], in1[0], in1[1], in1[2]);
         }
     }
+    sums.reduce_wave(red, lane, wave);
 #pragma unroll
-    for (int t = 0; t < ICP_TERMS + 2; ++t)
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) a[t] += __shfl_xor(a[t], o);
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int t = 0; t < ICP_TERMS + 2; ++t) red[tid >> 6][t] = a[t];
+    for (int o = 32; o > 0; o >>= 1) { n_pts += __shfl_xor(n_pts, o); n_planar += __shfl_xor(n_planar, o); }
+    if (lane == 0) { red_n[wave][0] = n_pts; red_n[wave][1] = n_planar; }
     __syncthreads();
     if (tid == 0) {
-        double s[ICP_TERMS + 2];
-        for (int t = 0; t < ICP_TERMS + 2; ++t) s[t] = red[0][t] + red[1][t] + red[2][t] + red[3][t];
-        if (stale) {  // the count that the reference goes on printing is the one of iteration 99 as well (:199)
-            for (int t = 0; t < ICP_TERMS; ++t) s[t] = st->stale[t];
-            s[17] = st->stale[0];
-        }
+        double s[RIGID_TERMS];
+        for (int t = 0; t < RIGID_TERMS; ++t) s[t] = RigidSums::combine(red, 4, t);
+        if (stale)  // the count that the reference goes on printing is the one of iteration 99 as well (:199)
+            for (int t = 0; t < RIGID_TERMS; ++t) s[t] = st->stale[t];
+        st->n_pts = (int)(red_n[0][0] + red_n[1][0] + red_n[2][0] + red_n[3][0]);
+        st->n_planar = (int)(stale ? s[0] : red_n[0][1] + red_n[1][1] + red_n[2][1] + red_n[3][1]);
         const int pairs = (int)s[0];
-        st->n_pts = (int)s[16];
-        st->n_planar = (int)s[17];
         int stop = 0;
         if (pairs < prm.min_pairs) {  // ICP :38-40 / Pt2Plane :166-169
             if (!prm.fail_only_first || st->iter < 1) st->success = 0;
             stop = 1;
         } else {
-            const double cnt = s[0];
-            const double m0[3] = {s[1] / cnt, s[2] / cnt, s[3] / cnt}, m1c[3] = {s[4] / cnt, s[5] / cnt, s[6] / cnt};
-            double H[9];
-            for (int i = 0; i < 3; ++i)
-                for (int j = 0; j < 3; ++j) H[3 * i + j] = s[7 + 3 * i + j] - cnt * m1c[i] * m0[j];
             float R[9], T[3];
-            rigid_from_H(H, m0, m1c, R, T);
+            rigid_from_sums(s, R, T);
             for (int i = 0; i < 9; ++i) s_rt[i] = R[i];
             for (int i = 0; i < 3; ++i) s_rt[9 + i] = T[i];
             // R_star = R R_star, T_star = R T_star + T in float64 (:50-51)
@@ -205,22 +192,8 @@ __global__ void __launch_bounds__(256) k_icp_update(const float *__restrict__ pc
     }
     __syncthreads();
     if (s_stop == 1) return;  // too few pairs: nothing is moved
-    const float r0 = s_rt[0], r1 = s_rt[1], r2 = s_rt[2], r3 = s_rt[3], r4 = s_rt[4], r5 = s_rt[5], r6 = s_rt[6], r7 = s_rt[7], r8 = s_rt[8];
-    const float t0 = s_rt[9], t1 = s_rt[10], t2 = s_rt[11];
-    for (int j = tid; j < n1; j += 256) {  // PC1 = (np.dot(R, PC1.T) + T).T  (:49)
-        const float x = pc1[3 * (size_t)j], y = pc1[3 * (size_t)j + 1], z = pc1[3 * (size_t)j + 2];
-        pc1[3 * (size_t)j] = r0 * x + r1 * y + r2 * z + t0;
-        pc1[3 * (size_t)j + 1] = r3 * x + r4 * y + r5 * z + t1;
-        pc1[3 * (size_t)j + 2] = r6 * x + r7 * y + r8 * z + t2;
-    }
-    if (prm.planar)
-        for (int j = tid; j < m1; j += 256) {  // the planar points move, their normals do not (:177)
-            float *q = pn1 + 6 * (size_t)j;
-            const float x = q[0], y = q[1], z = q[2];
-            q[0] = r0 * x + r1 * y + r2 * z + t0;
-            q[1] = r3 * x + r4 * y + r5 * z + t1;
-            q[2] = r6 * x + r7 * y + r8 * z + t2;
-        }
+    rigid_move(pc1, 3, n1, s_rt);                   // :49
+    if (prm.planar) rigid_move(pn1, 6, m1, s_rt);   // the planar points move, their normals do not (:177)
 }
 
 __global__ void k_icp_init(IcpState *st, double thr0, double thr1) {
@@ -276,6 +249,74 @@ CAELO_API int caelo_icp(caelo_ctx *c, const float *pc0, int64_t n0, float *pc1, 
         CAELO_LAUNCH_CHECK();
     }
     k_icp_result<<<1, 1, 0, s>>>(st, result);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// ICP step: MyICP.py:26-72 / :75-85 -- the refinement that follows the odometry
+// ------------------------------------------------------------------------------------------------
+// One iteration of the reference's point-to-point ICP: for every point of PC1 its nearest neighbour in PC0
+// (sklearn NearestNeighbors(n_neighbors=1): exact Euclidean distance in float64), the pairs closer than the
+// threshold, SolveRT on them, PC1 <- R PC1 + T.  The iteration control (threshold decay, Euler-angle stop rule)
+// stays on the host, like the reference's Python loop.
+__global__ void __launch_bounds__(256) k_icp_nn(const float *__restrict__ pc0, int n0, const float *__restrict__ pc1, int n1,
+                                                double thr, int64_t *__restrict__ idx0, uint8_t *__restrict__ mask,
+                                                int32_t *__restrict__ n_in) {
+    __shared__ float tile[ICP_TILE * 3];
+    __shared__ int s_cnt;
+    const int tid = threadIdx.x;
+    const int j = blockIdx.x * blockDim.x + tid;
+    if (tid == 0) s_cnt = 0;
+    double qx = 0.0, qy = 0.0, qz = 0.0;
+    if (j < n1) { qx = pc1[3 * (size_t)j]; qy = pc1[3 * (size_t)j + 1]; qz = pc1[3 * (size_t)j + 2]; }
+    double best;
+    const int besti = icp_nn_walk(pc0, 3, n0, qx, qy, qz, tile, best);
+    const bool in = j < n1 && sqrt(best) < thr;  // GetPtsInliners: distances < inlierThreshold (:80)
+    if (j < n1) { idx0[j] = besti; mask[j] = in ? 1 : 0; }
+    const unsigned long long bal = __ballot(in);
+    if ((tid & 63) == 0 && bal) atomicAdd(&s_cnt, __popcll(bal));
+    __syncthreads();
+    if (tid == 0 && s_cnt) atomicAdd(n_in, s_cnt);
+}
+
+// SolveRT on the inlier pairs and PC1 <- R PC1 + T (one workgroup; float32 like the reference's arrays)
+__global__ void __launch_bounds__(256) k_icp_fit_apply(const float *__restrict__ pc0, float *__restrict__ pc1, int n1,
+                                                       const int64_t *__restrict__ idx0, const uint8_t *__restrict__ mask,
+                                                       const int32_t *__restrict__ n_in, int min_inliers, float *__restrict__ rt) {
+    if (*n_in < min_inliers) return;  // the host stops the iteration (MyICP.py:38-40)
+    __shared__ double red[4][RIGID_TERMS];
+    const int tid = threadIdx.x;
+    RigidSums sums;
+    for (int i = tid; i < n1; i += 256) {  // (k_icp_update's walk over the point pairs)
+        if (!mask[i]) continue;
+        const float *u = pc0 + 3 * (size_t)idx0[i], *v = pc1 + 3 * (size_t)i;
+        sums.add(u[0], u[1], u[2], v[0], v[1], v[2]);
+    }
+    sums.reduce_wave(red, tid & 63, tid >> 6);
+    __syncthreads();
+    if (tid == 0) {
+        double s[RIGID_TERMS];
+        for (int t = 0; t < RIGID_TERMS; ++t) s[t] = RigidSums::combine(red, 4, t);
+        if (s[0] >= 1.0) rigid_from_sums(s, rt, rt + 9);  // (min_inliers <= 0 and no pair: rt stays the caller's)
+    }
+    __syncthreads();
+    rigid_move(pc1, 3, n1, rt);  // :50
+}
+
+CAELO_API int64_t caelo_icp_ws_bytes(int64_t n1) { return ((n1 * 9 + 255) / 256) * 256 + 256; }
+
+CAELO_API int caelo_icp_step(caelo_ctx *c, const float *pc0, int64_t n0, float *pc1, int64_t n1, double threshold,
+                             int min_inliers, float *rt, int32_t *n_inliers, void *ws, void *stream) {
+    CAELO_REQUIRE(c && pc0 && pc1 && rt && n_inliers && ws, "null argument");
+    CAELO_REQUIRE(n0 > 0 && n1 > 0 && n0 < (1 << 30) && n1 < (1 << 30), "bad shape");
+    hipStream_t s = caelo_stream(stream);
+    int64_t *idx0 = (int64_t *)ws;
+    uint8_t *mask = (uint8_t *)(idx0 + n1);
+    CAELO_HIP(hipMemsetAsync(n_inliers, 0, sizeof(int32_t), s));
+    k_icp_nn<<<(unsigned)((n1 + 255) / 256), 256, 0, s>>>(pc0, (int)n0, pc1, (int)n1, threshold, idx0, mask, n_inliers);
+    CAELO_LAUNCH_CHECK();
+    k_icp_fit_apply<<<1, 256, 0, s>>>(pc0, pc1, (int)n1, idx0, mask, n_inliers, min_inliers, rt);
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
 }

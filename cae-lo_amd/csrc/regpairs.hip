@@ -1,7 +1,7 @@
 // regpairs.hip -- caelo_register_pairs: the pipeline's pair stage (NN match, RANSAC hypotheses, certificates, refit) over a TABLE of
 // frame pairs whose rows are already resident, e.g. the frame steps 2, 5, 10 of a sequence after ONE extraction pass.
 //
-// Nothing is computed here that the consecutive path does not compute: match_table / ransac_table (match.hip) launch the pair
+// Nothing is computed here that the consecutive path does not compute: match_table (match.hip) and ransac_table (ransac.hip) launch the pair
 // stage's kernel bodies instantiated for a device pair table instead of a caelo_pair_set, so a pair gives the bits it gives in
 // a pipeline batch or through caelo_match + caelo_ransac.  What this file adds is the host side: the argument checks (the table
 // and the key point counts are read back once, before any launch), the slice order and the walk over the slices.

@@ -1,4 +1,4 @@
-"""The device-resident ICP loops (csrc/icp.hip: k_icp_nn2, k_icp_update, caelo_icp; caelo_icp_step) iteration by iteration
+"""The device-resident ICP loops (csrc/icp.hip: k_icp_nn2, k_icp_update, caelo_icp; k_icp_nn, k_icp_fit_apply, caelo_icp_step) iteration by iteration
 against the oracle's loops on the crafted clouds of tests/icp_clouds.py, and against what the reference itself returned
 on them (tests/golden/icp_loop.npz).
 
@@ -221,3 +221,23 @@ def test_icp_step_vs_one_oracle_iteration(engine, oracle_runs):
     _within("step", "R", rt[:9].reshape(3, 3), step["R_star"])
     _within("step", "T", rt[9:], step["T_star"])
     _within("step", "move", d1.cpu().numpy(), pc1.astype(np.float64) @ rt[:9].reshape(3, 3).T + rt[9:])
+
+
+@pytest.mark.parametrize("case", ["points", "edges"])
+def test_icp_step_is_the_loops_first_iteration(engine, case):
+    """Without planar points caelo_icp with max_iter = 1 and caelo_icp_step are the same computation -- one walk, one fit, one
+    move (icp_nn_walk; RigidSums, rigid_from_sums, rigid_move of csrc/caelo_rigid.h) -- so pose, pair count and the moved
+    cloud agree exactly: the loop multiplies the step's float32 pose into the identity in float64, which is exact.  On the
+    `points` clouds and on those of test_tile_and_block_edges with n0 one past the LDS tile and n1 one past a workgroup."""
+    import torch
+    pc0, pc1 = icp_clouds.clouds("points") if case == "points" else icp_clouds.shape_clouds(1025, 257)[:2]
+    least = 100 if case == "points" else 4
+    r, moved = _run(engine, (pc0, pc1), threshold0=0.5, max_iter=1, min_pairs=least)
+    d1 = torch.from_numpy(pc1.copy()).to(engine.device)
+    rt, n_in = engine.icp_step(torch.from_numpy(pc0).to(engine.device), d1, 0.5, min_inliers=least)
+    rt = rt.cpu().numpy()
+    assert (r.iterations, r.success) == (1, 1) and int(n_in.item()) >= least
+    assert (np.array(r.R_star) == rt[:9].astype(np.float64)).all()
+    assert (np.array(r.T_star) == rt[9:12].astype(np.float64)).all()
+    assert r.n_inliers_pts == int(n_in.item())
+    assert moved[1].tobytes() == d1.cpu().numpy().tobytes() and moved[1].tobytes() != pc1.tobytes()
