@@ -169,6 +169,7 @@ SIGNATURES = [
     ("caelo_extract_ws_bytes", c_i64, []),
     ("caelo_extract_ws_frame_offset", c_i64, []),
     ("caelo_extract_ws_kp_eligible_offset", c_i64, []),
+    ("caelo_extract_ws_ring_offset", c_i64, []),
     ("caelo_extract", c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp,
                               c_vp, c_vp]),
     ("caelo_extend_ws_bytes", c_i64, [c_int, c_int]),
@@ -190,6 +191,7 @@ SIGNATURES = [
     ("caelo_pipeline_set_pace", c_int, [c_vp, c_int]),
     ("caelo_pipeline_get_pace", c_int, [c_vp]),
     ("caelo_pipeline_streams", c_int, [c_vp, c_vp]),
+    ("caelo_pipeline_extract_ws_read", c_int, [c_vp, c_int, c_i64, c_i64, c_vp, c_vp]),
     ("caelo_upload_many", c_int, [c_vp, c_vp, c_vp, c_int, c_vp]),
     ("caelo_pipeline_run_uploading", c_int, [c_vp, c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_int, c_vp, c_i64, c_int, c_vp, c_vp, c_vp]),
     ("caelo_host_random_sample", c_int, [C.c_uint32, c_i64, c_vp]),

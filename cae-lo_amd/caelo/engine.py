@@ -242,6 +242,20 @@ class Pipeline:
         _ffi.check(self.eng.lib.caelo_pipeline_streams(self.h, out))
         return dict(zip(("front", "encoder", "pair", "voxel"), (out[i] for i in range(4))))
 
+    def extract_ring_and_map(self, i):
+        """Test aid: what the last batch left in the extract workspace of its frame ``i`` (caelo_pipeline_extract_ws_read) -> host
+        arrays (ring image [69,1800,5] f32, eligibility map [64] uint64, as ``Engine.extract_kp_eligible``).  On the current stream,
+        which ``run`` left waiting for every stage; synchronises."""
+        eng = self.eng
+        out = []
+        for off, n in ((int(eng.lib.caelo_extract_ws_ring_offset()), RING_H * RING_W * RING_C * 4),
+                       (int(eng.lib.caelo_extract_ws_kp_eligible_offset()), NET_H * 8)):
+            buf = eng.empty((n,), torch.uint8)
+            _ffi.check(eng.lib.caelo_pipeline_extract_ws_read(self.h, int(i), off, n, _ptr(buf), eng.stream))
+            out.append(buf)
+        torch.cuda.current_stream(eng.device).synchronize()
+        return (out[0].cpu().numpy().view(np.float32).reshape(RING_H, RING_W, RING_C).copy(), out[1].cpu().numpy().view(np.uint64).copy())
+
     def _jobs(self, ptrs, counts, rands, prev, out, pairs, dist_channels, exact_voxels, dedup, certify=False, rands_host=None, exact_patches=False,
               calib_angle=None):
         """The run's jobs as one record array, filled column-wise, handed over in ONE foreign call (a ctypes call per frame

@@ -66,6 +66,7 @@ struct caelo_ctx {
     int enc_hidden, enc_code;   // CAELO_ACT_*: conv3d_1..3 + dense_1 / dense_2 (caelo_set_encoder_model); tanh / tanh from caelo_create on
     bool enc_reference;   // caelo_set_encoder_reference: stage 1 = the exact-f32 k_enc_stage1 (precision reference)
     int32_t *faults;  // device counter of the pair kernels' lane-agreement checks (ransac.hip); 0 on healthy hardware
+    double *proj_edge;  // [1801][4] sin / cos (hi, lo) of the projection's column edges (ring.hip: proj_edge_table; made by caelo_create)
     float *dec_w;     // the decoder's image (decoder.hip, DEC_O_*): dense_3, dense_4 as B fragments, conv3d_4, the folded conv3d_5 / conv3d_6; null until set
     bool has_dec;
     int dec_hidden, dec_out;   // CAELO_ACT_*: dense_3, dense_4, conv3d_4, conv3d_5 / conv3d_6 (caelo_set_decoder_model)
@@ -278,14 +279,14 @@ int caelo_clear_many(const caelo_clear_list &list, hipStream_t s);
 int caelo_clear_many_set(const caelo_clear_list *lists, int n_frames, hipStream_t s);  // one launch, blockIdx.y = frame
 
 // internal launchers shared by the staged entry points and the fused caelo_extract (no clears inside)
-int ring_project_launch(const float *pc, int64_t n, float *ring, int32_t *counter, int32_t *winner, int32_t *status,
+int ring_project_launch(caelo_ctx *c, const float *pc, int64_t n, float *ring, int32_t *counter, int32_t *winner, int32_t *status,
                         hipStream_t s);
 int ring_respond_launch(caelo_ctx *c, const float *in, int in_w, int in_c, float *resp, hipStream_t s);
 int ring_keypoints_launch(const float *ring, int ring_w, int ring_c, int dist_c, const int32_t *counter, int cnt_w,
                           const float *resp, unsigned long long *cand, int32_t *cand_count,
                           int64_t *key_pixels, float *key_pts, int kp_ld, float *valid, int valid_ld, int32_t *n_key,
                           int32_t *status, hipStream_t s);
-int ring_project_set(const caelo_frame_set &fs, hipStream_t s);
+int ring_project_set(caelo_ctx *c, const caelo_frame_set &fs, hipStream_t s);
 int ring_respond_set(caelo_ctx *c, const caelo_frame_set &fs, int in_w, int in_c, hipStream_t s, int row0, int rows);
 int ring_keypoints_set(const caelo_frame_set &fs, int ring_w, int ring_c, int cnt_w, hipStream_t s);
 void vox_clear_items(caelo_voxmap *m, int level, caelo_clear_list &list);  // 0 brick keys only, 1 + scale-0 first-touch table, 2 everything

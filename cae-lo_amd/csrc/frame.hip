@@ -141,6 +141,8 @@ CAELO_API int64_t caelo_extract_ws_bytes(void) { return (int64_t)extract_layout(
 CAELO_API int64_t caelo_extract_ws_frame_offset(void) { return (int64_t)extract_layout().bits; }
 // (read-only, for tests of the key point eligibility map: k_ring_fill's 64 row words)
 CAELO_API int64_t caelo_extract_ws_kp_eligible_offset(void) { return (int64_t)extract_layout().kp_elig; }
+// (read-only, for tests of the projection on the fused path: the ring image [69][1800][5] f32)
+CAELO_API int64_t caelo_extract_ws_ring_offset(void) { return (int64_t)extract_layout().ring; }
 
 // The fused path in two halves so that the frame pipeline can put an event edge between them:
 // front = clear + ring image + response + keypoints + voxel map + patch gather (latency-bound kernels),
@@ -257,7 +259,7 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     if (given) {
         if ((rc = given_keypts_set(fs, s))) return rc;
     } else {
-        if ((rc = ring_project_set(fs, s))) return rc;
+        if ((rc = ring_project_set(args[0].ctx, fs, s))) return rc;
         // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
         if ((rc = ring_respond_set(args[0].ctx, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52))) return rc;
         if ((rc = ring_keypoints_set(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W, s))) return rc;

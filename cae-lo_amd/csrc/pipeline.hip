@@ -594,6 +594,16 @@ CAELO_API int caelo_pipeline_streams(const caelo_pipeline *p, void **out_host) {
     return CAELO_OK;
 }
 
+// (read-only, for tests of the front kernels' frame sets: `bytes` bytes at `offset` of the extract workspace of frame slot i of a batch,
+// which is laid out as caelo_extract's, copied to the device buffer `dst` on `stream`; ordered by `stream` alone (include/caelo.h))
+CAELO_API int caelo_pipeline_extract_ws_read(const caelo_pipeline *p, int i, int64_t offset, int64_t bytes, void *dst, void *stream) {
+    CAELO_REQUIRE(p && dst, "null argument");
+    CAELO_REQUIRE(i >= 0 && i < p->batch && i < CAELO_FB_MAX, "no such frame slot");
+    CAELO_REQUIRE(offset >= 0 && bytes >= 0 && offset + bytes <= caelo_extract_ws_bytes(), "range outside the workspace");
+    if (bytes) CAELO_HIP(hipMemcpyAsync(dst, (const char *)p->ws_extract[i] + offset, (size_t)bytes, hipMemcpyDeviceToDevice, caelo_stream(stream)));
+    return CAELO_OK;
+}
+
 CAELO_API int caelo_pipeline_cert_stats(caelo_pipeline *p, int64_t *out_host) {
     CAELO_REQUIRE(p && out_host, "null argument");
     std::lock_guard<std::mutex> lk(p->cert_mu);

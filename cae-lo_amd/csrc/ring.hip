@@ -7,7 +7,10 @@
 // All three are HBM/latency-bound at these sizes (2 MB of points, 3.7 MB response image):
 // one thread per point / pixel, coalesced rows, no intermediate tensors (the reference's CuPy path
 // materialises a 92 MB [64,1792,25,8] difference tensor, SphericalRing.py:144).
+#include <math.h>
 #include <stdarg.h>
+
+#include <vector>
 
 #include "caelo_internal.h"
 
@@ -30,6 +33,8 @@ CAELO_API int caelo_abi_version(void) { return CAELO_ABI_VERSION; }
 #endif
 CAELO_API int caelo_build_flags(void) { return CAELO_BUILD_WORD; }
 
+static int proj_edge_table(double **out);
+
 CAELO_API int caelo_create(caelo_ctx **out, int device) {
     CAELO_REQUIRE(out != nullptr, "null ctx pointer");
     int ndev = 0;
@@ -41,6 +46,11 @@ CAELO_API int caelo_create(caelo_ctx **out, int device) {
     c->device = device;
     CAELO_HIP(hipMalloc((void **)&c->faults, sizeof(int32_t)));
     CAELO_HIP(hipMemset(c->faults, 0, sizeof(int32_t)));
+    const int rc = proj_edge_table(&c->proj_edge);   // the projection's column edges (k_project_points)
+    if (rc) {
+        caelo_destroy(c);
+        return rc;
+    }
     *out = c;
     return CAELO_OK;
 }
@@ -51,7 +61,7 @@ CAELO_API void caelo_destroy(caelo_ctx *c) {
                      c->enc_b3, c->enc_bd1, c->enc_wd2, c->enc_bd2, c->enc32_bd1, c->dec_w};
     for (float *p : ptrs)
         if (p) (void)hipFree(p);
-    for (void *p : {c->enc_w1f, c->enc_w2x, c->enc_w3x, c->enc_wd1x, c->enc32_wd1x, c->enc_wd2q, (void *)c->faults})
+    for (void *p : {c->enc_w1f, c->enc_w2x, c->enc_w3x, c->enc_wd1x, c->enc32_wd1x, c->enc_wd2q, (void *)c->faults, (void *)c->proj_edge})
         if (p) (void)hipFree(p);
     delete c;
 }
@@ -92,7 +102,60 @@ CAELO_API int caelo_set_respond_weights(caelo_ctx *c, const float *w1, const flo
 // ------------------------------------------------------------------------------------------------
 struct ProjConst {
     double pi, az_res, v_res, v_off;
+    const double *edge;   // [1801][4]: sin and cos of the column edges' midpoint angles as hi / lo pairs (proj_edge_table)
 };
+
+// The column is int(colf) with colf = (pi - atan2(y, x)) / az_res, and the device's f64 atan2 is not the host's: on float32 points
+// whose atan2 is the last double of a column or the first of the one before, the two differ in the last bit and the point lands a
+// column beside the reference's (tests/golden/ring_edges.npz has a few hundred such points; tests/test_ring_edges_gpu.py).  So where
+// colf comes within PROJ_EDGE_BAND of an integer c -- far more than the device function is off by, about one point in 1e10 -- the
+// side is decided without atan2.  a -> fl(fl(pi - a) / az_res) is monotone: column c ends at a double A_c, and a correctly rounded
+// atan2(y, x) is <= A_c exactly when the direction (x, y) lies before the angle M_c half way between A_c and the next double, that is
+// when x sin M_c - y cos M_c > 0.  x and y are float32 and sin M_c, cos M_c are hi + lo doubles, so the two leading products are exact
+// as product + fma residue, their difference is exact (they cancel), and the rest is below the last bits of either.  The table holds
+// M_c to the 64 bits of the host's long double: the decision is the host libm's wherever its atan2 is correctly rounded and the
+// direction is not within 2^-11 ulp of M_c.
+// The band: OpenCL's bound for a double atan2, which the device library is written to, is 6 ulp, at most 6 * 4.4e-16 / az_res = 7.6e-13
+// columns, and the subtraction and the division add an ulp of colf each (4.5e-13 at column 1800): 1.2e-12 in all, assumed, not
+// measured.  The band is thirty times that.  Seen on the fixture: every point the kernel moved before it had this path is one whose
+// column changes under ONE ulp of atan2, none of those that need two.
+#define PROJ_EDGE_BAND 4e-11
+
+static ProjConst proj_const(const double *edge) {
+    ProjConst k;
+    k.pi = 3.14159265358979323846;
+    const double d2r = k.pi / 180.0;                        // SphericalRing.py:28
+    k.az_res = 0.20 * d2r;                                  // :35,:48
+    const double vdown = -24.8 * d2r, vup = 2.0 * d2r;      // :49-50
+    k.v_res = (vup - vdown) / (64 - 1);                     // :51
+    k.v_off = -vdown / k.v_res;                             // :52
+    k.edge = edge;
+    return k;
+}
+
+static bool proj_col_at_least(const ProjConst &k, double a, int c) { return (int)((k.pi - a) / k.az_res) >= c; }
+
+// host: the table (57 KB), made by caelo_create for the context's device and freed by caelo_destroy
+static int proj_edge_table(double **out) {
+    const ProjConst k = proj_const(nullptr);
+    std::vector<double> tab(4 * (CAELO_RING_W + 1), 0.0);
+    for (int c = 1; c <= CAELO_RING_W; ++c) {
+        // A_c: the largest double whose column is >= c, by bisection (the doubles around A_900 = 2.2e-16 are 1e-32 apart)
+        double lo = k.pi - c * k.az_res - 1e-9, hi = k.pi - c * k.az_res + 1e-9;
+        for (;;) {
+            const double mid = lo + (hi - lo) / 2;
+            if (mid <= lo || mid >= hi) break;
+            if (proj_col_at_least(k, mid, c)) lo = mid; else hi = mid;
+        }
+        const long double m = ((long double)lo + (long double)nextafter(lo, 4.0)) / 2;   // exact: 54 bits
+        const long double s = sinl(m), co = cosl(m);
+        tab[4 * c + 0] = (double)s;  tab[4 * c + 1] = (double)(s - (long double)tab[4 * c + 0]);
+        tab[4 * c + 2] = (double)co; tab[4 * c + 3] = (double)(co - (long double)tab[4 * c + 2]);
+    }
+    CAELO_HIP(hipMalloc((void **)out, tab.size() * sizeof(double)));
+    CAELO_HIP(hipMemcpy(*out, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    return CAELO_OK;
+}
 
 // every kernel below: blockIdx.z = frame of the set (caelo_internal.h)
 __global__ void __launch_bounds__(256) k_project_points(const caelo_frame_set fs, ProjConst k) {
@@ -114,7 +177,15 @@ __global__ void __launch_bounds__(256) k_project_points(const caelo_frame_set fs
         atomicOr(status, CAELO_ST_NONFINITE);
         return;
     }
-    const int col = (int)colf;
+    int col = (int)colf;
+    const double edge = rint(colf);
+    if (fabs(colf - edge) <= PROJ_EDGE_BAND && edge >= 1.0 && edge <= (double)CAELO_RING_W && fabsf(p.x) < INFINITY && fabsf(p.y) < INFINITY) {
+        const double *t = k.edge + 4 * (int)edge;
+        const double x = (double)p.x, y = (double)p.y;
+        const double xs = __dmul_rn(x, t[0]), yc = __dmul_rn(y, t[2]);              // (no contraction: the residues below are these products')
+        const double rest = __dadd_rn(__dsub_rn(__fma_rn(x, t[0], -xs), __fma_rn(y, t[2], -yc)), __dsub_rn(__dmul_rn(x, t[1]), __dmul_rn(y, t[3])));
+        col = __dadd_rn(__dsub_rn(xs, yc), rest) > 0.0 ? (int)edge : (int)edge - 1;
+    }
     const int row = CAELO_RING_H - (int)rowf;
     if (row < 0 || row >= CAELO_RING_H) return;                                       // :89
     if (col < 0 || col >= CAELO_RING_W) {
@@ -198,24 +269,18 @@ static int64_t set_max_points(const caelo_frame_set &fs) {
     return n;
 }
 
-int ring_project_launch(const float *pc, int64_t n, float *ring, int32_t *counter, int32_t *winner_ws, int32_t *status,
+int ring_project_launch(caelo_ctx *c, const float *pc, int64_t n, float *ring, int32_t *counter, int32_t *winner_ws, int32_t *status,
                         hipStream_t s) {
     caelo_frame_set fs = {};
     fs.n = 1;
     fs.f[0].pc = pc; fs.f[0].n = n; fs.f[0].ring = ring; fs.f[0].counter = counter; fs.f[0].winner = winner_ws; fs.f[0].status = status;
-    return ring_project_set(fs, s);
+    return ring_project_set(c, fs, s);
 }
 
-int ring_project_set(const caelo_frame_set &fs, hipStream_t s) {
+int ring_project_set(caelo_ctx *c, const caelo_frame_set &fs, hipStream_t s) {
     const int npix = CAELO_RING_H * CAELO_RING_W;
     const int64_t n = set_max_points(fs);
-    ProjConst k;
-    k.pi = 3.14159265358979323846;
-    const double d2r = k.pi / 180.0;                        // SphericalRing.py:28
-    k.az_res = 0.20 * d2r;                                  // :35,:48
-    const double vdown = -24.8 * d2r, vup = 2.0 * d2r;      // :49-50
-    k.v_res = (vup - vdown) / (64 - 1);                     // :51
-    k.v_off = -vdown / k.v_res;                             // :52
+    const ProjConst k = proj_const(c->proj_edge);
     k_project_points<<<dim3((unsigned)((n + 255) / 256), 1, fs.n), 256, 0, s>>>(fs, k);
     CAELO_LAUNCH_CHECK();
     k_ring_fill<<<dim3((npix + 255) / 256, 1, fs.n), 256, 0, s>>>(fs);
@@ -235,7 +300,7 @@ CAELO_API int caelo_project(caelo_ctx *c, const float *pc, int64_t n, float *rin
     cl.item[cl.n++] = {counter, npix * sizeof(int32_t), 0u};
     int rc = caelo_clear_many(cl, s);
     if (rc) return rc;
-    return ring_project_launch(pc, n, ring, counter, winner_ws, status, s);
+    return ring_project_launch(c, pc, n, ring, counter, winner_ws, status, s);
 }
 
 // ------------------------------------------------------------------------------------------------

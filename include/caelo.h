@@ -509,6 +509,7 @@ int64_t caelo_extract_ws_frame_offset(void);
  * 0..63; bit b of word y is set iff some pixel of columns 32 b .. 32 b + 31 of row y holds a point whose norm over the first
  * dist_channels ring channels is >= 10 (the range gate of SphericalRing.py:197-198).  Read-only; meant for tests. */
 int64_t caelo_extract_ws_kp_eligible_offset(void);
+int64_t caelo_extract_ws_ring_offset(void);   /* the fused path's ring image [69][1800][5] f32 (read-only, for tests) */
 int caelo_extract(caelo_ctx *ctx, caelo_voxmap *map, const float *pc, int64_t n, int dist_channels, int mode, float *key_pts,
                   int kp_ld, float *features, int feat_ld, float *valid, int valid_ld, int64_t *key_pixels,
                   int32_t *n_key, uint8_t *flags, int32_t *status, void *ws, void *stream);
@@ -776,6 +777,11 @@ int caelo_pipeline_get_pace(const caelo_pipeline *p);   /* the pacing in effect 
 /* The HIP streams of the stages: out_host[4] = front, encoder, pair, voxel maps.  Stages that share a stream report the same handle;
  * out_host[3] is null when the voxel maps are built on the front stream.  (Tests hold one stage back to check the hand-offs.) */
 int caelo_pipeline_streams(const caelo_pipeline *p, void **out_host);
+/* Read-only, for tests: copies `bytes` bytes at `offset` of the extract workspace of frame slot i of a batch to the device buffer `dst`,
+ * on `stream`.  The workspace is laid out as caelo_extract's (caelo_extract_ws_kp_eligible_offset(), caelo_extract_ws_ring_offset()).
+ * The copy is ordered by `stream` alone: the caller makes `stream` wait for the pipeline's front stage first -- the stream a run
+ * was flushed on (caelo_pipeline_flush) has waited for every stage -- and lets no later batch be issued before the copy is done. */
+int caelo_pipeline_extract_ws_read(const caelo_pipeline *p, int i, int64_t offset, int64_t bytes, void *dst, void *stream);
 /* n host -> device copies on `stream` behind one call (the scans of a batch that live in pinned host memory, the producer side of
  * PoseEstimation.py:214-245): dst[i] <- src[i], bytes[i] each, asynchronous like hipMemcpyAsync; a null dst[i] or src[i] is an error,
  * a zero bytes[i] is skipped.  The pipeline does not take part -- the caller orders the copies against it (an event of its own,
