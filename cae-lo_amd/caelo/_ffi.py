@@ -89,6 +89,11 @@ CERT_DTYPE = _np.dtype([("magic", "i4"), ("n_pairs", "i4"), ("flags", "i4"), ("l
 POSE_DTYPE = _np.dtype([("R", "f4", (9,)), ("T", "f4", (3,)), ("R_ransac", "f4", (9,)), ("T_ransac", "f4", (3,)), ("threshold", "f4"),
                         ("success", "i4"), ("iterations", "i4"), ("n_inliers", "i4"), ("best_trial", "i4"), ("n_pairs", "i4")])
 assert POSE_DTYPE.itemsize == C.sizeof(PoseResult)
+# caelo_adaptive_result (include/caelo.h): the comparison protocol's registrar (csrc/adaptive.hip)
+ADAPTIVE_MAX_TRIALS, ADAPTIVE_DRAWS = 10000, 10001   # include/caelo.h CAELO_ADAPTIVE_MAX_TRIALS / CAELO_ADAPTIVE_DRAWS
+ADAPTIVE_DTYPE = _np.dtype([("R", "f8", (9,)), ("T", "f8", (3,)), ("R_ransac", "f8", (9,)), ("T_ransac", "f8", (3,)), ("n_pairs", "i4"),
+                            ("n_inliers", "i4"), ("trials", "i4"), ("best_trial", "i4"), ("status", "i4"), ("reserved", "i4")])
+assert ADAPTIVE_DTYPE.itemsize == 216
 
 # (name, restype, argtypes) -- must list every symbol include/caelo.h declares
 SIGNATURES = [
@@ -216,6 +221,10 @@ SIGNATURES = [
     ("caelo_register_pairs", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_register_pairs_ws_bytes_dim", c_i64, [c_i64, c_int]),
     ("caelo_register_pairs_desc", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int]),
+    ("caelo_ransac_adaptive", c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_host_ransac_adaptive", c_int, [c_vp, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp]),
+    ("caelo_register_pairs_adaptive_ws_bytes", c_i64, [c_i64, c_int]),
+    ("caelo_register_pairs_adaptive", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int]),
 ]
 
 _lib = None

@@ -516,3 +516,18 @@ def SolveRelativePoses(rows, pairs, seeds, desc=None):
         res.append((np.array(r["R"], dtype=np.float32).reshape(3, 3), np.array(r["T"], dtype=np.float32).reshape(3, 1), bool(r["success"]),
                     idx[q][i1], i1, thr))
     return res
+
+
+def RansacFitRt(x1, x2, t, draws=None, seed=0):
+    """External/ransacfitRt.m, the registrar of the published comparison (Scripts/GenerateTrajactory.m:213), on the device: x1, x2
+    [3, n] (the script's layout) or [n, 3], n <= 1024, with x1 ~ R x2 + T; ``t`` the inlier distance.  3-point samples, the quaternion
+    fit, the adaptive trial count (p = 0.99, at least 100 trials, the identity after 10 000) and the refit on the inliers
+    (Engine.ransac_adaptive).  ``draws`` [10001, 3] uniform doubles, three per trial; default: RandomState(seed)'s
+    (caelo_host_random_sample) -- the sample rule is this project's, MATLAB's stream cannot be reproduced.
+    -> (Rt [3, 4] f64, inliers (0-based indices), trialcount).  Fewer than three pairs: Rt is empty ([0, 4]), as in the script."""
+    from . import adaptive
+    e = default_engine()
+    rec, mask = e.ransac_adaptive(x1, x2, adaptive.draw_table(seed) if draws is None else draws, threshold=float(t))
+    if int(rec["status"]) == 2:
+        return np.zeros((0, 4)), np.zeros(0, dtype=np.int64), 0
+    return np.c_[rec["R"].reshape(3, 3), rec["T"]], np.flatnonzero(mask), int(rec["trials"])

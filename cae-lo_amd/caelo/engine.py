@@ -1885,6 +1885,67 @@ class Engine:
             evals, status = np.zeros(P, np.int32), np.zeros(P, np.int32)
         return RegisteredPairs(results, masks, idx, evals, status)
 
+    # ---- the comparison protocol's registrar (csrc/adaptive.hip, caelo/adaptive.py) ----------------------
+    def _adaptive_draws(self, draws):
+        if isinstance(draws, torch.Tensor):
+            assert draws.dtype == torch.float64 and tuple(draws.shape) == (_ffi.ADAPTIVE_DRAWS, 3) and draws.is_contiguous() and draws.device == self.device
+            return draws
+        from . import adaptive
+        return torch.from_numpy(adaptive.check_draws(draws)).to(self.device)
+
+    def ransac_adaptive(self, x1, x2, draws, threshold=1.0):
+        """ransacfitRt.m on the device (caelo_ransac_adaptive): x1, x2 [n, 3] float64 with x1 ~ R x2 + T (host arrays, or device
+        tensors), n <= 1024; ``draws`` [10001, 3] f64 (caelo.adaptive.draw_table; host array or device tensor).  One workgroup.
+        -> (record (_ffi.ADAPTIVE_DTYPE: R, T the refit, R_ransac, T_ransac the best trial, n_pairs, n_inliers, trials, best_trial,
+        status 0 ok / 1 trial limit / 2 fewer than 3 pairs), mask [n] u8 (host)).  Synchronises."""
+        if isinstance(x1, torch.Tensor):
+            a, b = x1, x2
+            assert a.dtype == b.dtype == torch.float64 and a.shape == b.shape and a.dim() == 2 and a.shape[1] == 3 and a.is_contiguous() and b.is_contiguous()
+            if a.shape[0] > MAX_K:
+                raise ValueError("at most %d pairs, got %d" % (MAX_K, a.shape[0]))
+        else:
+            from . import adaptive
+            a, b = (torch.from_numpy(t).to(self.device) for t in adaptive.check_pairs(x1, x2))
+        n = int(a.shape[0])
+        res = self.zeros((_ffi.ADAPTIVE_DTYPE.itemsize,), torch.uint8)
+        mask = self.zeros((max(n, 1),), torch.uint8)
+        _ffi.check(self.lib.caelo_ransac_adaptive(self.ctx, _ptr(a), _ptr(b), n, _ptr(self._adaptive_draws(draws)), float(threshold),
+                                                  _ptr(res), _ptr(mask), None, self.stream))
+        return np.frombuffer(res.cpu().numpy().tobytes(), dtype=_ffi.ADAPTIVE_DTYPE)[0], mask.cpu().numpy()[:n]
+
+    def register_pairs_adaptive(self, rows, n_key, table, draws, threshold=1.0, desc=None):
+        """The comparison protocol's registrar over a table of frame pairs of resident rows, ONE call
+        (caelo_register_pairs_adaptive): ``rows`` / ``n_key`` / ``desc`` as for ``register_pairs``, ``table`` [P,2] (frame a, frame b),
+        ``draws`` [10001, 3] f64 shared by every pair (caelo.adaptive.draw_table).  The match direction is the script's: for each key
+        point of frame a the nearest descriptor of frame b -- ``pair_idx`` [P,1024] indexes frame B and ``masks`` [P,1024] is over
+        frame A's points, the other way round from ``register_pairs``; the pose maps frame b into frame a all the same.
+        -> RegisteredPairs(results [P] (_ffi.ADAPTIVE_DTYPE), masks [P,1024] u8 (host), pair_idx (device), evals = the trial counts,
+        status [P]) in the table's order.  The same refusals before any launch as ``register_pairs``.  Synchronises."""
+        assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
+        if desc is not None:
+            if desc.dtype != torch.float32 or desc.dim() != 3 or tuple(desc.shape[:2]) != (rows.shape[0], MAX_K) or not 1 <= desc.shape[2] <= 256:
+                raise ValueError("desc [F=%d,%d,D<=256] f32, got %s %s" % (rows.shape[0], MAX_K, tuple(desc.shape), desc.dtype))
+            if desc.stride(2) != 1 or desc.stride(0) != MAX_K * desc.stride(1) or desc.stride(1) < desc.shape[2]:
+                raise ValueError("desc must be contiguous or a column slice of a contiguous [F,%d,ld] block, got strides %s" % (MAX_K, tuple(desc.stride())))
+        assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
+        pr = np.ascontiguousarray(table.cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.int64).reshape(-1, 2)
+        if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
+            raise _ffi.CaeloError("register_pairs_adaptive: a frame index does not fit 32 bits")
+        P = int(pr.shape[0])
+        dim = 60 if desc is None else int(desc.shape[2])
+        idx = self.zeros((P, MAX_K), torch.int64)
+        if P == 0:   # (an empty tensor has no address to hand to the library)
+            return RegisteredPairs(np.zeros(0, dtype=_ffi.ADAPTIVE_DTYPE), np.zeros((0, MAX_K), dtype=np.uint8), idx, np.zeros(0, np.int32), np.zeros(0, np.int32))
+        pr_d = torch.from_numpy(pr.astype(np.int32)).to(self.device)
+        res_d = self.zeros((P, _ffi.ADAPTIVE_DTYPE.itemsize), torch.uint8)
+        mask_d = self.zeros((P, MAX_K), torch.uint8)
+        ws = self._ws("register_pairs_adaptive_d%d" % dim, int(self.lib.caelo_register_pairs_adaptive_ws_bytes(P, dim)))
+        _ffi.check(self.lib.caelo_register_pairs_adaptive(self.ctx, _ptr(rows), rows.shape[0], _ptr(n_key), _ptr(pr_d), P, _ptr(self._adaptive_draws(draws)),
+                                                          float(threshold), _ptr(idx), _ptr(res_d), _ptr(mask_d), _ptr(ws), self.stream,
+                                                          _ptr(desc), int(desc.stride(1)) if desc is not None else 64, dim))
+        results = np.frombuffer(res_d.cpu().numpy().tobytes(), dtype=_ffi.ADAPTIVE_DTYPE).copy()
+        return RegisteredPairs(results, mask_d.cpu().numpy(), idx, results["trials"].astype(np.int32), results["status"].astype(np.int32))
+
     def checked(self, ff, pc, dist_channels=5):
         """Synchronising status check of an extract() result: raises what the reference would raise."""
         raise_status(int(ff.status[0].item()))

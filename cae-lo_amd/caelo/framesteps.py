@@ -82,10 +82,14 @@ class StepRegistrar:
     rank before it, which registers the pairs that straddle the boundary (``boundary``: frame 0 its own); ``export`` / ``merge``
     bring every step's results together in pair order."""
 
-    def __init__(self, eng, steps, seed_base, certify, lo=0):
+    def __init__(self, eng, steps, seed_base, certify, lo=0, registrar=None):
+        """``registrar``: None = Match.py's RANSAC4RT (Engine.register_pairs; step 1 is the pipeline's own), or (draws, threshold) =
+        the comparison protocol's ransacfitRt.m (Engine.register_pairs_adaptive) -- then step 1 is registered here as well, from the
+        same resident rows, and one more frame is carried for it."""
         self.eng, self.seed_base, self.certify, self.lo = eng, int(seed_base), certify, int(lo)
-        self.steps = [s for s in steps if s != 1]
-        self.m = carry_frames(steps)
+        self.registrar = registrar
+        self.steps = [s for s in steps if s != 1 or registrar is not None]
+        self.m = carry_frames(steps) if registrar is None else max(1, carry_frames(steps))
         self.rows = self.n_key = None     # the carried frames [base, base + len)
         self.base = lo
         self.head = []                    # rows of the rank's first m frames (chunk by chunk)
@@ -98,7 +102,10 @@ class StepRegistrar:
             return
         table = [(a - base, b - base) for _, _, a, b in todo]
         assert all(0 <= i < rows.shape[0] for ab in table for i in ab), "a scheduled pair lies outside the resident window"
-        out = self.eng.register_pairs(rows.contiguous(), nk.contiguous(), table, [self.seed_base + kk for _, kk, _, _ in todo], certify=self.certify)
+        if self.registrar is not None:
+            out = self.eng.register_pairs_adaptive(rows.contiguous(), nk.contiguous(), table, self.registrar[0], self.registrar[1])
+        else:
+            out = self.eng.register_pairs(rows.contiguous(), nk.contiguous(), table, [self.seed_base + kk for _, kk, _, _ in todo], certify=self.certify)
         for s in self.steps:
             sel = [i for i, t in enumerate(todo) if t[0] == s]
             if sel:
@@ -146,7 +153,8 @@ class StepRegistrar:
     def merge(self, exports):
         """Rank 0: every rank's export() -> this object holds all results."""
         from . import _ffi
-        self.results = {s: [(ks, np.frombuffer(raw, dtype=_ffi.POSE_DTYPE)) for e in exports for ks, raw in e[s]] for s in self.steps}
+        dt = _ffi.POSE_DTYPE if self.registrar is None else _ffi.ADAPTIVE_DTYPE
+        self.results = {s: [(ks, np.frombuffer(raw, dtype=dt)) for e in exports for ks, raw in e[s]] for s in self.steps}
 
     def step_results(self, s):
         """-> (rel [p, 12] f32 (R | T), success [p], n_inliers [p], n_pairs [p], iterations [p]) of step s, in pair order."""
@@ -154,7 +162,10 @@ class StepRegistrar:
 
 
 def pack_results(entries, s):
-    """entries [(pair numbers k, record array (_ffi.POSE_DTYPE))] of step s, in any order -> what StepRegistrar.step_results returns."""
+    """entries [(pair numbers k, record array (_ffi.POSE_DTYPE))] of step s, in any order -> what StepRegistrar.step_results returns.
+    Records of the comparison protocol's registrar (_ffi.ADAPTIVE_DTYPE): the relative motions are chained by the script's rule (a
+    pair that is not solved repeats the motion of the pair before it, caelo.adaptive.chain_relative) and stay float64; ``iterations``
+    are the trial counts."""
     from . import _ffi
     ks = np.concatenate([k_ for k_, _ in entries]) if entries else np.zeros(0, dtype=np.int64)
     r = np.concatenate([r_ for _, r_ in entries]) if entries else np.zeros(0, dtype=_ffi.POSE_DTYPE)
@@ -162,5 +173,9 @@ def pack_results(entries, s):
     assert np.array_equal(ks[order], np.arange(len(ks))), "step %d: pairs %s registered" % (s, ks[order].tolist())
     r = r[order]
     p = len(r)
+    if r.dtype == _ffi.ADAPTIVE_DTYPE:
+        from . import adaptive
+        rel, solved = adaptive.fit_rows(r)
+        return adaptive.chain_relative(rel, solved), solved, r["n_inliers"].astype(np.int32), r["n_pairs"].astype(np.int32), r["trials"].astype(np.int32)
     rel = np.concatenate([r["R"].reshape(p, 9), r["T"].reshape(p, 3)], axis=1).astype(np.float32)
     return rel, r["success"] != 0, r["n_inliers"].astype(np.int32), r["n_pairs"].astype(np.int32), r["iterations"].astype(np.int32)

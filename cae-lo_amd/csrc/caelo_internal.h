@@ -241,6 +241,19 @@ struct caelo_pair_table {
 };
 int match_table(const caelo_pair_table &pt, hipStream_t s);
 int ransac_table(const caelo_pair_table &pt, hipStream_t s);
+// The comparison protocol's registrar over a whole pair table in ONE launch, a workgroup per entry (adaptive.hip): entry q takes
+// p0[i] = xyz of point i of frame pairs[q][0], p1[i] = xyz of point pair_idx[q][i] of frame pairs[q][1], i < n_key[pairs[q][0]].
+struct caelo_adaptive_table {
+    const float *rows;
+    const int32_t *n_key, *pairs;
+    const int64_t *pair_idx;          // [n_pairs][CAELO_MAX_KEYPTS], into frame pairs[q][1]
+    const double *draws;              // [CAELO_ADAPTIVE_DRAWS][3], shared by every entry
+    double threshold;
+    caelo_adaptive_result *result;    // [n_pairs]
+    uint8_t *mask;                    // [n_pairs][CAELO_MAX_KEYPTS]
+    int64_t n_pairs;
+};
+int adaptive_table(const caelo_adaptive_table &at, hipStream_t s);
 #ifdef __HIPCC__
 __device__ __forceinline__ const caelo_pair_dev &pair_of(const caelo_pair_set &ps, unsigned z) { return ps.p[z]; }
 __device__ __forceinline__ caelo_pair_dev pair_of(const caelo_pair_table &pt, unsigned z) {

@@ -14,6 +14,8 @@
 // three host vectors; nothing goes up -- a slice's order is part of its launches' arguments.
 // caelo_register_pairs_desc: the same walk with the NN match on descriptors of the caller's ([n_frames][1024][ld_desc], up to 256
 // wide) instead of the rows' columns 0:60; xyz and the counts still come from the rows.
+// caelo_register_pairs_adaptive: the same checks and the same single wait, the match with the two frames exchanged, and the
+// comparison protocol's registrar (adaptive.hip) over the whole table in one launch.
 #include "caelo_internal.h"
 
 #include <algorithm>
@@ -37,25 +39,13 @@ CAELO_API int64_t caelo_register_pairs_ws_bytes_dim(int64_t n_pairs, int dim) {
     return CAELO_FB_MAX * (rp_match_stride(dim) + rp_ransac_stride());
 }
 
-// desc == nullptr: the rows' own descriptors through match_table.  Otherwise the slice's pairs as a caelo_pair_set the host fills
-// from the table it has read back anyway (pair_of's other argument: the set travels in the kernel arguments like a slice's order)
-// and match_set, i.e. whichever match kernels `dim` selects; RANSAC never reads a descriptor and stays ransac_table.
-static int register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
-                          const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
-                          caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim) {
-    CAELO_REQUIRE(pairs, "null pair table");
-    CAELO_REQUIRE(n_frames >= 1 && n_frames < (1LL << 31), "n_frames must lie in [1, 2^31)");
-    CAELO_REQUIRE(n_pairs >= 0 && n_pairs < (1LL << 31), "n_pairs must lie in [0, 2^31)");
-    CAELO_REQUIRE(c && rows && n_key && rand && pair_idx_out && ws, "null argument");
-    CAELO_REQUIRE((results_out && masks_out) || (certs_out && !results_out && !masks_out),
-                  "results_out and masks_out go together; without them certs_out must take the pairs' certificates");
-    CAELO_REQUIRE((((uintptr_t)rows) & 15u) == 0 && (((uintptr_t)certs_out) & 15u) == 0 && (((uintptr_t)masks_out) & 3u) == 0 &&
-                      (((uintptr_t)ws) & 15u) == 0,
-                  "rows, certs_out and ws must be 16-byte aligned, masks_out 4-byte aligned");
-    if (n_pairs == 0) return CAELO_OK;
-    hipStream_t s = caelo_stream(stream);
-    // ---- the table and the counts as the device holds them once `stream` has reached this call: read back, checked, ordered
-    std::vector<int32_t> tab((size_t)n_pairs * 2), nk((size_t)n_frames), order((size_t)n_pairs);
+// The table and the counts as the device holds them once `s` has reached the call: read back (ONE wait), checked, and the entries
+// ordered (stably) by (frame 0, frame 1).  -> CAELO_OK, or the refusal with the error text set
+static int read_table(int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs, hipStream_t s, std::vector<int32_t> &tab,
+                      std::vector<int32_t> &order) {
+    std::vector<int32_t> nk((size_t)n_frames);
+    tab.resize((size_t)n_pairs * 2);
+    order.resize((size_t)n_pairs);
     CAELO_HIP(hipMemcpyAsync(tab.data(), pairs, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CAELO_HIP(hipMemcpyAsync(nk.data(), n_key, nk.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s));
     CAELO_HIP(hipStreamSynchronize(s));
@@ -76,6 +66,28 @@ static int register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, con
     std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
         return tab[2 * (size_t)a] != tab[2 * (size_t)b] ? tab[2 * (size_t)a] < tab[2 * (size_t)b] : tab[2 * (size_t)a + 1] < tab[2 * (size_t)b + 1];
     });
+    return CAELO_OK;
+}
+
+// desc == nullptr: the rows' own descriptors through match_table.  Otherwise the slice's pairs as a caelo_pair_set the host fills
+// from the table it has read back anyway (pair_of's other argument: the set travels in the kernel arguments like a slice's order)
+// and match_set, i.e. whichever match kernels `dim` selects; RANSAC never reads a descriptor and stays ransac_table.
+static int register_pairs(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                          const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
+                          caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim) {
+    CAELO_REQUIRE(pairs, "null pair table");
+    CAELO_REQUIRE(n_frames >= 1 && n_frames < (1LL << 31), "n_frames must lie in [1, 2^31)");
+    CAELO_REQUIRE(n_pairs >= 0 && n_pairs < (1LL << 31), "n_pairs must lie in [0, 2^31)");
+    CAELO_REQUIRE(c && rows && n_key && rand && pair_idx_out && ws, "null argument");
+    CAELO_REQUIRE((results_out && masks_out) || (certs_out && !results_out && !masks_out),
+                  "results_out and masks_out go together; without them certs_out must take the pairs' certificates");
+    CAELO_REQUIRE((((uintptr_t)rows) & 15u) == 0 && (((uintptr_t)certs_out) & 15u) == 0 && (((uintptr_t)masks_out) & 3u) == 0 &&
+                      (((uintptr_t)ws) & 15u) == 0,
+                  "rows, certs_out and ws must be 16-byte aligned, masks_out 4-byte aligned");
+    if (n_pairs == 0) return CAELO_OK;
+    hipStream_t s = caelo_stream(stream);
+    std::vector<int32_t> tab, order;
+    if (const int rc = read_table(n_frames, n_key, pairs, n_pairs, s, tab, order)) return rc;
     caelo_pair_table pt = {};
     pt.rows = rows; pt.n_key = n_key; pt.pairs = pairs;
     pt.pair_idx = pair_idx_out; pt.rand = rand; pt.result = results_out; pt.mask = masks_out; pt.cert = certs_out;
@@ -121,4 +133,49 @@ CAELO_API int caelo_register_pairs_desc(caelo_ctx *c, const float *rows, int64_t
     CAELO_REQUIRE(desc, "null descriptors");
     CAELO_REQUIRE(dim >= 1 && dim <= 256 && ld_desc >= dim && ld_desc < (1LL << 31), "dim must lie in [1, 256] and ld_desc in [dim, 2^31)");
     return register_pairs(c, rows, n_frames, n_key, pairs, n_pairs, rand, pair_idx_out, results_out, masks_out, certs_out, ws, stream, desc, ld_desc, dim);
+}
+
+// ---- the comparison protocol's registrar over a table (adaptive.hip; include/caelo.h) ----------------------------------------------
+// The match is match_set's with the two frames EXCHANGED (for each point of frame a the nearest descriptor of frame b), slice after
+// slice on CAELO_FB_MAX workspace slots; then one launch registers every entry.  Nothing but the match needs a workspace.
+CAELO_API int64_t caelo_register_pairs_adaptive_ws_bytes(int64_t n_pairs, int dim) {
+    if (n_pairs < 0) return 0;
+    return CAELO_FB_MAX * rp_match_stride(dim);
+}
+
+CAELO_API int caelo_register_pairs_adaptive(caelo_ctx *c, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs,
+                                            int64_t n_pairs, const double *draws, double threshold, int64_t *pair_idx_out,
+                                            caelo_adaptive_result *results_out, uint8_t *masks_out, void *ws, void *stream, const float *desc,
+                                            int64_t ld_desc, int dim) {
+    CAELO_REQUIRE(pairs, "null pair table");
+    CAELO_REQUIRE(n_frames >= 1 && n_frames < (1LL << 31), "n_frames must lie in [1, 2^31)");
+    CAELO_REQUIRE(n_pairs >= 0 && n_pairs < (1LL << 31), "n_pairs must lie in [0, 2^31)");
+    CAELO_REQUIRE(c && rows && n_key && draws && pair_idx_out && results_out && masks_out && ws, "null argument");
+    CAELO_REQUIRE((((uintptr_t)rows) & 15u) == 0 && (((uintptr_t)ws) & 15u) == 0 && (((uintptr_t)results_out) & 7u) == 0 && (((uintptr_t)draws) & 7u) == 0,
+                  "rows and ws must be 16-byte aligned, results_out and draws 8-byte aligned");
+    if (!desc) { desc = rows; ld_desc = 64; dim = 60; }
+    CAELO_REQUIRE(dim >= 1 && dim <= 256 && ld_desc >= dim && ld_desc < (1LL << 31), "dim must lie in [1, 256] and ld_desc in [dim, 2^31)");
+    if (n_pairs == 0) return CAELO_OK;
+    hipStream_t s = caelo_stream(stream);
+    std::vector<int32_t> tab, order;
+    if (const int rc = read_table(n_frames, n_key, pairs, n_pairs, s, tab, order)) return rc;
+    const int64_t stride = rp_match_stride(dim);
+    for (int64_t q0 = 0; q0 < n_pairs; q0 += CAELO_FB_MAX) {
+        caelo_pair_set ps = {};
+        ps.n = (int32_t)std::min<int64_t>(CAELO_FB_MAX, n_pairs - q0);
+        ps.faults = c->faults;
+        for (int z = 0; z < ps.n; ++z) {
+            const int64_t q = order[(size_t)(q0 + z)], a = tab[(size_t)(2 * q)], b = tab[(size_t)(2 * q + 1)];
+            caelo_pair_dev &d = ps.p[z];
+            d.f0 = desc + b * (CAELO_MAX_KEYPTS * ld_desc); d.f1 = desc + a * (CAELO_MAX_KEYPTS * ld_desc);   // exchanged: argmin over frame b
+            d.n0 = n_key + b; d.n1 = n_key + a;
+            d.pair_idx = pair_idx_out + q * CAELO_MAX_KEYPTS;
+            d.ws_match = (char *)ws + (int64_t)z * stride;
+        }
+        if (const int rc = match_set(ps, (int)ld_desc, CAELO_MAX_KEYPTS, (int)ld_desc, CAELO_MAX_KEYPTS, dim, s)) return rc;
+    }
+    caelo_adaptive_table at = {};
+    at.rows = rows; at.n_key = n_key; at.pairs = pairs; at.pair_idx = pair_idx_out; at.draws = draws; at.threshold = threshold;
+    at.result = results_out; at.mask = masks_out; at.n_pairs = n_pairs;
+    return adaptive_table(at, s);
 }

@@ -7,6 +7,7 @@
     python run_sequence.py --scans <raw KITTI seq>/velodyne --calib-angle 0.22 --out poses_/00.txt   # CorrectPC on the fly
     python run_sequence.py --scans <seq>/velodyne --frame-steps 1,5,10 --out poses_/00.txt   # + poses_/5_00.txt, poses_/10_00.txt, one extraction pass
     python run_sequence.py --desc-dir <usip desc>/00 --desc-dim 128 --keypts-source usip --keypts-dir <usip keypts>/00 --out poses_/00.txt
+    python run_sequence.py --desc-dir <usip desc>/00 ... --registrar comparison --matchability m/00.mat   # the published comparison's registrar
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 run_sequence.py --synthetic 800 ...
 
 Frames are sharded contiguously over the ranks (one process per GPU); every rank runs its frames through the
@@ -331,13 +332,15 @@ def run_local_files(eng, files, lo, hi, seed_base, chunk, dist_channels, batch_f
     return out
 
 
-def run_desc(eng, src, n, seed_base, chunk, steps, certify):
+def run_desc(eng, src, n, seed_base, chunk, steps, certify, registrar=None, calib_angle=None):
     """--desc-dir: the pair stage alone on descriptors of another method (caelo.keysources.DescSource; no scan is read, nothing is
     extracted).  Frames [0, n) chunk by chunk: a chunk's key points and descriptors become rows [k,1024,64] (xyz 60:63 | valid 63,
     columns 0:60 zero and unread) and desc [k,1024,D]; ONE Engine.register_pairs(..., desc=) call registers the consecutive pairs
     (i - 1, i) whose frame i the chunk holds and the pairs of every other step whose frame 1 it holds (framesteps.chunk_pairs), the
     last max(steps) frames being carried from chunk to chunk.  Pair k of a step draws RandomState(seed_base + k), as in every other
-    run.  -> {step: framesteps.pack_results(...)}."""
+    run.  ``registrar`` = (draws, threshold): the comparison protocol's registrar instead (Engine.register_pairs_adaptive; every pair
+    consumes the same draws); ``calib_angle`` then corrects the key points of sources other than the auto-encoder's on the device
+    (GenerateTrajactory.m:186-190).  -> {step: framesteps.pack_results(...)}."""
     others = [s for s in steps if s != 1]
     m = max(1, framesteps.carry_frames(steps))
     results = {s: [] for s in [1] + others}
@@ -354,14 +357,20 @@ def run_desc(eng, src, n, seed_base, chunk, steps, certify):
                 raise ValueError("frame %d has no key points" % (c0 + j))
             rows[j, :k, 60:63], rows[j, :k, 63], desc[j, :k], nk[j] = pts, 1.0, d, k
         rows, desc, nk = (torch.from_numpy(a).to(eng.device) for a in (rows, desc, nk))
+        if calib_angle is not None and src.keypts_source != "ae":   # (a padding row's origin would turn into NaN: it stays zero)
+            moved = eng.correct_pc(rows[:, :, 60:63].reshape(-1, 3).contiguous(), calib_angle).view(-1, 1024, 3)
+            rows[:, :, 60:63] = torch.where(rows[:, :, 63:64] > 0, moved, torch.zeros_like(moved))
         if carried is not None:
             rows, desc, nk = torch.cat([carried[0], rows]), torch.cat([carried[1], desc]), torch.cat([carried[2], nk])
         else:
             base = c0
         todo = [(1, i - 1, i - 1, i) for i in range(max(c0, 1), c1)] + [(s, k, a, b) for s in others for k, a, b in framesteps.chunk_pairs(c0, c1, s, 0)]
         if todo:
-            out = eng.register_pairs(rows, nk, [(a - base, b - base) for _, _, a, b in todo], [seed_base + k for _, k, _, _ in todo],
-                                     certify=certify, desc=desc)
+            table = [(a - base, b - base) for _, _, a, b in todo]
+            if registrar is not None:
+                out = eng.register_pairs_adaptive(rows, nk, table, registrar[0], registrar[1], desc=desc)
+            else:
+                out = eng.register_pairs(rows, nk, table, [seed_base + k for _, k, _, _ in todo], certify=certify, desc=desc)
             for s in results:
                 sel = [i for i, t in enumerate(todo) if t[0] == s]
                 if sel:
@@ -372,13 +381,24 @@ def run_desc(eng, src, n, seed_base, chunk, steps, certify):
     return {s: framesteps.pack_results(results[s], s) for s in results}
 
 
+def _registrar(args):
+    """--registrar: None for Match.py's RANSAC4RT, (draws [10001,3], threshold) for the comparison protocol's ransacfitRt.m."""
+    if args.registrar != "comparison":
+        return None
+    from caelo import adaptive
+    return adaptive.draw_table(args.draw_seed), float(args.inlier_threshold)
+
+
 def main_desc(args, ap, steps):
     """The --desc-dir run (one GPU): the files every other run writes, under the same names."""
     from caelo import keysources
     if args.gpus > 1:
         ap.error("--desc-dir runs on one GPU (--gpus %d): a pair table of a whole sequence takes seconds; sharding it is not implemented" % args.gpus)
-    if args.scans or args.synthetic or args.save_artifacts or args.calib_angle is not None:
-        ap.error("--desc-dir reads no scans: --scans, --synthetic, --save-artifacts and --calib-angle do not go with it")
+    if args.scans or args.synthetic or args.save_artifacts or (args.calib_angle is not None and args.registrar != "comparison"):
+        ap.error("--desc-dir reads no scans: --scans, --synthetic, --save-artifacts and --calib-angle do not go with it "
+                 "(--registrar comparison takes --calib-angle: it corrects the key points of --keypts-source 3dfeatnet|usip)")
+    if args.calib_angle is not None and not np.isfinite(args.calib_angle):
+        ap.error("--calib-angle must be a finite number of degrees")
     src = keysources.DescSource(args.desc_dir, args.desc_dim, args.keypts_source, args.keypts_dir, args.features_from)
     n = src.n_frames()
     if n < 2:
@@ -390,7 +410,7 @@ def main_desc(args, ap, steps):
     eng = Engine(device=0)
     Tr = stageio.read_calib_tr(args.calib) if args.calib else None
     t0 = time.time()
-    res = run_desc(eng, src, n, args.seed_base, args.chunk, steps, not args.no_certify)
+    res = run_desc(eng, src, n, args.seed_base, args.chunk, steps, not args.no_certify, _registrar(args), args.calib_angle)
     dt = time.time() - t0
     for s_, (rel, ok, nin, npairs, its) in res.items():
         assert len(rel) == len(framesteps.step_pairs(n, s_))
@@ -459,6 +479,17 @@ def main():
                          "--frame-step s reads the multiples only.)  --matchability M gets the same prefix per step.  With --gpus > 1 a rank "
                          "registers the step pairs whose frame 0 it owns: its halo is the next rank's first max(S) frames' rows (one more "
                          "all-gather), and every rank needs at least max(S) frames")
+    ap.add_argument("--registrar", default="match", choices=("match", "comparison"),
+                    help="how a pair is registered.  match (default): Match.py's RANSAC4RT -- for each key point of frame 1 the nearest descriptor "
+                         "of frame 0, 4-point samples, 500 trials per threshold level.  comparison: the protocol behind the reference's published "
+                         "table (Scripts/GenerateTrajactory.m -> External/ransacfitRt.m): for each key point of frame 0 the nearest descriptor of "
+                         "frame 1, 3-point samples, a quaternion fit, ONE inlier threshold, an adaptive trial count (p = 0.99, at least 100, "
+                         "the identity after 10 000) and a refit on the inliers; a pair that fails repeats the motion of the pair before it; "
+                         "--matchability then holds n_inliers / n_pairs and the trial counts of that protocol.  Every pair consumes the same "
+                         "draws (--draw-seed).  On the pipeline path the pairs of every step, step 1 included, are registered from the "
+                         "resident rows (Engine.register_pairs_adaptive).  One GPU; not with --save-artifacts")
+    ap.add_argument("--inlier-threshold", type=float, default=1.0, metavar="M", help="--registrar comparison: the inlier distance in metres (the script's 1.0)")
+    ap.add_argument("--draw-seed", type=int, default=0, help="--registrar comparison: RandomState(seed) gives the 10 001 x 3 uniform doubles of the trials")
     ap.add_argument("--encoder-h5", metavar="PATH", help="the patch encoder's Keras .h5 instead of the shipped EncoderModel4VoxelPatch.h5: a bare "
                     "encoder or a full autoencoder (its encoder half is taken), tanh or relu hidden layers, tanh or linear code -- "
                     "e.g. what the reference's AE4VoxelPatch.py trains.  Every rank loads it")
@@ -476,6 +507,14 @@ def main():
                 ap.error("%s %s: %s" % (opt, path, e))
             if got != kind:
                 ap.error("%s %s holds the %s network" % (opt, path, "response" if got == "respond" else "encoder"))
+    if args.registrar == "comparison":
+        if args.gpus > 1 or args.save_artifacts:
+            ap.error("--registrar comparison runs on one GPU and writes no Features / InliersIdx artefacts (--gpus %d%s)"
+                     % (args.gpus, ", --save-artifacts" if args.save_artifacts else ""))
+        if not (args.inlier_threshold > 0.0 and np.isfinite(args.inlier_threshold)):
+            ap.error("--inlier-threshold must be a positive number of metres")
+        if not 0 <= args.draw_seed < 2 ** 32:
+            ap.error("--draw-seed %d: RandomState takes seeds in [0, 2^32)" % args.draw_seed)
     if args.desc_dir or args.desc_dim is not None:
         if not args.desc_dir:
             ap.error("--desc-dim goes with --desc-dir")
@@ -568,7 +607,9 @@ def main():
     lo, hi = cdist.shard_frames(n, rank, world)
     t0 = time.time()
 
-    stepper = framesteps.StepRegistrar(eng, steps, args.seed_base, not args.no_certify, lo) if any(s_ != 1 for s_ in steps) else None
+    registrar = _registrar(args)   # (comparison: step 1 is registered from the resident rows too, the pipeline's own pair results are not used)
+    stepper = (framesteps.StepRegistrar(eng, steps, args.seed_base, not args.no_certify, lo, registrar=registrar)
+               if any(s_ != 1 for s_ in steps) or registrar is not None else None)
 
     def keep(c0, batch):
         if stepper is not None:   # (after the host redo of tied frames: the rows are final)
@@ -633,12 +674,16 @@ def main():
     torch.cuda.synchronize()
     dt = time.time() - t0
     if rank == 0:
+        if registrar is not None:
+            rel, ok, nin, np_1, it_1 = stepper.step_results(1)
+            thr = np.full(len(rel), args.inlier_threshold, np.float32)
+            records = [(it_1, np_1)] if records is not None else None
         poses = stageio.chain_poses(rel, Tr)
         stageio.write_poses(args.out, poses)
         if records is not None:
             from caelo import evaluate as ev
             ev.save_matchability(args.matchability, nin, np.concatenate([b for _, b in records]), np.concatenate([a for a, _ in records]))
-        for s_ in (stepper.steps if stepper is not None else []):
+        for s_ in ([s_ for s_ in stepper.steps if s_ != 1] if stepper is not None else []):
             rel_s, ok_s, nin_s, np_s, it_s = stepper.step_results(s_)
             assert len(rel_s) == len(framesteps.step_pairs(n, s_)), "step %d: %d pairs registered, %d scheduled" % (s_, len(rel_s), len(framesteps.step_pairs(n, s_)))
             stageio.write_poses(framesteps.step_path(args.out, s_), framesteps.expand_rows(stageio.chain_poses(rel_s, Tr), n, s_))

@@ -874,6 +874,50 @@ int caelo_register_pairs_desc(caelo_ctx *ctx, const float *rows, int64_t n_frame
                               const double *rand, int64_t *pair_idx_out, caelo_pose_result *results_out, uint8_t *masks_out,
                               caelo_ransac_cert *certs_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim);
 
+/* ---- the comparison protocol's registrar (additive; the ABI version stays 6) ---------------------------------------------------------
+ * The reference's published table was written by Scripts/GenerateTrajactory.m, which registers with External/ransacfitRt.m and not with
+ * Match.py: 3-point samples, a quaternion least-squares fit (estimateRigidTransform.m + quat2rot.m), ONE inlier threshold (1.0 m
+ * there), an adaptive trial count (ransac.m: p = 0.99, at least 100 trials, the identity after 10 000), `>=` when a new best is
+ * recorded (among equal counts the LATER trial wins) and a least-squares refit on the best trial's inliers.  float64 throughout.
+ * Pairs: p0[i] ~ R p1[i] + T, i < n <= 1024.  Trial t samples three DISTINCT pairs from draws[t][0:3] (uniform doubles in [0, 1);
+ * draws [CAELO_ADAPTIVE_DRAWS][3] f64; this sample rule is the project's own, MATLAB's randsample stream cannot be reproduced):
+ *   i0 = min(floor(u0 n), n - 1);  j1 = min(floor(u1 (n - 1)), n - 2), i1 = j1 + (j1 >= i0);
+ *   j2 = min(floor(u2 (n - 2)), n - 3), i2 = j2 + (j2 >= min(i0, i1)), one more if that is >= max(i0, i1).
+ * status 0: R, T the refit, R_ransac, T_ransac the best trial, best_trial its index, trials the script's trialcount; with fewer than 3
+ *   inliers R, T are the identity and n_inliers 0 (ransacfitRt.m:43-50).  n == 3: the direct fit, all three inliers, 0 trials,
+ *   best_trial -1.
+ * status 1: the walk ran into the limit: the identity, no inliers, trials = 10 000, best_trial -1.
+ * status 2: n < 3: the identity, no inliers, 0 trials.
+ * caelo_ransac_adaptive: p0, p1 [n][3] f64, draws, result and mask [n] u8 are DEVICE memory; one workgroup; ws is not used (may be
+ *   null).  Nothing is read back, nothing waits.
+ * caelo_host_ransac_adaptive: the same functions compiled for the host on HOST arrays; no device is touched.  The trial fits are the
+ *   kernel's operation for operation; the refit adds its inliers in index order where the kernel adds them as a tree.
+ * caelo_register_pairs_adaptive: caelo_register_pairs_desc's arguments with draws and threshold in place of rand, and no certificates
+ *   (desc null: the rows' columns 0:60).  The match direction is the script's, the OTHER way round from caelo_register_pairs: for each
+ *   key point i of frame a = pairs[q][0] the nearest descriptor of frame b = pairs[q][1] (the float64 argmin, first index on ties:
+ *   caelo_match with the two frames exchanged), so pair_idx_out [n_pairs][1024] indexes frame B, there are n_key[a] pairs, and
+ *   masks_out [n_pairs][1024] is over frame A's points (caelo_register_pairs: pair_idx indexes frame 0, the mask is over frame 1).
+ *   The pose still maps frame b into frame a.  Every pair consumes the same draws (ransac.m resets its stream per call).  The same
+ *   refusals before any launch and the same single wait for `stream` as caelo_register_pairs; the match runs in slices of 8 pairs, then
+ *   ONE launch registers all pairs, a workgroup each.  ws: caelo_register_pairs_adaptive_ws_bytes(n_pairs, dim) bytes, 16-byte aligned. */
+#define CAELO_ADAPTIVE_MAX_TRIALS 10000
+#define CAELO_ADAPTIVE_DRAWS (CAELO_ADAPTIVE_MAX_TRIALS + 1)
+typedef struct {
+    double R[9], T[3];                 /* refit */
+    double R_ransac[9], T_ransac[3];   /* best trial */
+    int32_t n_pairs, n_inliers, trials, best_trial;
+    int32_t status;                    /* 0 ok, 1 trial limit, 2 fewer than 3 pairs */
+    int32_t reserved;
+} caelo_adaptive_result;
+int caelo_ransac_adaptive(caelo_ctx *ctx, const double *p0, const double *p1, int64_t n, const double *draws, double threshold,
+                          caelo_adaptive_result *result, uint8_t *mask, void *ws, void *stream);
+int caelo_host_ransac_adaptive(const double *p0_host, const double *p1_host, int64_t n, const double *draws_host, double threshold,
+                               caelo_adaptive_result *result_host, uint8_t *mask_host);
+int64_t caelo_register_pairs_adaptive_ws_bytes(int64_t n_pairs, int dim);
+int caelo_register_pairs_adaptive(caelo_ctx *ctx, const float *rows, int64_t n_frames, const int32_t *n_key, const int32_t *pairs, int64_t n_pairs,
+                                  const double *draws, double threshold, int64_t *pair_idx_out, caelo_adaptive_result *results_out,
+                                  uint8_t *masks_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim);
+
 #ifdef __cplusplus
 }
 #endif
