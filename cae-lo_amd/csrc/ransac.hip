@@ -173,7 +173,7 @@ __device__ inline void sample4(const float *P0, int l0, const int64_t *pidx, con
 
 // hypothesis from 4 sampled pairs (SolveRT on the sample, Match.py:141-157)
 // The same arithmetic as sample4 followed by rigid_from_H<false>(s.H, s.m0, s.m1, R, T), written out on purpose: through a Sample4
-// the compiler keeps the whole record live and k_ransac_hyp goes from 168 to 208 registers (four_hypotheses says what leaving 168
+// the compiler keeps the whole record live and k_ransac_hyp goes from 168 to 208 registers (wave_hypotheses says what leaving 168
 // costs), k_ransac_finish from 160 to 176 bytes of scratch and its table form from 192 to 208.  sample4 stays the certificate's.
 __device__ inline void sample_hypothesis(const float *P0, int l0, const int64_t *pidx, const float *P1, int l1, int N,
                                          const double *r4, float R[9], float T[3]) {
@@ -274,13 +274,13 @@ __device__ inline void hypothesis_bound(const Sample4 &s, HypBound &hb) {
 }
 
 // Two launches per set of pairs (a third between them, k_ransac_hyp_up below, when a pair leaves a certificate).
-//   k_ransac_hyp     the 500 hypotheses of the first threshold level (0.4 m), four per wavefront, 16 per workgroup:
+//   k_ransac_hyp     the 500 hypotheses of the first threshold level (0.4 m), sixteen per wavefront, 64 per workgroup:
 //                    the matched pairs (P0[pair_idx[i]], P1[i]) are gathered once per workgroup into LDS (coalesced;
 //                    the residual loop then never touches global memory), Kabsch on the 4-samples (one hypothesis
-//                    per lane group), residuals of the four poses in one pass, ballot + popcount -> counts[trial].
+//                    per group of four lanes), residuals of four poses per pass, ballot + popcount -> counts[trial].
 //   k_ransac_finish  one workgroup per pair: replays the sequential accept / early-exit rules over the counts
 //                    (Match.py:181-206) as a prefix maximum; if the level failed (no hypothesis reached leastInliers,
-//                    :207-214) it evaluates the next level's 500 hypotheses itself, four per wavefront on eight
+//                    :207-214) it evaluates the next level's 500 hypotheses itself, sixteen per wavefront on eight
 //                    wavefronts (150 us per level; one per wavefront on four took 1.2 ms, which a pipeline felt) -- up to 1.6 m; then the winner's pose, the inlier mask (:193-194), the inlier count
 //                    and the refit over all inliers (:273-282).
 // Everything that crosses workgroups crosses a kernel boundary.  Round 1 finished inside the last workgroup of a
@@ -326,94 +326,111 @@ __device__ inline int hypothesis_count(const float *P0, int l0, const int64_t *p
     return cnt;
 }
 
-// One wavefront = RH_PER_WAVE hypotheses: lane l derives hypothesis l & 3 (the Kabsch step is a long serial f64 chain
-// that costs the same for 1 or 64 lanes; the 16 lanes that share a hypothesis must agree -- the hardware self-check),
-// then the four poses are broadcast through scalar registers and ONE pass over the staged pairs counts the inliers of
-// all four (a pair is read from LDS once).  Round 2 before: one hypothesis per wavefront, 35 us per 8 pairs.
-// `rnd`: the draws of the level (trial t at rnd + 4 t); counts[trial0 .. trial0 + 3] are written.
-#define RH_PER_WAVE 4
+// One wavefront = PW hypotheses, PW = 16 or 4: lane l derives hypothesis l & (PW - 1) (the Kabsch step is a long serial f64 chain
+// that costs the same for 1 or 64 lanes -- about 20 us of a launch, against 4 us for a pass over 1 024 pairs; the 64 / PW lanes
+// that share a hypothesis must agree -- the hardware self-check).  Then PW / RH_PER_PASS scoring passes: each broadcasts four poses
+// through scalar registers (the scalar register budget holds no more) and counts the inliers of all four in ONE walk over the
+// staged pairs (a pair is read from LDS once per pass).  Lane l < PW collects the count (and bound) of hypothesis l and stores it.
+// Sixteen per wavefront is a quarter of the wavefronts, each holding its 168 registers for the same chain and three more passes:
+// what a batch of pairs inside the pipeline launches.  Four per wavefront is one pass behind the chain: the shortest
+// launch, for a call of fewer than RH_WIDE_FROM pairs, which waits for it.  Round 2: one hypothesis per wavefront, 35 us per 8 pairs.
+// `rnd`: the draws of the level (trial t at rnd + 4 t); counts[trial0 .. trial0 + PW - 1] are written.
+#define RH_WIDE 16
+#define RH_NARROW 4
+#define RH_WIDE_FROM 4   // pairs per call from which the hypothesis kernels score RH_WIDE per wavefront (measured at one pair and at eight only: nothing in between)
+#define RH_PER_PASS 4
+#define RH_BLOCKS(PW) ((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * (PW) - 1) / (RE_WAVES * (PW)))   // workgroups per level and pair: 8 or 32, one round
 // CERT: also the certificate's bound (sN: per pair (|p1_j|, g |p0_j|); cert: the record `hi` / `idx` of the trials go to)
-template <bool CERT>
-__device__ __forceinline__ void four_hypotheses(const float *sP0, const float *sP1, int N, const double *rnd, int trial0, float thr, int lane,
+template <bool CERT, int PW>
+__device__ __forceinline__ void wave_hypotheses(const float *sP0, const float *sP1, int N, const double *rnd, int trial0, float thr, int lane,
                                        int32_t *faults, int32_t *counts, const float2 *sN = nullptr, caelo_ransac_cert *cert = nullptr,
                                        int level = 0) {
     // (__forceinline__: with a second caller -- k_ransac_hyp_up -- hipcc stopped inlining this function, and a CALL costs the callers
     // the full register budget: k_ransac_hyp went from 168 to 248 registers, no longer fitted beside two stage-1 workgroups, and its
     // launch stretched from 74 to 199 us inside the pipeline, profiles/r06_kernel_stats_bench.txt)
-    // ---- lane l: hypothesis trial0 + (l & 3) (a trial past the last repeats the last one; its count is not stored)
-    const int mine = min(trial0 + (lane & (RH_PER_WAVE - 1)), CAELO_RANSAC_MAX_TRIALS - 1);
+    // ---- lane l: hypothesis trial0 + (l & (PW - 1)) (a trial past the last repeats the last one; its count is not stored)
+    const int mine = min(trial0 + (lane & (PW - 1)), CAELO_RANSAC_MAX_TRIALS - 1);
+    const bool stores = lane < PW && trial0 + lane < CAELO_RANSAC_MAX_TRIALS;   // lane l < PW keeps hypothesis l's results
     float R[9], T[3];
     HypBound hb = {0.f, 0.f, 0};
     if (CERT) {
         Sample4 smp;
         sample4(sP0, 3, nullptr, sP1, 3, N, rnd + (size_t)mine * 4, smp);
         hypothesis_bound(smp, hb);
-        if (lane < RH_PER_WAVE && trial0 + lane < CAELO_RANSAC_MAX_TRIALS)
+        if (stores)
 #pragma unroll
             for (int q = 0; q < 4; ++q) (level ? cert->idx_up[level - 1] : cert->idx)[trial0 + lane][q] = smp.idx[q];
         rigid_from_H<false>(smp.H, smp.m0, smp.m1, R, T);   // (a rank-2 sample is kind 1: both poses are scored below)
     } else {
         sample_hypothesis(sP0, 3, nullptr, sP1, 3, N, rnd + (size_t)mine * 4, R, T);
     }
-    if (faults) {  // the 16 lanes of a hypothesis hold the same pose, bit for bit
+    if (faults) {  // the 64 / PW lanes of a hypothesis hold the same pose, bit for bit
         unsigned int hsh = 0;
 #pragma unroll
         for (int q = 0; q < 9; ++q) hsh = hsh * 0x9E3779B1u + __float_as_uint(R[q]);
 #pragma unroll
         for (int q = 0; q < 3; ++q) hsh = hsh * 0x9E3779B1u + __float_as_uint(T[q]);
-        const bool bad = hsh != (unsigned int)__shfl_xor((int)hsh, 4) || hsh != (unsigned int)__shfl_xor((int)hsh, 16) ||
-                         hsh != (unsigned int)__shfl_xor((int)hsh, 32);
+        bool bad = false;
+#pragma unroll
+        for (int o = PW; o < 64; o <<= 1) bad = bad || hsh != (unsigned int)__shfl_xor((int)hsh, o);
         if (__ballot(bad) != 0ull && lane == 0) atomicAdd(faults, 1);
     }
-    // ---- the four poses in scalar registers, one pass over the pairs
-    float Rs[RH_PER_WAVE][9], Ts[RH_PER_WAVE][3];
+    int my_cnt = 0, my_hi = 0;
+    // ---- PW / 4 passes: the poses of lanes l0 .. l0 + 3 in scalar registers, one walk over the pairs each
+#pragma unroll 1
+    for (int l0 = 0; l0 < PW && trial0 + l0 < CAELO_RANSAC_MAX_TRIALS; l0 += RH_PER_PASS) {   // (wave-uniform: a pass of trials past the last stores nothing)
+        float Rs[RH_PER_PASS][9], Ts[RH_PER_PASS][3];
 #pragma unroll
-    for (int h = 0; h < RH_PER_WAVE; ++h) {
+        for (int h = 0; h < RH_PER_PASS; ++h) {
 #pragma unroll
-        for (int q = 0; q < 9; ++q) Rs[h][q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(R[q]), h));
+            for (int q = 0; q < 9; ++q) Rs[h][q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(R[q]), l0 + h));
 #pragma unroll
-        for (int q = 0; q < 3; ++q) Ts[h][q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(T[q]), h));
+            for (int q = 0; q < 3; ++q) Ts[h][q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(T[q]), l0 + h));
+        }
+        int cnt[RH_PER_PASS] = {0, 0, 0, 0};
+        const int hh = lane - l0;   // 0 .. 3: the lane that keeps hypothesis l0 + hh
+        if (!CERT) {
+            for (int i = lane; i < ((N + 63) & ~63); i += 64) {
+                const bool live = i < N;
+                const int ii = live ? i : 0;
+                const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
+                const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
+#pragma unroll
+                for (int h = 0; h < RH_PER_PASS; ++h) {
+                    const bool in = live && residual(Rs[h], Ts[h], ax, ay, az, bx, by, bz) < thr;
+                    cnt[h] += __popcll(__ballot(in));
+                }
+            }
+        } else {
+            // ---- the same pass with the certificate's second test (hypothesis_bound)
+            float as[RH_PER_PASS], bs[RH_PER_PASS];
+#pragma unroll
+            for (int h = 0; h < RH_PER_PASS; ++h) {
+                as[h] = thr + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.a), l0 + h));
+                bs[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.b), l0 + h));
+            }
+            int hi[RH_PER_PASS] = {0, 0, 0, 0};
+            for (int i = lane; i < ((N + 63) & ~63); i += 64) {
+                const bool live = i < N;
+                const int ii = live ? i : 0;
+                const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
+                const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
+                const float2 nn = sN[ii];
+#pragma unroll
+                for (int h = 0; h < RH_PER_PASS; ++h) {
+                    const float r = residual(Rs[h], Ts[h], ax, ay, az, bx, by, bz);
+                    cnt[h] += __popcll(__ballot(live && r < thr));
+                    hi[h] += __popcll(__ballot(live && r < as[h] + fmaf(bs[h], nn.x, nn.y)));
+                }
+            }
+            if (hh >= 0 && hh < RH_PER_PASS) my_hi = hh == 0 ? hi[0] : (hh == 1 ? hi[1] : (hh == 2 ? hi[2] : hi[3]));
+        }
+        if (hh >= 0 && hh < RH_PER_PASS) my_cnt = hh == 0 ? cnt[0] : (hh == 1 ? cnt[1] : (hh == 2 ? cnt[2] : cnt[3]));
     }
-    int cnt[RH_PER_WAVE] = {0, 0, 0, 0};
-    if (!CERT) {
-        for (int i = lane; i < ((N + 63) & ~63); i += 64) {
-            const bool live = i < N;
-            const int ii = live ? i : 0;
-            const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
-            const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
-#pragma unroll
-            for (int h = 0; h < RH_PER_WAVE; ++h) {
-                const bool in = live && residual(Rs[h], Ts[h], ax, ay, az, bx, by, bz) < thr;
-                cnt[h] += __popcll(__ballot(in));
-            }
-        }
-    } else {
-        // ---- the same pass with the certificate's second test (hypothesis_bound); rank-2 samples get their two candidate poses
-        // scored as well, rank-1 samples no bound
-        float as[RH_PER_WAVE], bs[RH_PER_WAVE];
-        int kinds[RH_PER_WAVE];
-#pragma unroll
-        for (int h = 0; h < RH_PER_WAVE; ++h) {
-            as[h] = thr + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.a), h));
-            bs[h] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.b), h));
-            kinds[h] = __builtin_amdgcn_readlane(hb.kind, h);
-        }
-        int hi[RH_PER_WAVE] = {0, 0, 0, 0};
-        for (int i = lane; i < ((N + 63) & ~63); i += 64) {
-            const bool live = i < N;
-            const int ii = live ? i : 0;
-            const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
-            const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
-            const float2 nn = sN[ii];
-#pragma unroll
-            for (int h = 0; h < RH_PER_WAVE; ++h) {
-                const float r = residual(Rs[h], Ts[h], ax, ay, az, bx, by, bz);
-                cnt[h] += __popcll(__ballot(live && r < thr));
-                hi[h] += __popcll(__ballot(live && r < as[h] + fmaf(bs[h], nn.x, nn.y)));
-            }
-        }
-        if ((kinds[0] | kinds[1] | kinds[2] | kinds[3]) & 1) {  // wave-uniform: some hypothesis of this wavefront has two candidate poses
-            // (derived again from the sample: cheaper than carrying 24 more registers through the pass every wavefront runs)
+    if (CERT) {
+        // ---- rank-2 samples (kind 1) get their two candidate poses scored as well, rank-1 samples (kind 2) no bound
+        if (__ballot(stores && hb.kind == 1) != 0ull) {  // wave-uniform: some hypothesis of this wavefront has two candidate poses
+            // (derived again from the sample: cheaper than carrying 24 more registers through the passes every wavefront runs)
             float Ra[9], Ta[3], Rb[9], Tb[3];
             bool two;
             {
@@ -421,50 +438,47 @@ __device__ __forceinline__ void four_hypotheses(const float *sP0, const float *s
                 sample4(sP0, 3, nullptr, sP1, 3, N, rnd + (size_t)mine * 4, smp);
                 two = rigid_two_candidates(smp.H, smp.m0, smp.m1, Ra, Ta, Rb, Tb);
             }
-            int ha[RH_PER_WAVE] = {0, 0, 0, 0};
 #pragma unroll 1
-            for (int h = 0; h < RH_PER_WAVE; ++h) {
-                if (kinds[h] != 1) continue;  // (scalar condition)
-                if (!__builtin_amdgcn_readlane((int)two, h)) { ha[h] = N; continue; }
-                float Ras[9], Tas[3], Rbs[9], Tbs[3];
+            for (int h = 0; h < PW && trial0 + h < CAELO_RANSAC_MAX_TRIALS; ++h) {
+                if (__builtin_amdgcn_readlane(hb.kind, h) != 1) continue;  // (scalar condition)
+                int ha = N;
+                if (__builtin_amdgcn_readlane((int)two, h)) {
+                    const float as = thr + __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.a), h));
+                    const float bs = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(hb.b), h));
+                    float Ras[9], Tas[3], Rbs[9], Tbs[3];
 #pragma unroll
-                for (int q = 0; q < 9; ++q) {
-                    Ras[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ra[q]), h));
-                    Rbs[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Rb[q]), h));
-                }
+                    for (int q = 0; q < 9; ++q) {
+                        Ras[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ra[q]), h));
+                        Rbs[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Rb[q]), h));
+                    }
 #pragma unroll
-                for (int q = 0; q < 3; ++q) {
-                    Tas[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ta[q]), h));
-                    Tbs[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[q]), h));
+                    for (int q = 0; q < 3; ++q) {
+                        Tas[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Ta[q]), h));
+                        Tbs[q] = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(Tb[q]), h));
+                    }
+                    int na = 0, nb = 0;
+                    for (int i = lane; i < ((N + 63) & ~63); i += 64) {
+                        const bool live = i < N;
+                        const int ii = live ? i : 0;
+                        const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
+                        const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
+                        const float2 nn = sN[ii];
+                        const float lim = as + fmaf(bs, nn.x, nn.y);
+                        na += __popcll(__ballot(live && residual(Ras, Tas, ax, ay, az, bx, by, bz) < lim));
+                        nb += __popcll(__ballot(live && residual(Rbs, Tbs, ax, ay, az, bx, by, bz) < lim));
+                    }
+                    ha = max(na, nb);
                 }
-                int na = 0, nb = 0;
-                for (int i = lane; i < ((N + 63) & ~63); i += 64) {
-                    const bool live = i < N;
-                    const int ii = live ? i : 0;
-                    const float ax = sP0[3 * ii], ay = sP0[3 * ii + 1], az = sP0[3 * ii + 2];
-                    const float bx = sP1[3 * ii], by = sP1[3 * ii + 1], bz = sP1[3 * ii + 2];
-                    const float2 nn = sN[ii];
-                    const float lim = as[h] + fmaf(bs[h], nn.x, nn.y);
-                    na += __popcll(__ballot(live && residual(Ras, Tas, ax, ay, az, bx, by, bz) < lim));
-                    nb += __popcll(__ballot(live && residual(Rbs, Tbs, ax, ay, az, bx, by, bz) < lim));
-                }
-                ha[h] = max(na, nb);
+                if (lane == h) my_hi = max(my_hi, ha);
             }
-#pragma unroll
-            for (int h = 0; h < RH_PER_WAVE; ++h)
-                if (kinds[h] == 1) hi[h] = max(hi[h], ha[h]);
         }
-#pragma unroll
-        for (int h = 0; h < RH_PER_WAVE; ++h)
-            if (kinds[h] == 2) hi[h] = N;
-        if (lane < RH_PER_WAVE && trial0 + lane < CAELO_RANSAC_MAX_TRIALS)
-            (level ? cert->hi_up[level - 1] : cert->hi)[trial0 + lane] = lane == 0 ? hi[0] : (lane == 1 ? hi[1] : (lane == 2 ? hi[2] : hi[3]));
+        if (hb.kind == 2) my_hi = N;
+        if (stores) (level ? cert->hi_up[level - 1] : cert->hi)[trial0 + lane] = my_hi;
     }
-    if (lane < RH_PER_WAVE && trial0 + lane < CAELO_RANSAC_MAX_TRIALS)
-        counts[trial0 + lane] = lane == 0 ? cnt[0] : (lane == 1 ? cnt[1] : (lane == 2 ? cnt[2] : cnt[3]));
+    if (stores) counts[trial0 + lane] = my_cnt;
 }
 
-template <class PS>
+template <int PW, class PS>
 static __device__ __forceinline__ void ransac_hyp_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
     const auto &P = pair_of(ps, blockIdx.z);
     const float *__restrict__ pc0 = P.pc0, *__restrict__ pc1 = P.pc1;
@@ -505,20 +519,21 @@ static __device__ __forceinline__ void ransac_hyp_body(const PS &ps, int ld0, in
             cert->magic = CAELO_CERT_MAGIC;
         }
     }
-    const int trial0 = (blockIdx.x * RE_WAVES + wave) * RH_PER_WAVE;  // wave-uniform
+    const int trial0 = (blockIdx.x * RE_WAVES + wave) * PW;  // wave-uniform
     if (trial0 >= CAELO_RANSAC_MAX_TRIALS) return;
-    if (!in_lds) {  // more pairs than the LDS stage holds: one hypothesis at a time from global memory
-        for (int h = 0; h < RH_PER_WAVE && trial0 + h < CAELO_RANSAC_MAX_TRIALS; ++h) {
+    if (!in_lds) {  // more pairs than the LDS stage holds: one hypothesis at a time from global memory (a wavefront walks its PW trials
+                    // serially: at sixteen four times as many on a quarter of the wavefronts -- the same counts, never timed)
+        for (int h = 0; h < PW && trial0 + h < CAELO_RANSAC_MAX_TRIALS; ++h) {
             const int cnt = hypothesis_count(pc0, ld0, pair_idx, pc1, ld1, N, P.rand + (size_t)(trial0 + h) * 4, 0.4f, lane, ps.faults);
             if (lane == 0) ws->counts[trial0 + h] = cnt;
         }
         return;
     }
-    if (cert) four_hypotheses<true>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts, sN, cert, 0);
-    else four_hypotheses<false>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts);
+    if (cert) wave_hypotheses<true, PW>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts, sN, cert, 0);
+    else wave_hypotheses<false, PW>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts);
 }
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body(ps, ld0, ld1, k1_max); }
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body(pt, ld0, ld1, k1_max); }
+template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body<PW>(ps, ld0, ld1, k1_max); }
+template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body<PW>(pt, ld0, ld1, k1_max); }
 
 
 // Round 6: certificates for the 0.8 m and 1.6 m levels (Match.py:207-214).  A pair escalates when no hypothesis of a level reaches
@@ -529,8 +544,8 @@ __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_tab(const caelo_pa
 // in which case the host half meets a level without bounds and evaluates it the long way -- still exact); otherwise blockIdx.y's level
 // (0.8 m, 1.6 m: both, the second is wasted when the first succeeds, and escalations are rare) gets its `hi_up` / `idx_up` exactly as
 // the first level got `hi` / `idx`.  The inlier counts of these levels are not kept (scratch): the host half derives them.
-#define RU_BLOCKS 32   // (8 workgroups per level were tried for the sake of the launches that only look and leave: those took as long as before, 43 us on the pair stream, and a batch with a failing pair 4 x longer -- the failing_pairs leg fell from 17.5 k to 9.9 k frames/s)
-template <class PS>
+// (RH_BLOCKS(PW) workgroups per level and pair cover its 500 trials in one round.  At four per wavefront 8 workgroups needed four rounds and a batch with a failing pair took 4 x longer: 32 there)
+template <int PW, class PS>
 static __device__ __forceinline__ void ransac_hyp_up_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
     const auto &P = pair_of(ps, blockIdx.z);
     caelo_ransac_cert *cert = P.cert;
@@ -560,14 +575,14 @@ static __device__ __forceinline__ void ransac_hyp_up_body(const PS &ps, int ld0,
     __syncthreads();
     const int level = 1 + (int)blockIdx.y;   // 1, 2
     if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) cert->levels_up = 1;   // (k_ransac_hyp wrote 0 with the header)
-    // (RU_BLOCKS workgroups per level and pair, each walking its share of the 500 trials: 512 workgroups of 33 KB of LDS that only
-    // look at 500 counts and leave took 48 us of the pair stream per batch to be scheduled beside the encoder's persistent grids)
-    for (int trial0 = (blockIdx.x * RE_WAVES + wave) * RH_PER_WAVE; trial0 < CAELO_RANSAC_MAX_TRIALS; trial0 += RU_BLOCKS * RE_WAVES * RH_PER_WAVE)
-        four_hypotheses<true>(sP0, sP1, N, P.rand + (size_t)level * CAELO_RANSAC_MAX_TRIALS * 4, trial0, 0.4f * (float)(1 << level), lane, ps.faults,
+    // (RH_BLOCKS(PW) workgroups per level and pair, each walking its share of the 500 trials; most launches only look at the 500 counts
+    // and leave, and every workgroup of 33 KB of LDS has to be scheduled beside the encoder's persistent grids first)
+    for (int trial0 = (blockIdx.x * RE_WAVES + wave) * PW; trial0 < CAELO_RANSAC_MAX_TRIALS; trial0 += RH_BLOCKS(PW) * RE_WAVES * PW)
+        wave_hypotheses<true, PW>(sP0, sP1, N, P.rand + (size_t)level * CAELO_RANSAC_MAX_TRIALS * 4, trial0, 0.4f * (float)(1 << level), lane, ps.faults,
                               s_scratch, sN, cert, level);
 }
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body(ps, ld0, ld1, k1_max); }
-__global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body(pt, ld0, ld1, k1_max); }
+template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body<PW>(ps, ld0, ld1, k1_max); }
+template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body<PW>(pt, ld0, ld1, k1_max); }
 
 
 #define RF_WAVES 8   // the accept rules, the mask and the refit use four of them; all eight evaluate a next level's hypotheses
@@ -625,14 +640,14 @@ static __device__ __forceinline__ void ransac_finish_body(const PS &ps, int ld0,
         }
     }
     int level = 0;
-    while (!s_v.success && level < CAELO_RANSAC_LEVELS - 1) {  // rare: the next level's 500 hypotheses, four per wavefront like k_ransac_hyp
+    while (!s_v.success && level < CAELO_RANSAC_LEVELS - 1) {  // rare: the next level's 500 hypotheses, sixteen per wavefront like k_ransac_hyp
         __syncthreads();  // everyone has read s_v before it is overwritten
         ++level;
         const float thr_l = 0.4f * (float)(1 << level);
         const double *rnd_l = rnd + (size_t)level * CAELO_RANSAC_MAX_TRIALS * 4;
         if (in_lds) {
-            for (int trial0 = wave * RH_PER_WAVE; trial0 < CAELO_RANSAC_MAX_TRIALS; trial0 += RF_WAVES * RH_PER_WAVE)
-                four_hypotheses<false>(sP0, sP1, N, rnd_l, trial0, thr_l, lane, ps.faults, ws->counts);
+            for (int trial0 = wave * RH_WIDE; trial0 < CAELO_RANSAC_MAX_TRIALS; trial0 += RF_WAVES * RH_WIDE)   // (one workgroup walks the level: four rounds of the chain, not sixteen)
+                wave_hypotheses<false, RH_WIDE>(sP0, sP1, N, rnd_l, trial0, thr_l, lane, ps.faults, ws->counts);
         } else {
             for (int trial = wave; trial < CAELO_RANSAC_MAX_TRIALS; trial += RF_WAVES) {
                 const int cnt = hypothesis_count(pc0, ld0, pair_idx, pc1, ld1, N, rnd_l + (size_t)trial * 4, thr_l, lane, ps.faults);
@@ -757,12 +772,12 @@ CAELO_API int caelo_ransac(caelo_ctx *c, const float *pc0, int ld0, const float 
 // 0.8 / 1.6 m levels of the pairs whose first level failed (workgroups of the others return at once); `all_cert_only`: the host half
 // decides every pair, no finishing kernel.
 template <class PS>
-static int ransac_launch(const PS &ps, int ld0, int ld1, int64_t k1_max, bool any_cert, bool all_cert_only, hipStream_t s,
+static int ransac_launch(const PS &ps, int ld0, int ld1, int64_t k1_max, bool any_cert, bool all_cert_only, hipStream_t s, int per_wave,
                          void (*hyp)(PS, int, int, int64_t), void (*hyp_up)(PS, int, int, int64_t), void (*finish)(PS, int, int, int64_t)) {
-    hyp<<<dim3((CAELO_RANSAC_MAX_TRIALS + RE_WAVES * RH_PER_WAVE - 1) / (RE_WAVES * RH_PER_WAVE), 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+    hyp<<<dim3(RH_BLOCKS(per_wave), 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
     CAELO_LAUNCH_CHECK();
     if (any_cert) {
-        hyp_up<<<dim3(RU_BLOCKS, 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+        hyp_up<<<dim3(RH_BLOCKS(per_wave), 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
         CAELO_LAUNCH_CHECK();
     }
     if (all_cert_only) return CAELO_OK;
@@ -779,12 +794,18 @@ int ransac_set(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, hipSt
         any_cert = any_cert || ps.p[i].cert != nullptr;
         all_cert_only = all_cert_only && ps.p[i].cert && ps.p[i].cert_only;
     }
-    return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, k_ransac_hyp, k_ransac_hyp_up, k_ransac_finish);
+    if (ps.n >= RH_WIDE_FROM)
+        return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, RH_WIDE, k_ransac_hyp<RH_WIDE>, k_ransac_hyp_up<RH_WIDE>, k_ransac_finish);
+    return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, RH_NARROW, k_ransac_hyp<RH_NARROW>, k_ransac_hyp_up<RH_NARROW>, k_ransac_finish);
 }
 
 // The same launches over one slice of a pair table (caelo_register_pairs): the pipeline's rows, the kernels' table instantiations.
 int ransac_table(const caelo_pair_table &pt, hipStream_t s) {
     CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
-    return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, pt.cert != nullptr, pt.cert && pt.cert_only, s, k_ransac_hyp_tab, k_ransac_hyp_up_tab,
+    const bool any_cert = pt.cert != nullptr, all_cert_only = pt.cert && pt.cert_only;
+    if (pt.n >= RH_WIDE_FROM)
+        return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, any_cert, all_cert_only, s, RH_WIDE, k_ransac_hyp_tab<RH_WIDE>, k_ransac_hyp_up_tab<RH_WIDE>,
+                             k_ransac_finish_tab);
+    return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, any_cert, all_cert_only, s, RH_NARROW, k_ransac_hyp_tab<RH_NARROW>, k_ransac_hyp_up_tab<RH_NARROW>,
                          k_ransac_finish_tab);
 }

@@ -351,7 +351,12 @@ static void respond_fragments(const float *w1, const float *b1, const float *w2,
     }
 }
 
-__global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, int in_w, int in_c, const float *__restrict__ wts, int row0) {
+// amdgpu_waves_per_eu(5, 5): a register budget of 512 / 5.  Under __launch_bounds__(64) alone hipcc spreads the kernel over 100
+// VGPRs + 36 AGPRs (three wavefronts per SIMD on an idle chip, ONE beside two wavefronts of k_enc_stage1x, 2 x 168 registers);
+// asked for five it needs 88 and no AGPR, without scratch -- five alone, two beside stage 1 (20 KB of LDS for eight) -- and the
+// launch alone takes 23.5 instead of 24.5 us.  (6, 6) spills: 80 registers, 40 bytes of scratch.  DESIGN.md 5.2c.
+__global__ void __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(5, 5)))
+k_respond_mfma(const caelo_frame_set fs, int in_w, int in_c, const float *__restrict__ wts, int row0) {
     const float *__restrict__ in = fs.f[blockIdx.z].ring;
     float *__restrict__ resp = fs.f[blockIdx.z].resp;
     const int lane = threadIdx.x, g = lane >> 4, n = lane & 15;
@@ -374,6 +379,7 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
     if (todo == 0ull) return;
     __shared__ float s_in[2][((RESP_STAGE + 63) / 64) * 64];  // (padded: every lane stores NLD elements)
     // staging: element i = lane + 64 q of [row 3][pixel RESP_BPX + 2][channel 3]; everything but the block's column is loop-invariant
+    constexpr int RESP_NO_ELEMENT = -0x40000000;   // padding of the staging array, or a row outside the image
     int goff[NLD];
     unsigned int edge = 0u;  // bit q: the element is the left halo pixel; bit 16 + q: the right one
     float v[NLD];
@@ -383,7 +389,7 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
         const int row = i / RESP_ROW, j = i - row * RESP_ROW, px = j / 3, ci = j - px * 3;
         const int yy = y + row - 1;
         const bool ok = i < RESP_STAGE && (unsigned)yy < (unsigned)CAELO_NET_H;
-        goff[q] = ok ? (yy * in_w + px - 1) * in_c + ci : -1;
+        goff[q] = ok ? (yy * in_w + px - 1) * in_c + ci : RESP_NO_ELEMENT;   // (row 0's left halo pixel has a NEGATIVE offset before the block's column is added)
         edge |= (px == 0 ? 1u : 0u) << q | (px == RESP_BPX + 1 ? 1u : 0u) << (16 + q);
     }
     // branch-free through a buffer descriptor: an element outside the image gets an offset past the end of the buffer and the
@@ -393,7 +399,7 @@ __global__ void __launch_bounds__(64) k_respond_mfma(const caelo_frame_set fs, i
 #define RESP_LOAD(BLK)                                                                                            \
     _Pragma("unroll") for (int q = 0; q < NLD; ++q) {                                                              \
         const unsigned int hide = ((BLK) == 0 ? edge : 0u) | ((BLK) == NBLK - 1 ? edge >> 16 : 0u);               \
-        const bool ok_ = goff[q] >= 0 && !((hide >> q) & 1u);                                                     \
+        const bool ok_ = goff[q] != RESP_NO_ELEMENT && !((hide >> q) & 1u);                                       \
         const int ob_ = ok_ ? (goff[q] + (BLK) * RESP_BPX * in_c) * 4 : 0x7FFFFFF0;                               \
         v[q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsrc, ob_, 0, 0));                  \
     }
