@@ -183,6 +183,8 @@ SIGNATURES = [
     ("caelo_icp_step", c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, C.c_double, c_int, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_icp_loop_ws_bytes", c_i64, [c_i64, c_i64]),
     ("caelo_icp", c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.POINTER(IcpParams), c_vp, c_vp, c_vp]),
+    ("caelo_icp_grid_ws_layout", c_int, [c_i64, c_i64, c_i64, c_i64, c_vp]),
+    ("caelo_icp_grid", c_int, [c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, C.POINTER(IcpParams), c_vp, c_vp, c_vp]),
     ("caelo_pipeline_create", c_int, [c_vp, c_int, c_int, c_i64, C.POINTER(c_vp)]),
     ("caelo_pipeline_destroy", None, [c_vp]),
     ("caelo_pipeline_cert_stats", c_int, [c_vp, C.POINTER(c_i64)]),

@@ -920,10 +920,14 @@ class Engine:
                                            int(min_inliers), _ptr(rt), _ptr(n_in), _ptr(ws), self.stream))
         return rt, n_in
 
-    def icp(self, pc0, pc1, planar0=None, planar1=None, **kw):
+    def icp(self, pc0, pc1, planar0=None, planar1=None, nn="brute", **kw):
         """The reference's ICP loops entirely on the device (caelo_icp): pc1 [n1,3] (and planar1 [m1,6]) are MOVED in place.
         kw: threshold0/1, decay0/1, small_shift, ep, max_iter, min_iter, min_pairs, fail_only_first.  -> IcpResult bytes tensor
-        (read it with ``icp_result``: the only synchronisation)."""
+        (read it with ``icp_result``: the only synchronisation).  nn = "grid": the nearest neighbours come from a cell grid over
+        frame 0 (caelo_icp_grid: the same pairs and bits; it refuses growing thresholds and non-finite coordinates, and
+        synchronises once on entry)."""
+        if nn not in ("brute", "grid"):
+            raise ValueError("nn must be 'brute' or 'grid', not %r" % (nn,))
         for t in (pc0, pc1):
             assert t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == 3 and t.is_contiguous()
         use_planar = planar0 is not None
@@ -937,9 +941,14 @@ class Engine:
         m0 = planar0.shape[0] if use_planar else 0
         m1 = planar1.shape[0] if use_planar else 0
         res = self.empty((C.sizeof(_ffi.IcpResult),), torch.uint8)
-        ws = self._ws("icp_loop", int(self.lib.caelo_icp_loop_ws_bytes(pc1.shape[0], m1)))
-        _ffi.check(self.lib.caelo_icp(self.ctx, _ptr(pc0), pc0.shape[0], _ptr(pc1), pc1.shape[0], _ptr(planar0) if m0 else None, m0,
-                                      _ptr(planar1) if m1 else None, m1, C.byref(prm), _ptr(res), _ptr(ws), self.stream))
+        if nn == "grid":
+            lay = (C.c_int64 * 8)()
+            _ffi.check(self.lib.caelo_icp_grid_ws_layout(pc0.shape[0], pc1.shape[0], m0, m1, C.cast(lay, C.c_void_p)))
+            ws, fn = self._ws("icp_grid", int(lay[7])), self.lib.caelo_icp_grid
+        else:
+            ws, fn = self._ws("icp_loop", int(self.lib.caelo_icp_loop_ws_bytes(pc1.shape[0], m1))), self.lib.caelo_icp
+        _ffi.check(fn(self.ctx, _ptr(pc0), pc0.shape[0], _ptr(pc1), pc1.shape[0], _ptr(planar0) if m0 else None, m0,
+                      _ptr(planar1) if m1 else None, m1, C.byref(prm), _ptr(res), _ptr(ws), self.stream))
         return res
 
     @staticmethod

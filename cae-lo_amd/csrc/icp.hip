@@ -11,7 +11,8 @@
 // Euler-angle stop rule and the threshold decay of the reference's loop).  Every launch starts by reading a `done`
 // word of the state record, so after the loop has ended the remaining launches fall through; the host reads the
 // record once.  Round 1 synchronised twice per iteration (Python loop around caelo_icp_step).
-// At the end: caelo_icp_step, one iteration on its own (k_icp_nn, k_icp_fit_apply) with the loop's walk, fit and move.
+// Then caelo_icp_step, one iteration on its own (k_icp_nn, k_icp_fit_apply) with the loop's walk, fit and move; at the end
+// caelo_icp_grid, the loop with its nearest neighbours from a cell grid over frame 0 (for extended sets of 10^5 points).
 #include "caelo_internal.h"
 #include "caelo_rigid.h"
 
@@ -317,6 +318,267 @@ CAELO_API int caelo_icp_step(caelo_ctx *c, const float *pc0, int64_t n0, float *
     k_icp_nn<<<(unsigned)((n1 + 255) / 256), 256, 0, s>>>(pc0, (int)n0, pc1, (int)n1, threshold, idx0, mask, n_inliers);
     CAELO_LAUNCH_CHECK();
     k_icp_fit_apply<<<1, 256, 0, s>>>(pc0, pc1, (int)n1, idx0, mask, n_inliers, min_inliers, rt);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// caelo_icp_grid: the same loop with the nearest-neighbour search over a cell grid
+// ------------------------------------------------------------------------------------------------
+// Frame 0 never moves during a call and the thresholds only decay, so its points are binned ONCE per call into cubic cells whose
+// edge is the smallest power of two not below the call's initial threshold; every iteration a frame-1 point looks at the 3 x 3 x 3
+// cells around its own.  A pair closer than the threshold differs by less than one cell edge per axis, hence by at most one cell
+// index; the cell index floor(x / edge) - origin is exact in float64 (a power-of-two scaling, a floor, an integer difference) and
+// the clamp to the grid's box is monotone and 1-Lipschitz, so it keeps "at most one".  The distance expression, its type and order
+// and the gate are icp_nn_walk's / k_icp_nn2's; the minimum is kept by (squared distance, original index), which is what the
+// all-pairs walk's strict < over ascending indices keeps.  Where the gate fails idx0 is 0 or the nearest of the neighbourhood, not
+// the global nearest: nothing reads idx0 behind a zero mask (k_icp_update, planar_pair).
+#include <new>
+#include <vector>
+
+#define GRID_CELLS_PTS (1 << 22)     // most cells of the grid over pc0 (a 160 m x 160 m x 32 m box at 0.5 m cells is 3.3 M)
+#define GRID_CELLS_PLANAR (1 << 18)  // ... over planar0 (8 m cells at the reference's 5.0 m threshold)
+#define GRID_SCAN_CHUNK 2048         // cells per workgroup of the scan: 256 threads x 8
+
+struct IcpGrid {
+    double inv;         // 1 / cell edge, a power of two
+    double ox, oy, oz;  // the box's first cell per axis, in cells (integers held in doubles)
+    int32_t nx, ny, nz, ncell;
+};
+
+__host__ __device__ inline int grid_axis(float x, double inv, double o, int n) {
+    return (int)fmin(fmax(floor((double)x * inv) - o, 0.0), (double)(n - 1));
+}
+__host__ __device__ inline int grid_cell(const IcpGrid &g, float x, float y, float z) {
+    return (grid_axis(z, g.inv, g.oz, g.nz) * g.ny + grid_axis(y, g.inv, g.oy, g.ny)) * g.nx + grid_axis(x, g.inv, g.ox, g.nx);
+}
+
+__global__ void __launch_bounds__(256) k_grid_count(const float *__restrict__ p0, int ld0, int n0, IcpGrid g, int *__restrict__ cursor) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n0) return;
+    const float *s = p0 + (size_t)ld0 * i;
+    atomicAdd(&cursor[grid_cell(g, s[0], s[1], s[2])], 1);
+}
+
+// exclusive prefix of cnt inside each chunk of GRID_SCAN_CHUNK cells -> start, the chunk's total -> bsum[chunk].  (cnt and start may
+// be the same array: a thread reads its eight cells before it writes them.)
+__global__ void __launch_bounds__(256) k_grid_scan_chunks(const int *cnt, int *start, int *bsum, int ncell) {
+    __shared__ int wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int base = blockIdx.x * GRID_SCAN_CHUNK + tid * 8;
+    int v[8], s = 0;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { v[k] = base + k < ncell ? cnt[base + k] : 0; s += v[k]; }
+    int inc = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int t = __shfl_up(inc, o); if (lane >= o) inc += t; }
+    if (lane == 63) wsum[wave] = inc;
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < wave; ++w) off += wsum[w];
+    int run = off + inc - s;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { if (base + k < ncell) start[base + k] = run; run += v[k]; }
+    if (tid == 255 && bsum) bsum[blockIdx.x] = off + inc;
+}
+
+__global__ void __launch_bounds__(256) k_grid_scan_add(int *__restrict__ start, const int *__restrict__ bsum, int ncell, int n0) {
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c < ncell) start[c] += bsum[c / GRID_SCAN_CHUNK];
+    if (c == 0) start[ncell] = n0;
+}
+
+// (point, original index) in cell order; the order inside a cell is whatever the atomics give and the query does not depend on it.
+// cursor holds the counts and is back at zero afterwards
+__global__ void __launch_bounds__(256) k_grid_scatter(const float *__restrict__ p0, int ld0, int n0, IcpGrid g, const int *__restrict__ start,
+                                                      int *__restrict__ cursor, int4 *__restrict__ sorted) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n0) return;
+    const float *s = p0 + (size_t)ld0 * i;
+    const int c = grid_cell(g, s[0], s[1], s[2]);
+    const int pos = start[c] + atomicSub(&cursor[c], 1) - 1;
+    sorted[pos] = make_int4(__float_as_int(s[0]), __float_as_int(s[1]), __float_as_int(s[2]), i);
+}
+
+// k_icp_nn2 over the grid: a thread per frame-1 point, nine runs of up to three x-adjacent cells each (x is the fastest cell index,
+// so such a run is one contiguous range of `sorted`).  The ranges are read straight from global memory: neighbouring threads hold
+// unrelated queries, so there is no tile a workgroup could share, and the whole table (16 bytes a point) stays in L2.
+__global__ void __launch_bounds__(256) k_icp_nn_grid(const int4 *__restrict__ sorted, const int *__restrict__ start, IcpGrid g,
+                                                     const float *__restrict__ p1, int ld1, int n1, IcpState *st, int which,
+                                                     int64_t *__restrict__ idx0, uint8_t *__restrict__ mask) {
+    if (st->done || (which && st->iter >= 100)) return;
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j >= n1) return;
+    const double thr = which ? st->thr1 : st->thr0;
+    const float *q = p1 + (size_t)ld1 * j;
+    const double qx = q[0], qy = q[1], qz = q[2];
+    const int cx = grid_axis(q[0], g.inv, g.ox, g.nx), cy = grid_axis(q[1], g.inv, g.oy, g.ny), cz = grid_axis(q[2], g.inv, g.oz, g.nz);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
+    double b = 1.0e300;
+    int bi = 0x7fffffff;
+    for (int z = max(cz - 1, 0); z <= min(cz + 1, g.nz - 1); ++z)
+        for (int y = max(cy - 1, 0); y <= min(cy + 1, g.ny - 1); ++y) {
+            const int row = (z * g.ny + y) * g.nx;
+            const int hi = start[row + x1 + 1];
+            for (int e = start[row + x0]; e < hi; ++e) {
+                const int4 s = sorted[e];
+                const double dx = (double)__int_as_float(s.x) - qx, dy = (double)__int_as_float(s.y) - qy, dz = (double)__int_as_float(s.z) - qz;
+                const double d2 = dx * dx + dy * dy + dz * dz;  // icp_nn_walk's expression
+                if (d2 < b || (d2 == b && s.w < bi)) { b = d2; bi = s.w; }
+            }
+        }
+    const bool found = bi != 0x7fffffff;
+    idx0[j] = found ? bi : 0;
+    mask[j] = (found && sqrt(b) < thr) ? 1 : 0;
+}
+
+// the coordinates of a device array on the host: all finite?  and their range, in cells
+static bool grid_scan_host(const std::vector<float> &h, int ld, int64_t n, double inv, double lo[3], double hi[3]) {
+    for (int a = 0; a < 3; ++a) { lo[a] = 1.0e300; hi[a] = -1.0e300; }
+    for (int64_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) {
+            const float x = h[(size_t)ld * i + a];
+            if (!(x - x == 0.0f)) return false;  // NaN or infinite
+            const double c = floor((double)x * inv);
+            lo[a] = c < lo[a] ? c : lo[a];
+            hi[a] = c > hi[a] ? c : hi[a];
+        }
+    return true;
+}
+
+// the grid over a set whose points span cells lo .. hi: that box, shrunk about its middle along its longest axis until it has at
+// most `cap` cells (points outside land in the edge cells)
+static IcpGrid grid_make(double edge, const double lo[3], const double hi[3], int64_t cap) {
+    double o[3], n[3];
+    for (int a = 0; a < 3; ++a) {
+        o[a] = lo[a] < -1.0e12 ? -1.0e12 : lo[a];
+        const double top = hi[a] > 1.0e12 ? 1.0e12 : hi[a];
+        n[a] = top - o[a] + 1.0;
+        if (n[a] > 1048576.0) { o[a] += floor((n[a] - 1048576.0) / 2.0); n[a] = 1048576.0; }
+    }
+    while (n[0] * n[1] * n[2] > (double)cap) {
+        const int a = n[0] >= n[1] && n[0] >= n[2] ? 0 : (n[1] >= n[2] ? 1 : 2);
+        const double m = ceil(n[a] / 2.0);
+        o[a] += floor((n[a] - m) / 2.0);
+        n[a] = m;
+    }
+    IcpGrid g;
+    g.inv = 1.0 / edge; g.ox = o[0]; g.oy = o[1]; g.oz = o[2];
+    g.nx = (int)n[0]; g.ny = (int)n[1]; g.nz = (int)n[2]; g.ncell = g.nx * g.ny * g.nz;
+    return g;
+}
+
+// smallest power of two not below a positive finite threshold
+static double grid_edge(double thr) {
+    int e;
+    const double m = frexp(thr, &e);  // thr = m 2^e, m in [0.5, 1)
+    return ldexp(1.0, m == 0.5 ? e - 1 : e);
+}
+
+static int64_t grid_align(int64_t b) { return (b + 255) / 256 * 256; }
+
+CAELO_API int caelo_icp_grid_ws_layout(int64_t n0, int64_t n1, int64_t m0, int64_t m1, int64_t out[8]) {
+    CAELO_REQUIRE(out && n0 > 0 && n1 > 0 && m0 >= 0 && m1 >= 0 && n0 < (1 << 30) && n1 < (1 << 30) && m0 < (1 << 30) && m1 < (1 << 30),
+                  "bad argument");
+    int64_t o = grid_align(caelo_icp_loop_ws_bytes(n1, m1));
+    out[0] = o; o += grid_align(((int64_t)GRID_CELLS_PTS + 1) * 4);     // start of the cells of pc0
+    out[1] = o; o += grid_align((int64_t)GRID_CELLS_PTS * 4);           // their counters
+    out[2] = o; o += grid_align(n0 * 16);                               // pc0 in cell order: x, y, z, index
+    out[3] = o; o += grid_align(((int64_t)GRID_CELLS_PLANAR + 1) * 4);  // the same three for planar0
+    out[4] = o; o += grid_align((int64_t)GRID_CELLS_PLANAR * 4);
+    out[5] = o; o += grid_align(m0 * 16);
+    out[6] = o; o += grid_align((int64_t)(GRID_CELLS_PTS / GRID_SCAN_CHUNK) * 4);  // chunk totals of the scan
+    out[7] = o;                                                         // bytes in all
+    return CAELO_OK;
+}
+
+static int grid_build(const float *p0, int ld0, int64_t n0, const IcpGrid &g, int *start, int *cursor, int4 *sorted, int *bsum, hipStream_t s) {
+    const unsigned nb = (unsigned)((n0 + 255) / 256), chunks = (unsigned)((g.ncell + GRID_SCAN_CHUNK - 1) / GRID_SCAN_CHUNK);
+    CAELO_HIP(hipMemsetAsync(cursor, 0, (size_t)g.ncell * 4, s));
+    k_grid_count<<<nb, 256, 0, s>>>(p0, ld0, (int)n0, g, cursor);
+    CAELO_LAUNCH_CHECK();
+    k_grid_scan_chunks<<<chunks, 256, 0, s>>>(cursor, start, bsum, g.ncell);
+    CAELO_LAUNCH_CHECK();
+    k_grid_scan_chunks<<<1, 256, 0, s>>>(bsum, bsum, nullptr, (int)chunks);  // chunks <= GRID_SCAN_CHUNK: one workgroup
+    CAELO_LAUNCH_CHECK();
+    k_grid_scan_add<<<(unsigned)((g.ncell + 255) / 256), 256, 0, s>>>(start, bsum, g.ncell, (int)n0);
+    CAELO_LAUNCH_CHECK();
+    k_grid_scatter<<<nb, 256, 0, s>>>(p0, ld0, (int)n0, g, start, cursor, sorted);
+    CAELO_LAUNCH_CHECK();
+    return CAELO_OK;
+}
+
+CAELO_API int caelo_icp_grid(caelo_ctx *c, const float *pc0, int64_t n0, float *pc1, int64_t n1, const float *planar0, int64_t m0,
+                             float *planar1, int64_t m1, const caelo_icp_params *prm, caelo_icp_result *result, void *ws, void *stream) {
+    static_assert(GRID_CELLS_PTS / GRID_SCAN_CHUNK <= GRID_SCAN_CHUNK && GRID_CELLS_PLANAR <= GRID_CELLS_PTS, "the chunk totals are scanned by one workgroup");
+    CAELO_REQUIRE(c && pc0 && pc1 && prm && result && ws, "null argument");
+    CAELO_REQUIRE(((uintptr_t)ws & 15) == 0, "ws must be 16-byte aligned");  // the (x, y, z, index) tables are read as int4
+    CAELO_REQUIRE(n0 > 0 && n1 > 0 && n0 < (1 << 30) && n1 < (1 << 30), "bad shape");
+    const bool planar = prm->use_planar != 0;
+    if (planar) {
+        CAELO_REQUIRE(planar0 && planar1 && m0 > 0 && m1 > 0, "Found array with 0 sample(s) while a minimum of 1 is required (planar points)");
+        CAELO_REQUIRE(m0 < (1 << 30) && m1 < (1 << 30), "bad shape");
+    }
+    CAELO_REQUIRE(prm->max_iter >= 1 && prm->max_iter <= 1000, "max_iter must be in [1, 1000]");
+    // a grid built for the initial thresholds answers for every later one only if they never grow
+    CAELO_REQUIRE(prm->decay0 > 0.0 && prm->decay0 <= 1.0 && (!planar || (prm->decay1 > 0.0 && prm->decay1 <= 1.0)), "decay must be in (0, 1]: the thresholds must not grow");
+    CAELO_REQUIRE(prm->threshold0 > 0.0 && prm->threshold0 < 1.0e30 && (!planar || (prm->threshold1 > 0.0 && prm->threshold1 < 1.0e30)),
+                  "thresholds must be positive and finite");
+    hipStream_t s = caelo_stream(stream);
+    // the coordinates are looked at on the host before anything is launched: non-finite ones are refused, frame 0's range places the box
+    const double edge_p = grid_edge(prm->threshold0), edge_q = planar ? grid_edge(prm->threshold1) : 1.0;
+    std::vector<float> h0, h1, g0, g1;
+    try {  // (an allocation failure must not leave through the C ABI)
+        h0.resize((size_t)n0 * 3); h1.resize((size_t)n1 * 3);
+        if (planar) { g0.resize((size_t)m0 * 6); g1.resize((size_t)m1 * 6); }
+    } catch (const std::bad_alloc &) {
+        caelo_set_error("%s: no host memory for the coordinate check", __func__);
+        return CAELO_ERR_CAPACITY;
+    }
+    CAELO_HIP(hipMemcpyAsync(h0.data(), pc0, h0.size() * 4, hipMemcpyDeviceToHost, s));
+    CAELO_HIP(hipMemcpyAsync(h1.data(), pc1, h1.size() * 4, hipMemcpyDeviceToHost, s));
+    if (planar) {
+        CAELO_HIP(hipMemcpyAsync(g0.data(), planar0, g0.size() * 4, hipMemcpyDeviceToHost, s));
+        CAELO_HIP(hipMemcpyAsync(g1.data(), planar1, g1.size() * 4, hipMemcpyDeviceToHost, s));
+    }
+    CAELO_HIP(hipStreamSynchronize(s));
+    double lo_p[3], hi_p[3], lo_q[3], hi_q[3], lo_x[3], hi_x[3];
+    bool finite = grid_scan_host(h0, 3, n0, 1.0 / edge_p, lo_p, hi_p) && grid_scan_host(h1, 3, n1, 1.0 / edge_p, lo_x, hi_x);
+    if (planar) finite = finite && grid_scan_host(g0, 6, m0, 1.0 / edge_q, lo_q, hi_q) && grid_scan_host(g1, 6, m1, 1.0 / edge_q, lo_x, hi_x);
+    CAELO_REQUIRE(finite, "non-finite coordinate");
+    const IcpGrid gp = grid_make(edge_p, lo_p, hi_p, GRID_CELLS_PTS);
+    const IcpGrid gq = planar ? grid_make(edge_q, lo_q, hi_q, GRID_CELLS_PLANAR) : gp;
+
+    int64_t lay[8];
+    if (caelo_icp_grid_ws_layout(n0, n1, planar ? m0 : 0, planar ? m1 : 0, lay) != CAELO_OK) return CAELO_ERR_ARG;
+    char *w = (char *)ws;
+    IcpState *st = (IcpState *)ws;
+    int64_t *idx_p = (int64_t *)(w + ICP_STATE_BYTES);
+    int64_t *idx_q = idx_p + n1;
+    uint8_t *mask_p = (uint8_t *)(idx_q + (planar ? m1 : 0));
+    uint8_t *mask_q = mask_p + n1;
+    int *start_p = (int *)(w + lay[0]), *cursor_p = (int *)(w + lay[1]), *start_q = (int *)(w + lay[3]), *cursor_q = (int *)(w + lay[4]);
+    int4 *sorted_p = (int4 *)(w + lay[2]), *sorted_q = (int4 *)(w + lay[5]);
+    int *bsum = (int *)(w + lay[6]);
+    IcpParams kp;
+    kp.max_iter = prm->max_iter; kp.min_iter = prm->min_iter; kp.min_pairs = prm->min_pairs; kp.fail_only_first = prm->fail_only_first;
+    kp.decay0 = prm->decay0; kp.decay1 = prm->decay1; kp.small_shift = prm->small_shift; kp.ep = prm->ep;
+    kp.planar = planar ? 1 : 0; kp.pad = 0;
+    k_icp_init<<<1, 1, 0, s>>>(st, prm->threshold0, prm->threshold1);
+    CAELO_LAUNCH_CHECK();
+    if (grid_build(pc0, 3, n0, gp, start_p, cursor_p, sorted_p, bsum, s) != CAELO_OK) return CAELO_ERR_HIP;
+    if (planar && grid_build(planar0, 6, m0, gq, start_q, cursor_q, sorted_q, bsum, s) != CAELO_OK) return CAELO_ERR_HIP;
+    for (int it = 0; it < prm->max_iter; ++it) {
+        k_icp_nn_grid<<<(unsigned)((n1 + 255) / 256), 256, 0, s>>>(sorted_p, start_p, gp, pc1, 3, (int)n1, st, 0, idx_p, mask_p);
+        CAELO_LAUNCH_CHECK();
+        if (planar) {
+            k_icp_nn_grid<<<(unsigned)((m1 + 255) / 256), 256, 0, s>>>(sorted_q, start_q, gq, planar1, 6, (int)m1, st, 1, idx_q, mask_q);
+            CAELO_LAUNCH_CHECK();
+        }
+        k_icp_update<<<1, 256, 0, s>>>(pc0, pc1, (int)n1, idx_p, mask_p, planar0, planar1, planar ? (int)m1 : 0, idx_q, mask_q, st, kp);
+        CAELO_LAUNCH_CHECK();
+    }
+    k_icp_result<<<1, 1, 0, s>>>(st, result);
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
 }

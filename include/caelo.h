@@ -568,6 +568,26 @@ int64_t caelo_icp_loop_ws_bytes(int64_t n1, int64_t m1);
 int caelo_icp(caelo_ctx *ctx, const float *pc0, int64_t n0, float *pc1, int64_t n1, const float *planar0, int64_t m0, float *planar1,
               int64_t m1, const caelo_icp_params *params, caelo_icp_result *result, void *ws, void *stream);
 
+/* caelo_icp with the nearest-neighbour search over a cell grid: same arguments, parameters and result record, the
+ * same pairs in every iteration and so the same bits in `result`, pc1 and planar1 -- built for extended key point sets of 10^5
+ * points, where the all-pairs walk of caelo_icp is 10^10 distances an iteration.  Frame 0 (pc0, and planar0 on its own) is binned
+ * once per call into cubic cells whose edge is the smallest power of two not below the initial threshold (0.5 -> 0.5, 1.0 -> 1.0,
+ * 5.0 -> 8.0); each iteration a frame-1 point visits the 3 x 3 x 3 cells around its own and keeps the minimum by (squared distance,
+ * original index), with caelo_icp's distance expression and gate.  The box follows frame 0's extent up to 2^22 cells (2^18 for
+ * planar0); points outside it are clamped into its edge cells, which keeps the answer exact.
+ * Refused with CAELO_ERR_ARG before any launch, outputs untouched: what caelo_icp refuses; decay0 (and decay1 with use_planar)
+ * outside (0, 1] -- a grid built for the initial thresholds cannot answer for larger ones; a threshold that is not positive and
+ * finite; a NaN or infinite coordinate in any of the point arrays.  For that check, and to place the box, the arrays are copied
+ * to the host first: unlike caelo_icp the call SYNCHRONISES the stream once on entry.
+ * ws: 16-byte aligned (the tables are read as 16-byte words; every offset is a multiple of 256), out[7] bytes of
+ * caelo_icp_grid_ws_layout(n0, n1, m0, m1, out) (m0 = m1 = 0 without use_planar; CAELO_ERR_ARG for a null out or a size outside [1, 2^30),
+ * m0 / m1 from 0); CAELO_ERR_CAPACITY if the host copies for the coordinate check cannot be allocated.  out[0..2] = byte offsets of the
+ * cell starts [cells + 1] i32, the cell counters and the (x, y, z, index) table [n0][4] of pc0, out[3..5] the same for planar0,
+ * out[6] the scan's chunk totals.  The loop's own record and pair arrays lie in front, as in caelo_icp's workspace. */
+int caelo_icp_grid_ws_layout(int64_t n0, int64_t n1, int64_t m0, int64_t m1, int64_t out[8]);
+int caelo_icp_grid(caelo_ctx *ctx, const float *pc0, int64_t n0, float *pc1, int64_t n1, const float *planar0, int64_t m0, float *planar1,
+                   int64_t m1, const caelo_icp_params *params, caelo_icp_result *result, void *ws, void *stream);
+
 /* ---- evaluation: key point repeatability (EvaluationOnKeypts.py, csrc/evaluate.hip) -----------------------------------------
  * pts [n_frames][ld][3] f64 world-frame key points (device), n_key [n_frames] i32 (device): frame f holds rows 0 .. n_key[f]-1.
  * pairs [n_pairs][2] i32 (device) = (fit frame, query frame).  For every query point: the distance to its nearest fit point, exactly
