@@ -94,6 +94,7 @@ ADAPTIVE_MAX_TRIALS, ADAPTIVE_DRAWS = 10000, 10001   # include/caelo.h CAELO_ADA
 ADAPTIVE_DTYPE = _np.dtype([("R", "f8", (9,)), ("T", "f8", (3,)), ("R_ransac", "f8", (9,)), ("T_ransac", "f8", (3,)), ("n_pairs", "i4"),
                             ("n_inliers", "i4"), ("trials", "i4"), ("best_trial", "i4"), ("status", "i4"), ("reserved", "i4")])
 assert ADAPTIVE_DTYPE.itemsize == 216
+PLANAR_MAX = 48 * 1776   # include/caelo.h CAELO_PLANAR_MAX (caelo_planar_points)
 
 # (name, restype, argtypes) -- must list every symbol include/caelo.h declares
 SIGNATURES = [
@@ -227,6 +228,9 @@ SIGNATURES = [
     ("caelo_host_ransac_adaptive", c_int, [c_vp, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp]),
     ("caelo_register_pairs_adaptive_ws_bytes", c_i64, [c_i64, c_int]),
     ("caelo_register_pairs_adaptive", c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, C.c_double, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int]),
+    ("caelo_planar_ws_bytes", c_i64, []),
+    ("caelo_planar_points", c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_host_planar_points", c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
 ]
 
 _lib = None

@@ -4,6 +4,7 @@ tuples / dtypes, served by the HIP engine.
     reference                                   here
     SphericalRing.ProjectPC2SphericalRing :72   ProjectPC2SphericalRing(PC)
     SphericalRing.GetKeyPtsByAE           :113  GetKeyPtsByAE(SphericalRing, GridCounter, RespondImg)
+    its commented PlanarPts producer  :236-282  GetPlanarPts(SphericalRing, GridCounter, RespondImg); GetKeyPtsByAE(..., planar=True)
     SphericalRing.GetKeyPtsFromRawFileName:389  GetKeyPtsFromRawFileName(rawFileFullPath, RespondLayer)
     Voxel.Voxelization                    :100  Voxelization(PC)
     Voxel.GetPatchesList                  :177  GetPatchesList(Pts, AllVoxels0, AllVoxels1, AllVoxels2)
@@ -184,18 +185,33 @@ def ReconstructionLoss(autoencoder, PatchesList):
     return _out(torch.stack(loss, dim=1), as_np), _out(torch.stack(counts, dim=1), as_np)
 
 
-def GetKeyPtsByAE(SphericalRing, GridCounter, RespondImg):
-    """SphericalRing.py:113-291 -> (KeyPts [K,3] f32, KeyPixels [K,2] i64, PlanarPts [0] f32).
-    A 5-channel ring = demo mode (:414); a cropped 3-channel ring = batch mode
-    (BatchPreprocess.py:97-98,131-136)."""
-    e = default_engine()
-    as_np = _is_np(SphericalRing)
+def _ring_images(SphericalRing, GridCounter, RespondImg):
     ring = _dev(SphericalRing, torch.float32)
     cnt = _dev(np.asarray(GridCounter, dtype=np.int32) if _is_np(GridCounter) else GridCounter, torch.int32)
-    resp = _dev(RespondImg, torch.float32)
+    return ring, cnt, _dev(RespondImg, torch.float32)
+
+
+def GetPlanarPts(SphericalRing, GridCounter, RespondImg):
+    """The PlanarPts the reference's commented per-pixel loop would collect (SphericalRing.py:236-282: PlanarThreshold :129, the PCA
+    block :268-276) -> [m,6] f32 = x, y, z | normal with n_z > 0, in row-major pixel order (Engine.planar_points)."""
+    e = default_engine()
+    planar, _, n = e.planar_points(*_ring_images(SphericalRing, GridCounter, RespondImg))
+    return _out(planar[:int(n.item())], _is_np(SphericalRing))
+
+
+def GetKeyPtsByAE(SphericalRing, GridCounter, RespondImg, planar=False):
+    """SphericalRing.py:113-291 -> (KeyPts [K,3] f32, KeyPixels [K,2] i64, PlanarPts [0] f32).
+    A 5-channel ring = demo mode (:414); a cropped 3-channel ring = batch mode
+    (BatchPreprocess.py:97-98,131-136).  planar = True: PlanarPts is GetPlanarPts' [m,6] array instead of the reference's empty one."""
+    e = default_engine()
+    as_np = _is_np(SphericalRing)
+    ring, cnt, resp = _ring_images(SphericalRing, GridCounter, RespondImg)
     kpts, kpix, nkey, st = e.keypoints(ring, cnt, resp)
     k = int(nkey.item())
     raise_status(int(st.item()))
+    if planar:
+        pts, _, m = e.planar_points(ring, cnt, resp)
+        return _out(kpts[:k], as_np), _out(kpix[:k], as_np), _out(pts[:int(m.item())], as_np)
     planar = np.array([], dtype=np.float32) if as_np else torch.empty(0, dtype=torch.float32, device=e.device)
     return _out(kpts[:k], as_np), _out(kpix[:k], as_np), planar
 

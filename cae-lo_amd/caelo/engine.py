@@ -894,6 +894,20 @@ class Engine:
                                             _ptr(nkey), _ptr(status), self.stream))
         return kpts, kpix, nkey, status
 
+    def planar_points(self, ring, counter, resp):
+        """Planar points with normals (caelo_planar_points; SphericalRing.py:236-282) from what ``keypoints`` takes.
+        -> (planar [PLANAR_MAX,6] f32 = xyz | normal with n_z > 0, pixels [PLANAR_MAX,2] i32 (row, col), n [1] i32): rows 0 .. n - 1
+        in row-major pixel order, zeros behind them.  No synchronisation."""
+        assert ring.dtype == torch.float32 and counter.dtype == torch.int32 and resp.dtype == torch.float32
+        assert ring.is_contiguous() and counter.is_contiguous() and resp.is_contiguous()
+        planar = self.zeros((_ffi.PLANAR_MAX, 6), torch.float32)
+        pixels = self.zeros((_ffi.PLANAR_MAX, 2), torch.int32)
+        n = self.empty((1,), torch.int32)
+        _ffi.check(self.lib.caelo_planar_points(self.ctx, _ptr(ring), ring.shape[1], ring.shape[2], _ptr(counter), counter.shape[1],
+                                                _ptr(resp), _ptr(self._ws("planar", self.lib.caelo_planar_ws_bytes())), _ptr(planar),
+                                                _ptr(pixels), _ptr(n), self.stream))
+        return planar, pixels, n
+
     def extend_keypts(self, ring, counter, key_pixels, n_key=None):
         """ExtendKeyPtsInShpericalRing on device tensors: ring [H,W,C] f32, counter [Hc,Wc] i32 (MUTATED: the windows
         are zeroed like SphericalRing.py:307), key_pixels [K,2] i64 -> (ext_pts [K*169,3] f32, n_ext [1] i32)."""

@@ -14,9 +14,19 @@
 #define ISS_MAX_GRID_Y 65535
 
 // ---- the cyclic Jacobi ---------------------------------------------------------------------------------------------------------
+// __host__ __device__: planar.hip runs it in a kernel and in its host twin.  The device pass compiles the same intrinsics as before;
+// the host pass takes the IEEE division and square root they stand for.
+#define ISS_HD __host__ __device__ __forceinline__
+#ifdef __HIP_DEVICE_COMPILE__
+#define ISS_DIV(a, b) __ddiv_rn((a), (b))
+#define ISS_SQRT(a) __dsqrt_rn(a)
+#else
+#define ISS_DIV(a, b) ((a) / (b))
+#define ISS_SQRT(a) sqrt(a)
+#endif
 
 // (x, y) <- (c * x - s * y, s * x + c * y)
-__device__ __forceinline__ void iss_turn(double &x, double &y, double c, double s) {
+ISS_HD void iss_turn(double &x, double &y, double c, double s) {
     const double x0 = x, y0 = y;
     x = c * x0 - s * y0;
     y = s * x0 + c * y0;
@@ -27,16 +37,16 @@ __device__ __forceinline__ void iss_turn(double &x, double &y, double c, double 
 // and a row and column of zeros stay zeros: c * 0 - s * 0 and s * 0 + c * 0 are 0, and the diagonal entry is never touched.
 // WITH_V: an applied rotation (cosine c, sine s) turns columns P and Q of v as well.
 template <bool WITH_V, int P, int Q>
-__device__ __forceinline__ void iss_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double (*v)[3]) {
+ISS_HD void iss_rotate(double &app, double &aqq, double &apq, double &arp, double &arq, double (*v)[3]) {
     if (apq == 0.0) return;
     const double g = fabs(apq);
     if (fabs(app) + g == fabs(app) && fabs(aqq) + g == fabs(aqq)) {
         apq = 0.0;
         return;
     }
-    const double theta = __ddiv_rn(aqq - app, 2.0 * apq);
-    const double t = __ddiv_rn(copysign(1.0, theta), fabs(theta) + __dsqrt_rn(theta * theta + 1.0));   // (theta^2 = inf: t = 0)
-    const double c = __ddiv_rn(1.0, __dsqrt_rn(t * t + 1.0));
+    const double theta = ISS_DIV(aqq - app, 2.0 * apq);
+    const double t = ISS_DIV(copysign(1.0, theta), fabs(theta) + ISS_SQRT(theta * theta + 1.0));   // (theta^2 = inf: t = 0)
+    const double c = ISS_DIV(1.0, ISS_SQRT(t * t + 1.0));
     const double s = t * c;
     const double h = t * apq;
     app = app - h;
@@ -55,7 +65,7 @@ __device__ __forceinline__ void iss_rotate(double &app, double &aqq, double &apq
 // collects the rotations, and column c is then the eigenvector of the diagonal entry c; a row and column that are exactly zero keep
 // their unit vector exactly.  Without it v is not read (nullptr).  A pure function of the six entries.
 template <bool WITH_V>
-__device__ __forceinline__ void iss_jacobi(double &a00, double &a01, double &a02, double &a11, double &a12, double &a22, double (*v)[3]) {
+ISS_HD void iss_jacobi(double &a00, double &a01, double &a02, double &a11, double &a12, double &a22, double (*v)[3]) {
     for (int sweep = 0; sweep < ISS_SWEEPS; ++sweep) {
         if (a01 == 0.0 && a02 == 0.0 && a12 == 0.0) break;
         iss_rotate<WITH_V, 0, 1>(a00, a11, a01, a02, a12, v);

@@ -15,7 +15,11 @@ kept in a bounded cache.
 
 --icp pt2pt (default): the reference's own alternative at RefinePoses.py:295, ``ICP(KeyPts0, KeyPts1_)`` with MyICP.ICP's defaults.
 --icp pt2plane: the call at :291-294.  GetKeyPtsByAE returns an empty PlanarPts (SphericalRing.py:219,285), on which that call fails
-in scikit-learn (MyICP.py:94), so it is accepted only with --keypts-dir files whose PlanarPts are non-empty for every frame.
+in scikit-learn (MyICP.py:94), so it is accepted only with planar points for every frame: from --keypts-dir files whose PlanarPts are
+non-empty, or, with --scans / --synthetic, from --planar-pts ring.
+--planar-pts ring: a frame's planar points are made on the device beside its extended key points, from the same ring, counter and
+response, by the producer the reference wrote down in GetKeyPtsByAE's commented loop (SphericalRing.py:236-282; caelo_planar_points,
+DESIGN.md 9m).  --save-keypts writes them as PlanarPts.  A frame without a planar point is refused with its number.
 One GPU."""
 import argparse
 import collections
@@ -35,8 +39,9 @@ CACHE_FRAMES = 48   # extended key point sets kept: at most 1024 x 169 points = 
 class KeyPts:
     """frame -> (ExtendedKeyPts [n,3] f32, PlanarPts [m,6] f32) on the host, with the device copy of the extended set kept beside it."""
 
-    def __init__(self, eng, n_frames, keypts_dir=None, files=None, synthetic=None, calib_angle=None, save_dir=None):
+    def __init__(self, eng, n_frames, keypts_dir=None, files=None, synthetic=None, calib_angle=None, save_dir=None, planar_ring=False):
         self.eng, self.n, self.dir, self.files, self.synthetic, self.angle, self.save_dir = eng, n_frames, keypts_dir, files, synthetic, calib_angle, save_dir
+        self.planar_ring = planar_ring   # --planar-pts ring
         self.cache = collections.OrderedDict()   # frame -> (host ext, host planar, device ext)
 
     def path(self, frame):
@@ -61,7 +66,14 @@ class KeyPts:
         if self.angle is not None:
             pc = eng.correct_pc(pc, self.angle)
         ring, cnt, st = eng.project(pc)
-        kpts, kpix, nkey, st = eng.keypoints(ring, cnt, eng.respond(ring), status=st)
+        resp = eng.respond(ring)
+        kpts, kpix, nkey, st = eng.keypoints(ring, cnt, resp, status=st)
+        planar = np.zeros((0, 6), np.float32)
+        if self.planar_ring:   # (before extend_keypts zeroes the key points' windows in cnt)
+            pl, _, n_pl = eng.planar_points(ring, cnt, resp)
+            planar = pl[:int(n_pl.item())].cpu().numpy()
+            if planar.shape[0] == 0:
+                raise SystemExit("frame %d has no planar points" % frame)
         k = int(nkey.item())
         from caelo.engine import raise_status
         raise_status(int(st.item()))
@@ -73,8 +85,9 @@ class KeyPts:
         if self.save_dir:
             where = os.path.abspath(self.save_dir)   # (save_keypts names <seq>/<folder>/<scan name>.mat from the scan's path)
             raw = os.path.join(os.path.dirname(where), "velodyne", os.path.basename(self.files[frame]) if self.files else "%06d.bin" % frame)
-            stageio.save_keypts(raw, kpts[:k].cpu().numpy(), ExtendedKeyPts=host, folder=os.path.basename(where))
-        return host, np.zeros((0, 6), np.float32), dev
+            stageio.save_keypts(raw, kpts[:k].cpu().numpy(), ExtendedKeyPts=host, PlanarPts=planar if self.planar_ring else None,
+                                folder=os.path.basename(where))
+        return host, planar, dev
 
     def _entry(self, frame):
         frame = int(frame)
@@ -142,6 +155,8 @@ def run(argv=None):
     ap.add_argument("--calib-angle", type=float, default=None, metavar="DEG", help="CorrectPC on the device before the projection (raw KITTI scans: 0.22)")
     ap.add_argument("--keypts-dir", help="<seq>/KeyPts: <frame:06d>.bin.mat with ExtendedKeyPts and PlanarPts (BatchPreprocess.py:140-148)")
     ap.add_argument("--save-keypts", metavar="DIR", help="write the key points made from --scans / --synthetic to DIR (a KeyPts folder)")
+    ap.add_argument("--planar-pts", choices=("ring",), help="make every frame's planar points with normals on the device from its ring image "
+                    "(SphericalRing.py:236-282); with --scans / --synthetic, what --icp pt2plane registers with")
     ap.add_argument("--dejump", action="store_true", help="FixJumpPoses first (RefinePoses.py:233-262)")
     ap.add_argument("--mode", default="keyframes", choices=("keyframes", "consecutive"), help="RefineOdometry's iOption 1 / 0")
     ap.add_argument("--start-frame", type=int, default=0, help="iStartFrame")
@@ -164,6 +179,8 @@ def run(argv=None):
         ap.error("--calib-angle is a finite number of degrees and goes with --scans / --synthetic")
     if args.save_keypts and args.keypts_dir:
         ap.error("--save-keypts writes what --scans / --synthetic make")
+    if args.planar_pts and args.keypts_dir:
+        ap.error("--planar-pts makes planar points from --scans / --synthetic; --keypts-dir files carry their own")
     poses_ = stageio.read_poses(args.poses)
     n = poses_.shape[0]
     if n < 4:
@@ -177,12 +194,13 @@ def run(argv=None):
     if args.icp == "pt2plane":   # refused before any launch
         why = ("--icp pt2plane is ICP_Pt2PtAndPt2Plane (RefinePoses.py:291-294), which needs planar points with normals; GetKeyPtsByAE stores an "
                "empty PlanarPts (SphericalRing.py:219,285: its producer is commented out) and scikit-learn refuses to fit it (MyICP.py:94)")
-        if not args.keypts_dir:
+        if not args.keypts_dir and not args.planar_pts:
             ap.error(why + ": give --keypts-dir files that hold PlanarPts, or use --icp pt2pt (RefinePoses.py:295)")
-        counts = KeyPts(None, n, keypts_dir=args.keypts_dir).planar_counts()
-        bad = [f for f, c in enumerate(counts) if c <= 0]
-        if bad:
-            ap.error(why + ": no PlanarPts for frame(s) %s of %s" % (bad[:10], args.keypts_dir))
+        if args.keypts_dir:
+            counts = KeyPts(None, n, keypts_dir=args.keypts_dir).planar_counts()
+            bad = [f for f, c in enumerate(counts) if c <= 0]
+            if bad:
+                ap.error(why + ": no PlanarPts for frame(s) %s of %s" % (bad[:10], args.keypts_dir))
     files = None
     if args.scans:
         files = sorted(glob.glob(os.path.join(args.scans, "*.bin")))
@@ -195,7 +213,7 @@ def run(argv=None):
     eng = default_engine()
     keypts = KeyPts(eng, n, keypts_dir=args.keypts_dir, files=files,
                     synthetic=dict(scene_kind=args.scene, trajectory=args.trajectory) if args.synthetic else None,
-                    calib_angle=args.calib_angle, save_dir=args.save_keypts)
+                    calib_angle=args.calib_angle, save_dir=args.save_keypts, planar_ring=bool(args.planar_pts))
     planar = args.icp == "pt2plane"
     core = refine.make_core(keypts, Tr, device_icp(eng, keypts, args.nn, planar), seed_base=args.seed_base if planar else None, per_pair=True)
     pairs = None

@@ -938,6 +938,36 @@ int caelo_register_pairs_adaptive(caelo_ctx *ctx, const float *rows, int64_t n_f
                                   const double *draws, double threshold, int64_t *pair_idx_out, caelo_adaptive_result *results_out,
                                   uint8_t *masks_out, void *ws, void *stream, const float *desc, int64_t ld_desc, int dim);
 
+/* ---- planar points with normals (additive; the ABI version stays 6; csrc/planar.hip) -----------------------------------
+ * What ICP_Pt2PtAndPt2Plane registers with (RefinePoses.py:291-294; caelo_icp / caelo_icp_grid with use_planar): the producer written
+ * down in GetKeyPtsByAE's commented per-pixel loop (SphericalRing.py:236-282).  Inputs as for caelo_keypoints: ring [>=64][ring_w][ring_c]
+ * f32 (ring_c 3 or 5), counter [>=64][cnt_w] i32 (occupied = counter > 0), resp [64][1792][8] f32.  For every pixel of rows 8..55 and
+ * columns 8..1783 (:64-68) in row-major order:
+ *   1. the pixel is occupied (:243);  2. its 5 x 5 window holds at least 5 occupied pixels beside it (:246-250);
+ *   3. minDiff = the minimum over those of the float32 L2 norm of the response difference (caelo_keypoints' arithmetic; a NaN among
+ *      them stays a NaN and fails every comparison);
+ *   4. if (double)minDiff > 0.2 and the float32 norm of the centre's x, y, z is < 10 the pixel is skipped (:259-262);
+ *   5. (double)minDiff < 0.4 (:268, PlanarThreshold :129);
+ *   6. the float64 covariance (mean = sum / N, centred second moments / (N - 1), summed in window order) of the x, y, z of the
+ *      occupied window pixels without the centre (:269-271), the eigenvector of its smallest eigenvalue by a cyclic Jacobi, the
+ *      first one among equal eigenvalues (:272-274);
+ *   7. |n_z| > 0.9 (:275) -> the row [x, y, z, n_x, n_y, n_z] (:276): the point's float32 bits, the normal rounded to float32, its
+ *      sign chosen so that n_z > 0 (LAPACK's is arbitrary; the ICP multiplies by the normal twice and does not depend on it).
+ * A non-finite coordinate in a window makes the covariance NaN and the pixel fails 7.
+ * planar [CAELO_PLANAR_MAX][6] f32, pixels [CAELO_PLANAR_MAX][2] i32 (row, col; may be NULL), n_planar [1] i32: rows 0 .. n_planar - 1 are
+ * written, in row-major pixel order, the rows behind them are left alone.  No atomic decides a position: the same input gives the
+ * same bytes on every run.
+ * caelo_planar_points: device memory; two launches on `stream`, nothing is read back, nothing waits.  ws: caelo_planar_ws_bytes()
+ *   bytes, 16-byte aligned, no initialisation needed.  Refused before any launch (CAELO_ERR_ARG): a null argument (but pixels), ring_w or
+ *   cnt_w below 1792, ring_c other than 3 or 5, a ws that is not 16-byte aligned.
+ * caelo_host_planar_points: the same per-pixel function compiled for the host, looped over HOST arrays; no context, no device. */
+#define CAELO_PLANAR_MAX (48 * 1776)
+int64_t caelo_planar_ws_bytes(void);
+int caelo_planar_points(caelo_ctx *ctx, const float *ring, int ring_w, int ring_c, const int32_t *counter, int cnt_w, const float *resp,
+                        void *ws, float *planar, int32_t *pixels, int32_t *n_planar, void *stream);
+int caelo_host_planar_points(const float *ring_host, int ring_w, int ring_c, const int32_t *counter_host, int cnt_w, const float *resp_host,
+                             float *planar_host, int32_t *pixels_host, int32_t *n_planar_host);
+
 #ifdef __cplusplus
 }
 #endif
