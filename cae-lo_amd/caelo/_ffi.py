@@ -95,6 +95,7 @@ ADAPTIVE_DTYPE = _np.dtype([("R", "f8", (9,)), ("T", "f8", (3,)), ("R_ransac", "
                             ("n_inliers", "i4"), ("trials", "i4"), ("best_trial", "i4"), ("status", "i4"), ("reserved", "i4")])
 assert ADAPTIVE_DTYPE.itemsize == 216
 PLANAR_MAX = 48 * 1776   # include/caelo.h CAELO_PLANAR_MAX (caelo_planar_points)
+SC_RINGS, SC_SECTORS, LOOP_DENSE_MAX = 20, 60, 4096   # the Scan Context image; caelo_loop_search's dense outputs stop at 4096 frames
 
 # (name, restype, argtypes) -- must list every symbol include/caelo.h declares
 SIGNATURES = [
@@ -231,6 +232,12 @@ SIGNATURES = [
     ("caelo_planar_ws_bytes", c_i64, []),
     ("caelo_planar_points", c_int, [c_vp, c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     ("caelo_host_planar_points", c_int, [c_vp, c_int, c_int, c_vp, c_int, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_sc_ws_bytes", c_i64, [c_i64]),
+    ("caelo_scan_context", c_int, [c_vp, c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_host_scan_context", c_int, [c_vp, c_i64, c_int, c_vp, c_i64, c_vp, c_vp, c_vp]),
+    ("caelo_loop_search_ws_bytes", c_i64, [c_i64, c_i64, c_i64, c_int, c_int]),
+    ("caelo_loop_search", c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, C.c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    ("caelo_host_loop_search", c_int, [c_vp, c_vp, c_i64, c_i64, c_i64, c_int, c_int, C.c_float, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
 ]
 
 _lib = None

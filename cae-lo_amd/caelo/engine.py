@@ -908,6 +908,43 @@ class Engine:
                                                 _ptr(pixels), _ptr(n), self.stream))
         return planar, pixels, n
 
+    def scan_context(self, pts, n_pts):
+        """Scan Context descriptors (caelo_scan_context): pts [F,Nmax,C] f32 (C 3 or 4), n_pts [F] i32 ->
+        (sc [F,20,60] f32, u [F,1200] f32 unit columns, valid [F] i64: bit c = column c is not empty).  No synchronisation."""
+        assert pts.dtype == torch.float32 and pts.dim() == 3 and pts.is_contiguous() and n_pts.dtype == torch.int32 and n_pts.is_contiguous()
+        f = pts.shape[0]
+        assert n_pts.shape == (f,)
+        sc = self.zeros((f, _ffi.SC_RINGS, _ffi.SC_SECTORS), torch.float32)
+        u = self.zeros((f, _ffi.SC_RINGS * _ffi.SC_SECTORS), torch.float32)
+        valid = self.zeros((f,), torch.int64)
+        ws = self._ws("scan_context", int(self.lib.caelo_sc_ws_bytes(f)))
+        _ffi.check(self.lib.caelo_scan_context(self.ctx, _ptr(pts), pts.shape[1], pts.shape[2], _ptr(n_pts), f, _ptr(sc), _ptr(u),
+                                               _ptr(valid), _ptr(ws), self.stream))
+        return sc, u, valid
+
+    def loop_search(self, u, valid, min_gap=50, k=1, max_dist=None, min_cols=1, queries=None, dense=False):
+        """The all-pairs column-shifted search (caelo_loop_search) over what ``scan_context`` returns: for every query
+        i of ``queries`` = (q0, q1) (all frames when None) the k best candidates j <= i - min_gap by (distance, lower j), only those
+        below max_dist when given.  -> (cand [Nq,k] i32, dist [Nq,k] f32, shift [Nq,k] i32), empty slots -1 / +inf / -1; dense = True
+        adds (dist [Nq,N] f32, shift [Nq,N] i8) over every pair, +inf / -1 outside the candidates.  Turning scan i by shift * 6 degrees
+        about z brings it to j's heading.  No synchronisation."""
+        assert u.dtype == torch.float32 and u.dim() == 2 and u.is_contiguous() and valid.dtype == torch.int64 and valid.is_contiguous()
+        n = u.shape[0]
+        q0, q1 = (0, n) if queries is None else (int(queries[0]), int(queries[1]))
+        nq = max(q1 - q0, 0)
+        cand = self.empty((nq, k), torch.int32)
+        dist = self.empty((nq, k), torch.float32)
+        shift = self.empty((nq, k), torch.int32)
+        dd = self.empty((nq, n), torch.float32) if dense else None
+        ds = self.empty((nq, n), torch.int8) if dense else None
+        if nq == 0:   # (an empty tensor has no address to hand over)
+            return (cand, dist, shift, dd, ds) if dense else (cand, dist, shift)
+        ws = self._ws("loop_search", max(16,int(self.lib.caelo_loop_search_ws_bytes(n, q0, q1, int(min_gap), int(k)))))
+        _ffi.check(self.lib.caelo_loop_search(self.ctx, _ptr(u), _ptr(valid), n, q0, q1, int(min_gap), int(k),
+                                              float("inf") if max_dist is None else float(max_dist), int(min_cols), _ptr(cand), _ptr(dist),
+                                              _ptr(shift), _ptr(dd), _ptr(ds), _ptr(ws), self.stream))
+        return (cand, dist, shift, dd, ds) if dense else (cand, dist, shift)
+
     def extend_keypts(self, ring, counter, key_pixels, n_key=None):
         """ExtendKeyPtsInShpericalRing on device tensors: ring [H,W,C] f32, counter [Hc,Wc] i32 (MUTATED: the windows
         are zeroed like SphericalRing.py:307), key_pixels [K,2] i64 -> (ext_pts [K*169,3] f32, n_ext [1] i32)."""

@@ -304,6 +304,59 @@ def save_registration(path, row):
 
 
 
+# ---- loop closures (detect_loops.py's loops file against ground truth) -----------------------------------------------------------
+def lidar_positions(poses, Tr):
+    """Ground truth poses [n, 12] (camera frame) and Tr [3, 4] -> the LiDAR's world positions [n, 3] f64: pose applied to Tr's origin."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 3, 4)
+    t_tr = np.asarray(Tr, dtype=np.float64).reshape(3, 4)[:, 3]
+    return poses[:, :, 0:3] @ t_tr + poses[:, :, 3]
+
+
+def revisits(positions, revisit_radius=4.0, min_gap=50):
+    """-> [n, n] bool: frame j <= i - min_gap lies within revisit_radius metres of frame i (all pairs on the host)."""
+    p = np.asarray(positions, dtype=np.float64)
+    d = np.sqrt(((p[:, None, :] - p[None, :, :]) ** 2).sum(axis=2))
+    i, j = np.mgrid[0:len(p), 0:len(p)]
+    return (d < revisit_radius) & (j <= i - min_gap)
+
+
+def loops(poses, Tr, loop_rows, revisit_radius=4.0, min_gap=50):
+    """Detected loops [m, 19] (caelo.loops: i j dist shift verified n_inliers threshold R(9) T(3)) against ground truth poses.
+    -> dict: n_revisit_queries (frames with a ground-truth revisit), recall (those for which a detected loop is a true revisit),
+    precision / precision_verified (detected / verified loops that are true revisits; nan without any), and for the verified loops
+    the errors of (R, T) against the ground-truth motion of frame i into frame j in the LiDAR frame: error_eulers [v, 3] degrees
+    (GetErrorEulers), error_ts [v, 3] metres, RRE / RTE [v] as sums of absolute components, RTE_norm [v], and success [v] =
+    RRE < 1 degree and RTE < 0.5 m (EvaluationOnRegistration.py:22-23)."""
+    poses = np.asarray(poses, dtype=np.float64).reshape(-1, 12)
+    rows = np.asarray(loop_rows, dtype=np.float64).reshape(-1, 19)
+    n = poses.shape[0]
+    li, lj = rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64)
+    if rows.size and (li.min() < 0 or li.max() >= n or lj.min() < 0 or lj.max() >= n):
+        raise ValueError("a loop names a frame outside the %d ground truth poses" % n)
+    rev = revisits(lidar_positions(poses, Tr), revisit_radius, min_gap)
+    true = rev[li, lj]
+    has = rev.any(axis=1)
+    found = np.zeros(n, dtype=bool)
+    found[li[true]] = True
+    ver = rows[:, 4] > 0
+    R_Tr, T_Tr = GetRtFromOnePose(np.asarray(Tr, dtype=np.float64))
+    R_Tr_inv = np.linalg.inv(R_Tr)
+    T_Tr_inv = -np.dot(R_Tr_inv, T_Tr)
+    gtR = np.zeros((int(ver.sum()), 3, 3))
+    gtT = np.zeros((int(ver.sum()), 3))
+    for k, r in enumerate(rows[ver]):
+        R, T = GetLidarRelRtBetween2Poses(poses[int(r[1])], poses[int(r[0])], R_Tr, T_Tr, R_Tr_inv, T_Tr_inv)
+        gtR[k], gtT[k] = R, T.reshape(3)
+    eul = GetErrorEulers(gtR, rows[ver, 7:16].reshape(-1, 3, 3))
+    err_t = rows[ver, 16:19] - gtT
+    rre, rte = np.abs(eul).sum(axis=1).astype(np.float64), np.abs(err_t).sum(axis=1)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return dict(n_revisit_queries=int(has.sum()), n_loops=len(rows), n_verified=int(ver.sum()),
+                    recall=float(np.float64((found & has).sum()) / has.sum()), precision=float(np.float64(true.sum()) / len(rows)),
+                    precision_verified=float(np.float64((true & ver).sum()) / ver.sum()), error_eulers=eul, error_ts=err_t, RRE=rre, RTE=rte,
+                    RTE_norm=LA.norm(err_t, axis=1), success=(rre < T_RRE) & (rte < T_RTE))
+
+
 # ---- reconstruction quality of an autoencoder (AE4VoxelPatch.py:213,228,242-284) ----------------------------------------------------
 def reconstruction(engine, scans, threshold=0.1):
     """How well the engine's autoencoder (Engine.load_autoencoder) rebuilds the patches of ``scans`` (an iterable of [N,4] f32 clouds):

@@ -7,6 +7,7 @@
                                  [--frame-step s] [--inner] --out AccuracyOfKeyPts_1_0_00.mat
     python evaluate.py reconstruction --autoencoder-h5 AutoencoderModel4VoxelPatch.h5 (--scans <seq>/velodyne | --synthetic N) \\
                                       [--threshold 0.1] [--every k] --out recon.mat
+    python evaluate.py loops --gt poses/00.txt --calib calib/00/calib_.txt --loops loops.txt [--revisit-radius 4] [--min-gap 50]
 
 registration (EvaluationOnRegistration.py / EvalOnReg_KeyPts.py): one --gt / --est / --calib / --matchability per sequence, the
 sequences concatenated; prints RRE, stdRRE, RTE, stdRTE, success rate (RRE < 1 deg and RTE < 0.5 m), inlier ratio (both
@@ -16,6 +17,9 @@ keypoints (EvaluationOnKeypts.py): key point repeatability of one sequence; the 
 reconstruction (AE4VoxelPatch.py:213,228,242-284): how well an autoencoder file rebuilds the patches of scans -- per frame and scale
 the mean binary_crossentropy and the IoU of the voxels with value > threshold (Voxel.VoxelModel2PC's test), and the mean loss over all
 patches (Keras's validation-loss figure); the decoder runs on the GPU (caelo_decode).
+loops: detect_loops.py's loops file against ground truth -- a frame j <= i - min_gap within the revisit radius of frame i (LiDAR
+positions, all pairs on the host) is a revisit; prints the recall over the frames that have one, the precision of the detected and of
+the verified loops, and the verified loops' RRE / RTE against the ground-truth motion (success: RRE < 1 deg and RTE < 0.5 m).
 """
 import argparse
 import os
@@ -55,6 +59,25 @@ def reconstruction_main(ap, a):
     return 0
 
 
+def loops_main(ap, a):
+    from caelo import loops as lp
+    if not a.revisit_radius > 0:
+        ap.error("--revisit-radius must be a positive number of metres")
+    if a.min_gap < 1:
+        ap.error("--min-gap must be >= 1")
+    try:
+        res = ev.loops(np.loadtxt(a.gt), ev.read_tr(a.calib), lp.read_loops(a.loops), a.revisit_radius, a.min_gap)
+    except ValueError as e:
+        ap.error(str(e))
+    print("loops: %d detected, %d verified; %d frames have a revisit within %g m (min gap %d): recall %.6g  precision %.6g  "
+          "precision of verified %.6g" % (res["n_loops"], res["n_verified"], res["n_revisit_queries"], a.revisit_radius, a.min_gap,
+                                          res["recall"], res["precision"], res["precision_verified"]))
+    if res["n_verified"]:
+        print("verified loops: RRE mean %.6g max %.6g deg  RTE mean %.6g max %.6g m (sums of absolute components)  success %d of %d" % (
+            res["RRE"].mean(), res["RRE"].max(), res["RTE"].mean(), res["RTE"].max(), int(res["success"].sum()), res["n_verified"]))
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     sub = ap.add_subparsers(dest="cmd", required=True)
@@ -82,9 +105,17 @@ def main(argv=None):
     c.add_argument("--threshold", type=float, default=0.1, help="a rebuilt voxel is set when its value exceeds this (0 < t < 1)")
     c.add_argument("--every", type=int, default=1, help="evaluate every k-th scan")
     c.add_argument("--out", required=True, help="the result file (.mat): n_key, loss, iou, patch_loss, mean_loss, threshold")
+    lo = sub.add_parser("loops", help="detected loop closures against ground truth: recall, precision, RRE / RTE of the verified ones")
+    lo.add_argument("--gt", required=True, help="ground truth poses [n, 12]")
+    lo.add_argument("--calib", required=True, help="calib_.txt (row 4 = Tr) or KITTI calib.txt")
+    lo.add_argument("--loops", required=True, help="detect_loops.py's output: i j dist shift verified n_inliers threshold R(9) T(3)")
+    lo.add_argument("--revisit-radius", type=float, default=4.0, help="frames closer than this (m) are the same place")
+    lo.add_argument("--min-gap", type=int, default=50, help="a revisit lies at least this many frames back")
     a = ap.parse_args(argv)
     if a.cmd == "reconstruction":
         return reconstruction_main(ap, a)
+    if a.cmd == "loops":
+        return loops_main(ap, a)
     if a.frame_step < 1:
         ap.error("--frame-step must be >= 1")
 

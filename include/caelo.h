@@ -968,6 +968,48 @@ int caelo_planar_points(caelo_ctx *ctx, const float *ring, int ring_w, int ring_
 int caelo_host_planar_points(const float *ring_host, int ring_w, int ring_c, const int32_t *counter_host, int cnt_w, const float *resp_host,
                              float *planar_host, int32_t *pixels_host, int32_t *n_planar_host);
 
+/* ---- loop closure: Scan Context descriptors and the all-pairs shifted search (additive; the ABI version stays 6; csrc/loopclose.hip,
+ * DESIGN.md 9n).  Kim & Kim, "Scan Context", IROS 2018; the definitions below are this library's own (tests/loops_ref.py restates them).
+ * Descriptor  SC [20 rings][60 sectors] f32 per scan.  For every point with finite x, y, z, in float64: r = sqrt(x^2 + y^2),
+ *   theta = atan2(y, x) (+ 2 pi if negative); skipped unless r < 80; ring = min(19, floor(r / 4)), sector = min(59, floor(theta /
+ *   (2 pi) * 60)), evaluated in that order (a point on the +y, -x or -y axis then opens sector 15, 30, 45); SC[ring][sector] = max over
+ *   its points of (float)z + 2.0f; an empty bin is 0.  Further columns of a point are ignored.
+ * Prepared    per column c, in f32: norm^2 = fmaf(v_r, v_r, acc) over r = 0..19 in order, norm = its correctly rounded square root,
+ *   u[c * 20 + r] = v_r / norm (0 for a zero column), bit c of `valid` = norm > 0.
+ * Distance    of query i to candidate j at shift s in 0..59: num_s = the f32 fmaf chain over k = 0..1199 ascending, from 0, of
+ *   u_i[k] * u_j[(k + 20 s) mod 1200]; n_s = popcount(valid_i & rot_s(valid_j)), bit c of rot_s = bit (c + s) mod 60 of valid_j;
+ *   d_s = 1.0f - num_s / (float)n_s.  A shift with n_s < min_cols, or whose d_s is not below +inf, is skipped.  d(i, j) = min_s d_s, the
+ *   lowest s among equals; no shift left: no distance (+inf, shift -1).  If the sensor at frame i is yawed by +psi against frame j at
+ *   the same place, s ~ psi / 6 degrees: turning scan i by +s * 6 degrees about z brings it to j's heading.
+ * Search      the candidates of query i are j in [0, i - min_gap]; the result is the k <= 8 best by (d, then lower j), with max_dist
+ *   (+inf: none) only those with d < max_dist; empty slots are -1 / +inf / -1.
+ * caelo_scan_context: pts [n_frames][ld][cols] f32 (cols 3 or 4), n_pts [n_frames] i32 (DEVICE; points 0 .. min(n_pts, ld) - 1 of a frame
+ *   count) -> sc [n_frames][20][60] f32, u [n_frames][1200] f32 (16-byte aligned), valid [n_frames] u64.  ws: caelo_sc_ws_bytes(n_frames)
+ *   bytes, 16-byte aligned, no initialisation needed.  One fill and two launches on `stream`; nothing waits.  The same input gives the
+ *   same bytes on every run.
+ * caelo_loop_search: u [n][1200], valid [n] as above; queries [q0, q1) (a running odometry asks for its new frames only) ->
+ *   cand, shift [q1 - q0][k] i32, dist [q1 - q0][k] f32; dense_dist [q1 - q0][n] f32 and dense_shift [q1 - q0][n] i8 (both or neither,
+ *   +inf / -1 outside the candidates; for tests and evaluation, refused above n = 4096).  ws: caelo_loop_search_ws_bytes(n, q0, q1,
+ *   min_gap, k) bytes (0 for arguments that are refused), 16-byte aligned, no initialisation needed.  Two launches; nothing waits; no
+ *   atomic decides a result.
+ * Refused before any launch (CAELO_ERR_ARG): a null argument (but the dense pair), cols other than 3 or 4, ld outside [1, 2^31), n_frames
+ *   outside [0, 65535], n outside [1, 2^24], a query range outside 0 <= q0 <= q1 <= n, k outside 1..8, min_gap < 1, min_cols outside
+ *   1..60, a NaN max_dist, one dense output without the other, dense outputs above 4096 frames, a ws or u that is not 16-byte aligned.
+ * caelo_host_scan_context, caelo_host_loop_search: the same functions compiled for the host over HOST arrays, with fmaf, sqrtf and / in
+ *   the same order; no context, no device. */
+int64_t caelo_sc_ws_bytes(int64_t n_frames);
+int caelo_scan_context(caelo_ctx *ctx, const float *pts, int64_t ld, int cols, const int32_t *n_pts, int64_t n_frames, float *sc, float *u,
+                       uint64_t *valid, void *ws, void *stream);
+int caelo_host_scan_context(const float *pts_host, int64_t ld, int cols, const int32_t *n_pts_host, int64_t n_frames, float *sc_host,
+                            float *u_host, uint64_t *valid_host);
+int64_t caelo_loop_search_ws_bytes(int64_t n, int64_t q0, int64_t q1, int min_gap, int k);
+int caelo_loop_search(caelo_ctx *ctx, const float *u, const uint64_t *valid, int64_t n, int64_t q0, int64_t q1, int min_gap, int k,
+                      float max_dist, int min_cols, int32_t *cand, float *dist, int32_t *shift, float *dense_dist, int8_t *dense_shift,
+                      void *ws, void *stream);
+int caelo_host_loop_search(const float *u_host, const uint64_t *valid_host, int64_t n, int64_t q0, int64_t q1, int min_gap, int k,
+                           float max_dist, int min_cols, int32_t *cand_host, float *dist_host, int32_t *shift_host, float *dense_dist_host,
+                           int8_t *dense_shift_host);
+
 #ifdef __cplusplus
 }
 #endif
