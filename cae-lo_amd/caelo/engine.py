@@ -1881,6 +1881,21 @@ class Engine:
                 batch.result[j].copy_(r); batch.inlier_mask[j].copy_(m); batch.pair_idx[j].copy_(x)
         return tied, counts
 
+    def _table_args(self, who, rows, n_key, table, desc):
+        """What register_pairs and register_pairs_adaptive check alike: rows [F,1024,64], n_key [F], desc [F,1024,D] or None.
+        -> the table as [P,2] int64, every index within 32 bits."""
+        assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
+        if desc is not None:
+            if desc.dtype != torch.float32 or desc.dim() != 3 or tuple(desc.shape[:2]) != (rows.shape[0], MAX_K) or not 1 <= desc.shape[2] <= 256:
+                raise ValueError("desc [F=%d,%d,D<=256] f32, got %s %s" % (rows.shape[0], MAX_K, tuple(desc.shape), desc.dtype))
+            if desc.stride(2) != 1 or desc.stride(0) != MAX_K * desc.stride(1) or desc.stride(1) < desc.shape[2]:
+                raise ValueError("desc must be contiguous or a column slice of a contiguous [F,%d,ld] block, got strides %s" % (MAX_K, tuple(desc.stride())))
+        assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
+        pr = np.ascontiguousarray(table.cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.int64).reshape(-1, 2)
+        if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
+            raise _ffi.CaeloError("%s: a frame index does not fit 32 bits" % who)
+        return pr
+
     def register_pairs(self, rows, n_key, pairs, seeds, certify=True, desc=None):
         """The pipeline's pair stage over a table of frame pairs of resident rows, ONE call (caelo_register_pairs): ``rows``
         [F,1024,64] f32 and ``n_key`` [F] i32 on the device (a FrameBatch's), ``pairs`` [P,2] (frame 0, frame 1) -- any two frames,
@@ -1893,16 +1908,7 @@ class Engine:
         n_key lies outside [1, 1024].  Synchronises.
         ``desc`` [F,1024,D] f32 on the device (D <= 256; contiguous or row-strided, i.e. a column slice of a wider block): the NN
         match runs on these descriptors instead of the rows' columns 0:60 (caelo_register_pairs_desc); the rows still give xyz."""
-        assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
-        if desc is not None:
-            if desc.dtype != torch.float32 or desc.dim() != 3 or tuple(desc.shape[:2]) != (rows.shape[0], MAX_K) or not 1 <= desc.shape[2] <= 256:
-                raise ValueError("desc [F=%d,%d,D<=256] f32, got %s %s" % (rows.shape[0], MAX_K, tuple(desc.shape), desc.dtype))
-            if desc.stride(2) != 1 or desc.stride(0) != MAX_K * desc.stride(1) or desc.stride(1) < desc.shape[2]:
-                raise ValueError("desc must be contiguous or a column slice of a contiguous [F,%d,ld] block, got strides %s" % (MAX_K, tuple(desc.stride())))
-        assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
-        pr = np.ascontiguousarray(pairs.cpu().numpy() if isinstance(pairs, torch.Tensor) else pairs, dtype=np.int64).reshape(-1, 2)
-        if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
-            raise _ffi.CaeloError("register_pairs: a frame index does not fit 32 bits")
+        pr = self._table_args("register_pairs", rows, n_key, pairs, desc)
         P = int(pr.shape[0])
         if isinstance(seeds, np.ndarray) and seeds.dtype == np.float64:
             draws = np.ascontiguousarray(seeds).reshape(P, -1)
@@ -1981,16 +1987,7 @@ class Engine:
         frame A's points, the other way round from ``register_pairs``; the pose maps frame b into frame a all the same.
         -> RegisteredPairs(results [P] (_ffi.ADAPTIVE_DTYPE), masks [P,1024] u8 (host), pair_idx (device), evals = the trial counts,
         status [P]) in the table's order.  The same refusals before any launch as ``register_pairs``.  Synchronises."""
-        assert rows.dtype == torch.float32 and rows.dim() == 3 and tuple(rows.shape[1:]) == (MAX_K, 64) and rows.is_contiguous()
-        if desc is not None:
-            if desc.dtype != torch.float32 or desc.dim() != 3 or tuple(desc.shape[:2]) != (rows.shape[0], MAX_K) or not 1 <= desc.shape[2] <= 256:
-                raise ValueError("desc [F=%d,%d,D<=256] f32, got %s %s" % (rows.shape[0], MAX_K, tuple(desc.shape), desc.dtype))
-            if desc.stride(2) != 1 or desc.stride(0) != MAX_K * desc.stride(1) or desc.stride(1) < desc.shape[2]:
-                raise ValueError("desc must be contiguous or a column slice of a contiguous [F,%d,ld] block, got strides %s" % (MAX_K, tuple(desc.stride())))
-        assert n_key.dtype == torch.int32 and n_key.is_contiguous() and n_key.numel() == rows.shape[0]
-        pr = np.ascontiguousarray(table.cpu().numpy() if isinstance(table, torch.Tensor) else table, dtype=np.int64).reshape(-1, 2)
-        if pr.size and (pr.min() < -(1 << 31) or pr.max() >= (1 << 31)):
-            raise _ffi.CaeloError("register_pairs_adaptive: a frame index does not fit 32 bits")
+        pr = self._table_args("register_pairs_adaptive", rows, n_key, table, desc)
         P = int(pr.shape[0])
         dim = 60 if desc is None else int(desc.shape[2])
         idx = self.zeros((P, MAX_K), torch.int64)

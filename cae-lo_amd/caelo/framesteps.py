@@ -78,56 +78,66 @@ class StepRegistrar:
     """run_sequence.py's hook: called with every finished chunk (frames [c0, c0 + k) of a FrameBatch) of a rank that owns frames
     [lo, hi), it registers the pairs of the steps other than 1 whose frame 1 the chunk holds and whose frame 0 the rank owns -- all
     steps in ONE pair table, so that the pairs that share an anchor frame meet in a launch -- and carries the last max(steps) frames'
-    rows over to the next chunk.  Several ranks: every rank also keeps its FIRST max(steps) frames' rows (``head``), the halo of the
-    rank before it, which registers the pairs that straddle the boundary (``boundary``: frame 0 its own); ``export`` / ``merge``
-    bring every step's results together in pair order."""
+    rows over to the next chunk.  run_sequence.run_desc ``push``es chunks of rows with another method's descriptor block beside
+    them.  Several ranks: every rank also keeps its FIRST max(steps) frames' rows (``head``), the halo of the rank before it, which
+    registers the pairs that straddle the boundary (``boundary``: frame 0 its own); ``export`` / ``merge`` bring every step's
+    results together in pair order."""
 
-    def __init__(self, eng, steps, seed_base, certify, lo=0, registrar=None):
-        """``registrar``: None = Match.py's RANSAC4RT (Engine.register_pairs; step 1 is the pipeline's own), or (draws, threshold) =
-        the comparison protocol's ransacfitRt.m (Engine.register_pairs_adaptive) -- then step 1 is registered here as well, from the
-        same resident rows, and one more frame is carried for it."""
+    def __init__(self, eng, steps, seed_base, certify, lo=0, registrar=None, step_one=False):
+        """``registrar``: None = Match.py's RANSAC4RT (Engine.register_pairs; step 1 is the pipeline's own unless ``step_one``), or
+        (draws, threshold) = the comparison protocol's ransacfitRt.m (Engine.register_pairs_adaptive) -- then step 1 is registered
+        here as well, from the same resident rows.  Whenever step 1 is registered here one more frame is carried for it."""
         self.eng, self.seed_base, self.certify, self.lo = eng, int(seed_base), certify, int(lo)
         self.registrar = registrar
-        self.steps = [s for s in steps if s != 1 or registrar is not None]
-        self.m = carry_frames(steps) if registrar is None else max(1, carry_frames(steps))
-        self.rows = self.n_key = None     # the carried frames [base, base + len)
+        step_one = step_one or registrar is not None
+        self.steps = [s for s in steps if s != 1 or step_one]
+        self.m = max(1, carry_frames(steps)) if step_one else carry_frames(steps)
+        self.rows = self.n_key = self.desc = None     # the carried frames [base, base + len); desc: their descriptor block, if one is pushed
         self.base = lo
         self.head = []                    # rows of the rank's first m frames (chunk by chunk)
         self.head_n = 0
         self.results = {s: [] for s in self.steps}   # per step: (pair numbers k, record array (_ffi.POSE_DTYPE))
 
-    def _register(self, rows, nk, base, todo):
-        """todo [(s, k, frame 0, frame 1)] on the window rows = frames [base, base + len(rows))."""
+    def _register(self, rows, nk, base, todo, desc=None):
+        """todo [(s, k, frame 0, frame 1)] on the window rows = frames [base, base + len(rows)) (desc: the same frames' descriptors)."""
         if not todo:
             return
         table = [(a - base, b - base) for _, _, a, b in todo]
         assert all(0 <= i < rows.shape[0] for ab in table for i in ab), "a scheduled pair lies outside the resident window"
+        kw = {} if desc is None else {"desc": desc}   # (without descriptors the registrars are called as they always were)
         if self.registrar is not None:
-            out = self.eng.register_pairs_adaptive(rows.contiguous(), nk.contiguous(), table, self.registrar[0], self.registrar[1])
+            out = self.eng.register_pairs_adaptive(rows.contiguous(), nk.contiguous(), table, self.registrar[0], self.registrar[1], **kw)
         else:
-            out = self.eng.register_pairs(rows.contiguous(), nk.contiguous(), table, [self.seed_base + kk for _, kk, _, _ in todo], certify=self.certify)
+            out = self.eng.register_pairs(rows.contiguous(), nk.contiguous(), table, [self.seed_base + kk for _, kk, _, _ in todo],
+                                          certify=self.certify, **kw)
         for s in self.steps:
             sel = [i for i, t in enumerate(todo) if t[0] == s]
             if sel:
                 self.results[s].append((np.array([todo[i][1] for i in sel], dtype=np.int64), out.results[sel]))
 
-    def keep(self, c0, batch):
+    def push(self, c0, rows, n_key, desc=None):
+        """Frames [c0, c0 + len(rows)): rows [k,1024,64], n_key [k] and, optionally, the descriptors [k,1024,D] the match runs on
+        (every chunk with them or none)."""
         import torch
-        k = batch.k
-        rows, nk = batch.rows[:k], batch.n_key[:k]
+        k = rows.shape[0]
         if self.head_n < self.m:
             take = min(k, self.m - self.head_n)
             self.head.append(rows[:take].clone())
             self.head_n += take
         if self.rows is not None:
             assert self.base + self.rows.shape[0] == c0, "chunks must arrive in order"
-            rows, nk = torch.cat([self.rows, rows]), torch.cat([self.n_key, nk])
+            rows, n_key = torch.cat([self.rows, rows]), torch.cat([self.n_key, n_key])
+            desc = None if desc is None else torch.cat([self.desc, desc])
         else:
             self.base = c0
-        self._register(rows, nk, self.base, [(s, kk, a, b) for s in self.steps for kk, a, b in chunk_pairs(c0, c0 + k, s, self.lo)])
+        self._register(rows, n_key, self.base, [(s, kk, a, b) for s in self.steps for kk, a, b in chunk_pairs(c0, c0 + k, s, self.lo)], desc)
         keep_n = min(self.m, rows.shape[0])
         self.base = c0 + k - keep_n
-        self.rows, self.n_key = rows[rows.shape[0] - keep_n:].clone(), nk[nk.shape[0] - keep_n:].clone()
+        self.rows, self.n_key = rows[rows.shape[0] - keep_n:].clone(), n_key[n_key.shape[0] - keep_n:].clone()
+        self.desc = None if desc is None else desc[desc.shape[0] - keep_n:].clone()
+
+    def keep(self, c0, batch):
+        self.push(c0, batch.rows[:batch.k], batch.n_key[:batch.k])
 
     def head_rows(self):
         """[max(steps), 1024, 64]: the rank's first frames (what the rank before it needs); zero rows past a shorter shard."""

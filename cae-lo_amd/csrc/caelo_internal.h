@@ -219,28 +219,6 @@ struct caelo_pair_set {
 };
 int match_set(const caelo_pair_set &ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, hipStream_t s);
 int ransac_set(const caelo_pair_set &ps, int pld0, int pld1, int64_t k1_max, hipStream_t s);
-// The same launches over a pair TABLE on the device (caelo_register_pairs): slot z of a launch is entry order[z] of the table
-// pairs [.][2] = (frame 0, frame 1), both frames rows of ONE resident block [n_frames][CAELO_MAX_KEYPTS][64] f32 (descriptor 0:60 |
-// xyz 60:63 | valid 63, the pipeline's rows).  Per-pair outputs are indexed by the table entry, workspaces by the slot.  The
-// kernels are the set kernels' bodies instantiated for this argument (pair_of): no arithmetic of their own.
-struct caelo_pair_table {
-    const float *rows;
-    const int32_t *n_key;        // [n_frames]
-    const int32_t *pairs;        // [n_pairs][2]
-    int32_t order[CAELO_FB_MAX]; // the table entries of this launch's slots (in the kernel arguments: nothing to upload)
-    int64_t *pair_idx;           // [n_pairs][CAELO_MAX_KEYPTS]
-    const double *rand;          // [n_pairs][CAELO_RANSAC_LEVELS * CAELO_RANSAC_MAX_TRIALS * 4]
-    caelo_pose_result *result;   // [n_pairs] (null with cert_only)
-    uint8_t *mask;               // [n_pairs][CAELO_MAX_KEYPTS] (null with cert_only)
-    caelo_ransac_cert *cert;     // [n_pairs], nullable
-    char *ws_match, *ws_ransac;  // [CAELO_FB_MAX] slots of ws_match_stride / ws_ransac_stride bytes
-    int64_t ws_match_stride, ws_ransac_stride;
-    int32_t cert_only;
-    int32_t n;                   // slots of this launch (<= CAELO_FB_MAX)
-    int32_t *faults;
-};
-int match_table(const caelo_pair_table &pt, hipStream_t s);
-int ransac_table(const caelo_pair_table &pt, hipStream_t s);
 // The comparison protocol's registrar over a whole pair table in ONE launch, a workgroup per entry (adaptive.hip): entry q takes
 // p0[i] = xyz of point i of frame pairs[q][0], p1[i] = xyz of point pair_idx[q][i] of frame pairs[q][1], i < n_key[pairs[q][0]].
 struct caelo_adaptive_table {
@@ -254,25 +232,6 @@ struct caelo_adaptive_table {
     int64_t n_pairs;
 };
 int adaptive_table(const caelo_adaptive_table &at, hipStream_t s);
-#ifdef __HIPCC__
-__device__ __forceinline__ const caelo_pair_dev &pair_of(const caelo_pair_set &ps, unsigned z) { return ps.p[z]; }
-__device__ __forceinline__ caelo_pair_dev pair_of(const caelo_pair_table &pt, unsigned z) {
-    const int64_t q = pt.order[z];
-    const int64_t a = pt.pairs[2 * q], b = pt.pairs[2 * q + 1];   // (checked on the host before any launch)
-    caelo_pair_dev d;
-    d.f0 = pt.rows + a * ((int64_t)CAELO_MAX_KEYPTS * 64); d.f1 = pt.rows + b * ((int64_t)CAELO_MAX_KEYPTS * 64);
-    d.n0 = pt.n_key + a; d.n1 = pt.n_key + b;
-    d.pc0 = d.f0 + 60; d.pc1 = d.f1 + 60;
-    d.pair_idx = pt.pair_idx + q * CAELO_MAX_KEYPTS;
-    d.ws_match = pt.ws_match + (int64_t)z * pt.ws_match_stride; d.ws_ransac = pt.ws_ransac + (int64_t)z * pt.ws_ransac_stride;
-    d.rand = pt.rand + q * ((int64_t)CAELO_RANSAC_LEVELS * CAELO_RANSAC_MAX_TRIALS * 4);
-    d.result = pt.result ? pt.result + q : nullptr;
-    d.mask = pt.mask ? pt.mask + q * CAELO_MAX_KEYPTS : nullptr;
-    d.cert = pt.cert ? pt.cert + q : nullptr;
-    d.cert_only = pt.cert_only;
-    return d;
-}
-#endif
 // the host half of the exact RANSAC on one certificate record (certify.hip): 0 exact, 1 the draws are needed (an escalation, rnd null),
 // 2 no bounds in the record, 3 no record, -1 failure
 int certify_record(const caelo_ransac_cert &c, const double *rnd, caelo_pose_result *res, uint8_t *mask, int64_t mask_len, int32_t *evals);

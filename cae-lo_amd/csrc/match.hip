@@ -3,12 +3,11 @@
 // Reference behaviour restated here (never its code):
 //   NN match             Match.py:257-258   cdist (f64) + argmin(axis=0), first minimum wins
 //
-// Two launches per set or table of pairs: k_match_prep writes frame 0's f16 operand image, k_match_screen screens the all-pairs
+// Two launches per set of pairs: k_match_prep writes frame 0's f16 operand image, k_match_screen screens the all-pairs
 // matrix on the f16 matrix cores and certifies each column's argmin in float64 (match_screen.inc; descriptors wider than 64:
 // match_screen_wide.inc).  Descriptors 63 and 64 wide leave no room for the screen's two norm slots and take k_match_mfma below,
 // the all-f64 kernel.  What follows the match -- RANSAC over the matched pairs and the refit -- is ransac.hip.
 // The workspace of caelo_match is self-cleaning (zero-filled once by its owner).
-#include <type_traits>
 
 #include "caelo_internal.h"
 
@@ -331,26 +330,22 @@ __global__ void __launch_bounds__(64 * MM_WAVES) k_match_mfma(const caelo_pair_s
 #include "match_screen.inc"
 #include "match_screen_wide.inc"
 
-// Every launch of the screen: k_match_prep* + k_match_screen* over one set or table of pairs -- the padded row count, the 16-byte row
-// test (`aligned`: every descriptor pointer of the launch is 16-byte aligned, rows16), the two grids; the kernels follow from the argument
-// (a set or a table) and the number of K = 64 blocks.  `between`: an event recorded after the prep kernel (caelo_match_profile).
+// Every launch of the screen: k_match_prep* + k_match_screen* over one set of pairs -- the padded row count, the 16-byte row test
+// (`aligned`: every descriptor pointer of the launch is 16-byte aligned, rows16), the two grids; the kernels follow from the number of
+// K = 64 blocks.  `between`: an event recorded after the prep kernel (caelo_match_profile).
 static bool rows16(const caelo_pair_set &ps) {
     bool a = true;
     for (int i = 0; i < ps.n; ++i) a = a && (((uintptr_t)ps.p[i].f0 | (uintptr_t)ps.p[i].f1) & 15u) == 0;
     return a;
 }
-template <class PS>
-static int screen_launch(const PS &ps, bool aligned, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, hipStream_t s, hipEvent_t between = nullptr) {
-    constexpr bool TABLE = std::is_same<PS, caelo_pair_table>::value;   // (tables hold the pipeline's rows: 60-d, one block)
+static int screen_launch(const caelo_pair_set &ps, bool aligned, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, hipStream_t s,
+                         hipEvent_t between = nullptr) {
     const int nb = dim <= 62 ? 1 : msw_nb(dim);
     const int64_t kpad = ms_pad16(k0_max > k1_max ? k0_max : k1_max);
     const int v4 = (aligned && dim % 4 == 0 && ld0 % 4 == 0 && ld1 % 4 == 0) ? 1 : 0;
     const dim3 grid_prep((unsigned)((kpad / 16 + 3) / 4), 1, ps.n), grid((unsigned)((k1_max + 16 * MS_CT - 1) / (16 * MS_CT)), 1, ps.n);
-    void (*screen)(PS, int, int64_t, int, int64_t, int, int64_t, int);
-    if constexpr (TABLE) {
-        k_match_prep_tab<<<grid_prep, 256, 0, s>>>(ps, ld0, k0_max, dim, kpad, v4);
-        screen = k_match_screen_tab;
-    } else if (nb == 1) {
+    void (*screen)(caelo_pair_set, int, int64_t, int, int64_t, int, int64_t, int);
+    if (nb == 1) {
         k_match_prep<<<grid_prep, 256, 0, s>>>(ps, ld0, k0_max, dim, kpad, v4);
         screen = k_match_screen;
     } else {
@@ -395,7 +390,7 @@ CAELO_API int caelo_match_profile(caelo_ctx *c, const float *const *rows, int n_
     float both = 0.f, prep = 0.f;
     for (int r = 0; r < repeats && rc == CAELO_OK; ++r) {
         CAELO_HIP(hipEventRecord(ev[0], s));
-        rc = screen_launch(ps, true, 64, CAELO_MAX_KEYPTS, 64, CAELO_MAX_KEYPTS, 60, s, ev[1]);   // (the pipeline's rows, as match_table)
+        rc = screen_launch(ps, true, 64, CAELO_MAX_KEYPTS, 64, CAELO_MAX_KEYPTS, 60, s, ev[1]);   // (the pipeline's rows: 60-d, one block)
         if (rc != CAELO_OK) break;
         CAELO_HIP(hipEventRecord(ev[2], s));
         CAELO_HIP(hipEventSynchronize(ev[2]));
@@ -428,12 +423,4 @@ int match_set(const caelo_pair_set &ps, int ld0, int64_t k0_max, int ld1, int64_
         k_match_mfma<false><<<grid, 64 * MM_WAVES, 0, s>>>(ps, ld0, k0_max, ld1, k1_max, dim);
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
-}
-
-// The match's launches over one slice of a pair table (caelo_register_pairs): the shapes of match_set for the pipeline's rows
-// (ld 64, 1024 rows, descriptor width 60, 16-byte aligned rows: the vector loads), the kernels' table instantiations.
-int match_table(const caelo_pair_table &pt, hipStream_t s) {
-    CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
-    CAELO_REQUIRE((((uintptr_t)pt.rows) & 15u) == 0, "rows not 16-byte aligned");
-    return screen_launch(pt, true, 64, CAELO_MAX_KEYPTS, 64, CAELO_MAX_KEYPTS, 60, s);
 }

@@ -155,10 +155,8 @@ __device__ inline float ms_fragments(const float *__restrict__ f, int ld, int ro
 
 // frame 0 of every pair as A fragments: one wavefront per 16-row tile (frame 1's 16 columns are converted by the wavefronts that
 // own them, in k_match_screen)
-// (PS: where the launch's pairs come from -- a caelo_pair_set in the kernel arguments or a caelo_pair_table on the device, pair_of)
-template <class PS>
-static __device__ __forceinline__ void match_prep_body(const PS &ps, int ld0, int64_t k0_max, int dim, int64_t kpad, int vec) {
-    const auto &P = pair_of(ps, blockIdx.z);
+static __device__ __forceinline__ void match_prep_body(const caelo_pair_set &ps, int ld0, int64_t k0_max, int dim, int64_t kpad, int vec) {
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     const int k0 = P.n0 ? min(max(*P.n0, 0), (int)k0_max) : (int)k0_max;
     const MsWs W = ms_ws(P.ws_match, kpad, 1);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
@@ -175,9 +173,6 @@ static __device__ __forceinline__ void match_prep_body(const PS &ps, int ld0, in
 }
 __global__ void __launch_bounds__(256) k_match_prep(const caelo_pair_set ps, int ld0, int64_t k0_max, int dim, int64_t kpad, int vec) {
     match_prep_body(ps, ld0, k0_max, dim, kpad, vec);
-}
-__global__ void __launch_bounds__(256) k_match_prep_tab(const caelo_pair_table pt, int ld0, int64_t k0_max, int dim, int64_t kpad, int vec) {
-    match_prep_body(pt, ld0, k0_max, dim, kpad, vec);
 }
 
 // cdist's distance of two frame-0 rows to one frame-1 row, exactly as exact_dist computes it (sequential f64 sum of squared
@@ -362,9 +357,8 @@ static __device__ __forceinline__ void ms_certify_tail(const float *__restrict__
 #ifndef MS_OCC
 #define MS_OCC 4
 #endif
-template <class PS>
-static __device__ __forceinline__ void match_screen_body(const PS &ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, int64_t kpad, int vec) {
-    const auto &P = pair_of(ps, blockIdx.z);
+static __device__ __forceinline__ void match_screen_body(const caelo_pair_set &ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max, int dim, int64_t kpad, int vec) {
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     const float *__restrict__ f0 = P.f0, *__restrict__ f1 = P.f1;
     int64_t *__restrict__ pair_idx = P.pair_idx;
     const MsWs W = ms_ws(P.ws_match, kpad, 1);
@@ -491,8 +485,4 @@ static __device__ __forceinline__ void match_screen_body(const PS &ps, int ld0, 
 __global__ void __launch_bounds__(64 * MS_NW, MS_OCC) k_match_screen(const caelo_pair_set ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max,
                                                              int dim, int64_t kpad, int vec) {
     match_screen_body(ps, ld0, k0_max, ld1, k1_max, dim, kpad, vec);
-}
-__global__ void __launch_bounds__(64 * MS_NW, MS_OCC) k_match_screen_tab(const caelo_pair_table pt, int ld0, int64_t k0_max, int ld1, int64_t k1_max,
-                                                                 int dim, int64_t kpad, int vec) {
-    match_screen_body(pt, ld0, k0_max, ld1, k1_max, dim, kpad, vec);
 }

@@ -39,7 +39,7 @@ __host__ __device__ inline int msw_nb(int dim) { return (dim + 2 + 63) / 64; }
 
 // frame 0 of every pair as A fragments: one wavefront per 16-row tile, a first pass over the row for its norms, a second for the blocks
 __global__ void __launch_bounds__(256) k_match_prep_wide(const caelo_pair_set ps, int ld0, int64_t k0_max, int dim, int nb, int64_t kpad, int vec) {
-    const auto &P = pair_of(ps, blockIdx.z);
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     const int k0 = P.n0 ? min(max(*P.n0, 0), (int)k0_max) : (int)k0_max;
     const MsWs W = ms_ws(P.ws_match, kpad, nb);
     const int lane = threadIdx.x & 63, g = lane >> 4, m = lane & 15;
@@ -99,7 +99,7 @@ static __device__ __forceinline__ void msw_tile_products(const uint4 (&fr)[NB * 
 template <int NB>
 __global__ void __launch_bounds__(64 * MS_NW, MSW_OCC(NB)) k_match_screen_wide(const caelo_pair_set ps, int ld0, int64_t k0_max, int ld1, int64_t k1_max,
                                                                                 int dim, int64_t kpad, int vec) {
-    const auto &P = pair_of(ps, blockIdx.z);
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     const float *__restrict__ f0 = P.f0, *__restrict__ f1 = P.f1;
     int64_t *__restrict__ pair_idx = P.pair_idx;
     const MsWs W = ms_ws(P.ws_match, kpad, NB);

@@ -7,7 +7,7 @@
 //   SolveRelativePose    Match.py:260-283   inlier refit
 //
 // The reference draws from NumPy's global RNG inside the loop; here the caller hands over the uniform doubles in
-// consumption order (3 levels x 500 trials x 4).  Up to three launches per set or table of pairs; what crosses
+// consumption order (3 levels x 500 trials x 4).  Up to three launches per set of pairs; what crosses
 // workgroups crosses a launch (the note above RE_WAVES says why no workgroup finishes for the others):
 //   k_ransac_hyp      the first level's 500 hypotheses scored in parallel, and the certificate's bounds (certify.hip)
 //   k_ransac_hyp_up   only for pairs that leave a certificate and whose first level failed: the upper levels' bounds
@@ -174,7 +174,7 @@ __device__ inline void sample4(const float *P0, int l0, const int64_t *pidx, con
 // hypothesis from 4 sampled pairs (SolveRT on the sample, Match.py:141-157)
 // The same arithmetic as sample4 followed by rigid_from_H<false>(s.H, s.m0, s.m1, R, T), written out on purpose: through a Sample4
 // the compiler keeps the whole record live and k_ransac_hyp goes from 168 to 208 registers (wave_hypotheses says what leaving 168
-// costs), k_ransac_finish from 160 to 176 bytes of scratch and its table form from 192 to 208.  sample4 stays the certificate's.
+// costs), k_ransac_finish from 160 to 176 bytes of scratch.  sample4 stays the certificate's.
 __device__ inline void sample_hypothesis(const float *P0, int l0, const int64_t *pidx, const float *P1, int l1, int N,
                                          const double *r4, float R[9], float T[3]) {
     float s0[4][3], s1[4][3];
@@ -478,9 +478,9 @@ __device__ __forceinline__ void wave_hypotheses(const float *sP0, const float *s
     if (stores) counts[trial0 + lane] = my_cnt;
 }
 
-template <int PW, class PS>
-static __device__ __forceinline__ void ransac_hyp_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
-    const auto &P = pair_of(ps, blockIdx.z);
+template <int PW>
+static __device__ __forceinline__ void ransac_hyp_body(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max) {
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     const float *__restrict__ pc0 = P.pc0, *__restrict__ pc1 = P.pc1;
     const int64_t *__restrict__ pair_idx = P.pair_idx;
     RansacWs *ws = (RansacWs *)P.ws_ransac;
@@ -533,7 +533,6 @@ static __device__ __forceinline__ void ransac_hyp_body(const PS &ps, int ld0, in
     else wave_hypotheses<false, PW>(sP0, sP1, N, P.rand, trial0, 0.4f, lane, ps.faults, ws->counts);
 }
 template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body<PW>(ps, ld0, ld1, k1_max); }
-template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_body<PW>(pt, ld0, ld1, k1_max); }
 
 
 // Round 6: certificates for the 0.8 m and 1.6 m levels (Match.py:207-214).  A pair escalates when no hypothesis of a level reaches
@@ -545,9 +544,9 @@ template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_
 // (0.8 m, 1.6 m: both, the second is wasted when the first succeeds, and escalations are rare) gets its `hi_up` / `idx_up` exactly as
 // the first level got `hi` / `idx`.  The inlier counts of these levels are not kept (scratch): the host half derives them.
 // (RH_BLOCKS(PW) workgroups per level and pair cover its 500 trials in one round.  At four per wavefront 8 workgroups needed four rounds and a batch with a failing pair took 4 x longer: 32 there)
-template <int PW, class PS>
-static __device__ __forceinline__ void ransac_hyp_up_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
-    const auto &P = pair_of(ps, blockIdx.z);
+template <int PW>
+static __device__ __forceinline__ void ransac_hyp_up_body(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max) {
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     caelo_ransac_cert *cert = P.cert;
     if (!cert) return;
     RansacWs *ws = (RansacWs *)P.ws_ransac;
@@ -582,13 +581,11 @@ static __device__ __forceinline__ void ransac_hyp_up_body(const PS &ps, int ld0,
                               s_scratch, sN, cert, level);
 }
 template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body<PW>(ps, ld0, ld1, k1_max); }
-template <int PW> __global__ void __launch_bounds__(64 * RE_WAVES) k_ransac_hyp_up_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_hyp_up_body<PW>(pt, ld0, ld1, k1_max); }
 
 
 #define RF_WAVES 8   // the accept rules, the mask and the refit use four of them; all eight evaluate a next level's hypotheses
-template <class PS>
-static __device__ __forceinline__ void ransac_finish_body(const PS &ps, int ld0, int ld1, int64_t k1_max) {
-    const auto &P = pair_of(ps, blockIdx.z);
+static __device__ __forceinline__ void ransac_finish_body(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max) {
+    const caelo_pair_dev &P = ps.p[blockIdx.z];
     if (P.cert && P.cert_only) return;   // (a mixed set: this pair's result comes from the host half)
     const float *__restrict__ pc0 = P.pc0, *__restrict__ pc1 = P.pc1;
     const int64_t *__restrict__ pair_idx = P.pair_idx;
@@ -678,7 +675,7 @@ static __device__ __forceinline__ void ransac_finish_body(const PS &ps, int ld0,
     // dwords) and the sums of the refit over the inliers (:193-194, :273-282)
     // (the sums, their reduction and the fit below are RigidSums / rigid_from_sums of caelo_rigid.h written out.  This kernel runs in
     // the pipeline's pair stage and was held instruction for instruction when this file was split off match.hip; with the helpers it is
-    // the same arithmetic in other instructions -- 128 registers, scratch 160 -> 124 bytes, table form 192 -> 152 -- compiled, never timed)
+    // the same arithmetic in other instructions -- 128 registers, scratch 160 -> 124 bytes -- compiled, never timed)
     double acc[RIGID_TERMS];
 #pragma unroll
     for (int t = 0; t < RIGID_TERMS; ++t) acc[t] = 0.0;
@@ -751,7 +748,6 @@ static __device__ __forceinline__ void ransac_finish_body(const PS &ps, int ld0,
     }
 }
 __global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish(const caelo_pair_set ps, int ld0, int ld1, int64_t k1_max) { ransac_finish_body(ps, ld0, ld1, k1_max); }
-__global__ void __launch_bounds__(64 * RF_WAVES, 4) k_ransac_finish_tab(const caelo_pair_table pt, int ld0, int ld1, int64_t k1_max) { ransac_finish_body(pt, ld0, ld1, k1_max); }
 
 
 CAELO_API int caelo_ransac(caelo_ctx *c, const float *pc0, int ld0, const float *pc1, int ld1, const int64_t *pair_idx,
@@ -768,20 +764,22 @@ CAELO_API int caelo_ransac(caelo_ctx *c, const float *pc0, int ld0, const float 
     return ransac_set(ps, ld0, ld1, k1_max, caelo_stream(stream));
 }
 
-// Every launch of the RANSAC kernels over one set or table of pairs.  `any_cert`: some pair leaves a certificate -- bounds for the
+// Every launch of the RANSAC kernels over one set of pairs.  `any_cert`: some pair leaves a certificate -- bounds for the
 // 0.8 / 1.6 m levels of the pairs whose first level failed (workgroups of the others return at once); `all_cert_only`: the host half
-// decides every pair, no finishing kernel.
-template <class PS>
-static int ransac_launch(const PS &ps, int ld0, int ld1, int64_t k1_max, bool any_cert, bool all_cert_only, hipStream_t s, int per_wave,
-                         void (*hyp)(PS, int, int, int64_t), void (*hyp_up)(PS, int, int, int64_t), void (*finish)(PS, int, int, int64_t)) {
-    hyp<<<dim3(RH_BLOCKS(per_wave), 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+// decides every pair, no finishing kernel.  Sets of RH_WIDE_FROM pairs and more score RH_WIDE hypotheses per wavefront.
+static int ransac_launch(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, bool any_cert, bool all_cert_only, hipStream_t s) {
+    const bool wide = ps.n >= RH_WIDE_FROM;
+    const int blocks = wide ? RH_BLOCKS(RH_WIDE) : RH_BLOCKS(RH_NARROW);
+    auto hyp = wide ? k_ransac_hyp<RH_WIDE> : k_ransac_hyp<RH_NARROW>;
+    auto hyp_up = wide ? k_ransac_hyp_up<RH_WIDE> : k_ransac_hyp_up<RH_NARROW>;
+    hyp<<<dim3(blocks, 1, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
     CAELO_LAUNCH_CHECK();
     if (any_cert) {
-        hyp_up<<<dim3(RH_BLOCKS(per_wave), 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+        hyp_up<<<dim3(blocks, 2, ps.n), 64 * RE_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
         CAELO_LAUNCH_CHECK();
     }
     if (all_cert_only) return CAELO_OK;
-    finish<<<dim3(1, 1, ps.n), 64 * RF_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
+    k_ransac_finish<<<dim3(1, 1, ps.n), 64 * RF_WAVES, 0, s>>>(ps, ld0, ld1, k1_max);
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
 }
@@ -794,18 +792,5 @@ int ransac_set(const caelo_pair_set &ps, int ld0, int ld1, int64_t k1_max, hipSt
         any_cert = any_cert || ps.p[i].cert != nullptr;
         all_cert_only = all_cert_only && ps.p[i].cert && ps.p[i].cert_only;
     }
-    if (ps.n >= RH_WIDE_FROM)
-        return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, RH_WIDE, k_ransac_hyp<RH_WIDE>, k_ransac_hyp_up<RH_WIDE>, k_ransac_finish);
-    return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s, RH_NARROW, k_ransac_hyp<RH_NARROW>, k_ransac_hyp_up<RH_NARROW>, k_ransac_finish);
-}
-
-// The same launches over one slice of a pair table (caelo_register_pairs): the pipeline's rows, the kernels' table instantiations.
-int ransac_table(const caelo_pair_table &pt, hipStream_t s) {
-    CAELO_REQUIRE(pt.n >= 1 && pt.n <= CAELO_FB_MAX, "bad pair count");
-    const bool any_cert = pt.cert != nullptr, all_cert_only = pt.cert && pt.cert_only;
-    if (pt.n >= RH_WIDE_FROM)
-        return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, any_cert, all_cert_only, s, RH_WIDE, k_ransac_hyp_tab<RH_WIDE>, k_ransac_hyp_up_tab<RH_WIDE>,
-                             k_ransac_finish_tab);
-    return ransac_launch(pt, 64, 64, CAELO_MAX_KEYPTS, any_cert, all_cert_only, s, RH_NARROW, k_ransac_hyp_tab<RH_NARROW>, k_ransac_hyp_up_tab<RH_NARROW>,
-                         k_ransac_finish_tab);
+    return ransac_launch(ps, ld0, ld1, k1_max, any_cert, all_cert_only, s);
 }

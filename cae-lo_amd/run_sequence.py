@@ -341,10 +341,8 @@ def run_desc(eng, src, n, seed_base, chunk, steps, certify, registrar=None, cali
     run.  ``registrar`` = (draws, threshold): the comparison protocol's registrar instead (Engine.register_pairs_adaptive; every pair
     consumes the same draws); ``calib_angle`` then corrects the key points of sources other than the auto-encoder's on the device
     (GenerateTrajactory.m:186-190).  -> {step: framesteps.pack_results(...)}."""
-    others = [s for s in steps if s != 1]
-    m = max(1, framesteps.carry_frames(steps))
-    results = {s: [] for s in [1] + others}
-    carried, base = None, 0
+    order = [1] + [s for s in steps if s != 1]
+    stepper = framesteps.StepRegistrar(eng, order, seed_base, certify, 0, registrar=registrar, step_one=True)
     for c0 in range(0, n, chunk):
         c1 = min(n, c0 + chunk)
         rows = np.zeros((c1 - c0, 1024, 64), np.float32)
@@ -360,25 +358,21 @@ def run_desc(eng, src, n, seed_base, chunk, steps, certify, registrar=None, cali
         if calib_angle is not None and src.keypts_source != "ae":   # (a padding row's origin would turn into NaN: it stays zero)
             moved = eng.correct_pc(rows[:, :, 60:63].reshape(-1, 3).contiguous(), calib_angle).view(-1, 1024, 3)
             rows[:, :, 60:63] = torch.where(rows[:, :, 63:64] > 0, moved, torch.zeros_like(moved))
-        if carried is not None:
-            rows, desc, nk = torch.cat([carried[0], rows]), torch.cat([carried[1], desc]), torch.cat([carried[2], nk])
-        else:
-            base = c0
-        todo = [(1, i - 1, i - 1, i) for i in range(max(c0, 1), c1)] + [(s, k, a, b) for s in others for k, a, b in framesteps.chunk_pairs(c0, c1, s, 0)]
-        if todo:
-            table = [(a - base, b - base) for _, _, a, b in todo]
-            if registrar is not None:
-                out = eng.register_pairs_adaptive(rows, nk, table, registrar[0], registrar[1], desc=desc)
-            else:
-                out = eng.register_pairs(rows, nk, table, [seed_base + k for _, k, _, _ in todo], certify=certify, desc=desc)
-            for s in results:
-                sel = [i for i, t in enumerate(todo) if t[0] == s]
-                if sel:
-                    results[s].append((np.array([todo[i][1] for i in sel], dtype=np.int64), out.results[sel]))
-        keep_n = min(m, rows.shape[0])
-        base = c1 - keep_n
-        carried = (rows[rows.shape[0] - keep_n:].clone(), desc[desc.shape[0] - keep_n:].clone(), nk[nk.shape[0] - keep_n:].clone())
-    return {s: framesteps.pack_results(results[s], s) for s in results}
+        stepper.push(c0, rows, nk, desc)
+    return {s: stepper.step_results(s) for s in order}
+
+
+def _write_step(args, s, n, Tr, rel, ok, nin, npairs, its, what="", say=True):
+    """A step's files and its summary line: the poses chained through Tr (one row per input frame for s != 1, framesteps.expand_rows)
+    at framesteps.step_path(--out, s), --matchability (it needs npairs and its) under the same prefix."""
+    assert len(rel) == len(framesteps.step_pairs(n, s)), "step %d: %d pairs registered, %d scheduled" % (s, len(rel), len(framesteps.step_pairs(n, s)))
+    poses = stageio.chain_poses(rel, Tr)
+    stageio.write_poses(framesteps.step_path(args.out, s), poses if s == 1 else framesteps.expand_rows(poses, n, s))
+    if args.matchability:
+        from caelo import evaluate as ev
+        ev.save_matchability(framesteps.step_path(args.matchability, s), nin, npairs, its)
+    if say:
+        print("step %d: %d pairs (%d solved)%s -> %s" % (s, len(rel), int(np.sum(ok)), what, framesteps.step_path(args.out, s)))
 
 
 def _registrar(args):
@@ -412,13 +406,8 @@ def main_desc(args, ap, steps):
     t0 = time.time()
     res = run_desc(eng, src, n, args.seed_base, args.chunk, steps, not args.no_certify, _registrar(args), args.calib_angle)
     dt = time.time() - t0
-    for s_, (rel, ok, nin, npairs, its) in res.items():
-        assert len(rel) == len(framesteps.step_pairs(n, s_))
-        stageio.write_poses(framesteps.step_path(args.out, s_), stageio.chain_poses(rel, Tr) if s_ == 1 else framesteps.expand_rows(stageio.chain_poses(rel, Tr), n, s_))
-        if args.matchability:
-            from caelo import evaluate as ev
-            ev.save_matchability(framesteps.step_path(args.matchability, s_), nin, npairs, its)
-        print("step %d: %d pairs (%d solved) on %d-d descriptors -> %s" % (s_, len(rel), int(np.sum(ok)), src.dim, framesteps.step_path(args.out, s_)))
+    for s_, r in res.items():
+        _write_step(args, s_, n, Tr, *r, what=" on %d-d descriptors" % src.dim)
     print("%d frames in %.2f s (reading key points and descriptors included)" % (n, dt))
 
 
@@ -643,18 +632,14 @@ def main():
             rank, len(tie_log), sum(n for _, n in tie_log), [f for f, _ in tie_log][:20]), file=sys.stderr)
     if world > 1:   # the pair that straddles the rank boundary: ONE all-gather of the boundary rows
         gathered = cdist.all_gather_boundary(last.rows)
-        if rank > 0:
-            prev = FrameFeatures.from_rows(gathered[rank - 1])
-            bd = ransac_draws(args.seed_base + lo - 1)
-            if args.no_certify:
-                r = eng.pose_result(eng.match_pose(prev, first, torch.from_numpy(bd).to(eng.device))[0])
-            else:   # exact like every other pair
-                r = _ffi.PoseResult.from_buffer_copy(eng.match_pose_exact(prev, first, torch.from_numpy(bd).to(eng.device), bd)[0].tobytes())
-            row = np.r_[np.array(r.R, np.float32), np.array(r.T, np.float32)][None]
-            rel = np.concatenate([row, rel]); ok = np.r_[bool(r.success), ok]; thr = np.r_[np.float32(r.threshold), thr]
-            nin = np.r_[np.int32(r.n_inliers), nin]
+        if rank > 0:   # (exact unless --no-certify, like every other pair)
+            both = torch.stack([gathered[rank - 1], first.rows])
+            n_key = both[:, :, 63].sum(dim=1).round().to(torch.int32)   # (as FrameFeatures.from_rows counts them)
+            raw = eng.register_pairs(both, n_key, [(0, 1)], [args.seed_base + lo - 1], certify=not args.no_certify).results
+            r1, o1, t1, n1 = _parse_poses(raw, 1)
+            rel = np.concatenate([r1, rel]); ok = np.r_[o1, ok]; thr = np.r_[t1, thr]; nin = np.r_[n1, nin]
             if records is not None:
-                records.insert(0, (np.array([r.iterations], np.int32), np.array([r.n_pairs], np.int32)))
+                records.insert(0, _parse_records(raw, 1))
         cols = [rel, ok, thr, nin]
         if records is not None:   # (two more columns: small integers, exact in float32)
             cols += [np.concatenate([a for a, _ in records]) if records else np.zeros(0), np.concatenate([b for _, b in records]) if records else np.zeros(0)]
@@ -675,22 +660,13 @@ def main():
     dt = time.time() - t0
     if rank == 0:
         if registrar is not None:
-            rel, ok, nin, np_1, it_1 = stepper.step_results(1)
+            rel, ok, nin, np_c, it_c = stepper.step_results(1)
             thr = np.full(len(rel), args.inlier_threshold, np.float32)
-            records = [(it_1, np_1)] if records is not None else None
-        poses = stageio.chain_poses(rel, Tr)
-        stageio.write_poses(args.out, poses)
-        if records is not None:
-            from caelo import evaluate as ev
-            ev.save_matchability(args.matchability, nin, np.concatenate([b for _, b in records]), np.concatenate([a for a, _ in records]))
+            records = [(it_c, np_c)] if records is not None else None
+        np_1, it_1 = (np.concatenate([b for _, b in records]), np.concatenate([a for a, _ in records])) if records is not None else (None, None)
+        _write_step(args, 1, n, Tr, rel, ok, nin, np_1, it_1, say=False)   # (step 1's lines, one per pair, follow the other steps')
         for s_ in ([s_ for s_ in stepper.steps if s_ != 1] if stepper is not None else []):
-            rel_s, ok_s, nin_s, np_s, it_s = stepper.step_results(s_)
-            assert len(rel_s) == len(framesteps.step_pairs(n, s_)), "step %d: %d pairs registered, %d scheduled" % (s_, len(rel_s), len(framesteps.step_pairs(n, s_)))
-            stageio.write_poses(framesteps.step_path(args.out, s_), framesteps.expand_rows(stageio.chain_poses(rel_s, Tr), n, s_))
-            if args.matchability:
-                from caelo import evaluate as ev
-                ev.save_matchability(framesteps.step_path(args.matchability, s_), nin_s, np_s, it_s)
-            print("step %d: %d pairs (%d solved) -> %s" % (s_, len(rel_s), int(np.sum(ok_s)), framesteps.step_path(args.out, s_)))
+            _write_step(args, s_, n, Tr, *stepper.step_results(s_))
         for i in range(len(rel) if len(rel) <= 200 else 0):
             print("%06d-%06d ok=%d thr=%.1f inliers=%4d T=[% .3f % .3f % .3f]" % (i, i + 1, ok[i], thr[i], nin[i], rel[i, 9], rel[i, 10], rel[i, 11]))
         print("%d frames, %d pairs on %d GPU(s) in %.2f s (%.1f frames/s incl. scan loading / synthesis, upload and read-back; %d of %d poses solved) -> %s" % (

@@ -5,7 +5,7 @@ Lane l of a wavefront derives trial0 + (l & (PW - 1)); PW / 4 scoring passes of 
 500 does not divide by 64, the last workgroup holds 52 and its last wavefront 4; at four, the last wavefront of the last workgroup holds
 none.  A call of fewer than four pairs runs four per wavefront (the shortest launch), a call of four or more sixteen (a quarter of the
 wavefronts): the single calls below (Engine.match_pose, match_pose_exact, ransac) pin the former, the table of all seven sets through
-caelo_register_pairs the latter and the `_tab` kernels, and the two leave the same records and results.
+caelo_register_pairs (a set per slice of the table) the latter, and the two leave the same records and results.
 
 Crafted pair sets of N in {5, 63, 64, 65, 1000, 1024} key points: seeded descriptors that match one to one, a known rigid motion on about
 two thirds of the pairs (so that about a fifth of the 4-samples are all inliers and reach leastInliers) and outliers on the rest; one set
@@ -271,7 +271,7 @@ def test_rank_deficient_samples(run, name):
 
 
 def test_table_of_seven_scores_sixteen_per_wavefront(engine, run, parent_records):
-    """All seven sets as ONE table (caelo_register_pairs: the `_tab` kernels, sixteen hypotheses per wavefront) leave the records, the
+    """All seven sets as ONE table (caelo_register_pairs: a set per slice, sixteen hypotheses per wavefront) leave the records, the
     kernels' own results and the masks of the seven single calls (four per wavefront)."""
     from caelo import _ffi
     cs = [run(name) for name in CASES]

@@ -93,10 +93,12 @@ class _StubEngine:
 
     def __init__(self):
         self.calls = []
+        self.desc_frames = []      # per call: None, or the frame markers of (the rows window, the desc window)
 
-    def register_pairs(self, rows, n_key, pairs, seeds, certify=True):
+    def register_pairs(self, rows, n_key, pairs, seeds, certify=True, desc=None):
         import collections
         assert rows.shape[0] == n_key.shape[0] and len(pairs) == len(seeds)
+        self.desc_frames.append(None if desc is None else ([int(v) for v in rows[:, 0, 0]], [int(v) for v in desc[:, 0, 0]]))
         res = np.zeros(len(pairs), dtype=_ffi.POSE_DTYPE)
         for q, ((a, b), seed) in enumerate(zip(pairs, seeds)):
             assert 0 <= a < rows.shape[0] and 0 <= b < rows.shape[0], "table index outside the resident window"
@@ -141,3 +143,32 @@ def test_step_registrar_carries_rows_and_splits_ranks(chunk, world):
         want = fs.step_pairs(n, s)
         assert len(rel) == len(want) and (npairs == 100).all()
         assert [(int(r[0]), int(r[1])) for r in rel] == want and [int(r[9]) for r in rel] == fs.step_seeds(n, s, seed_base)
+
+
+@pytest.mark.parametrize("chunk", [4, 7, 23])
+@pytest.mark.parametrize("steps", [[1, 5], [5, 1]])
+def test_step_registrar_with_descriptors_registers_step_one_too(steps, chunk):
+    """StepRegistrar(step_one=True).push(c0, rows, n_key, desc) -- what run_sequence.run_desc does: over 23 frames every pair of steps
+    1 and 5 is registered exactly once and in step order, pair k with seed_base + k, from the right two frames; every table index
+    lies inside the window handed over (the stub refuses others), and row i of the descriptor window is the frame of row i of the
+    rows window.  A chunk of 4 is smaller than the largest step: the carried window then spans more than one earlier chunk."""
+    import torch
+    n, seed_base = 23, 300
+    eng = _StubEngine()
+    reg = fs.StepRegistrar(eng, steps, seed_base, True, 0, step_one=True)
+    assert reg.steps == steps and reg.m == 5
+    for c0 in range(0, n, chunk):
+        b = _batch(c0, min(n, c0 + chunk))
+        desc = torch.zeros((b.k, 1024, 32))
+        desc[:, 0, 0] = b.rows[:, 0, 0]
+        reg.push(c0, b.rows, b.n_key, desc)
+    assert eng.calls and all(w <= 5 + chunk for w, _ in eng.calls)
+    assert all(d is not None and d[0] == d[1] and d[0] == list(range(d[0][0], d[0][0] + len(d[0]))) for d in eng.desc_frames)
+    assert sum(len(pairs) for _, pairs in eng.calls) == sum(len(fs.step_pairs(n, s)) for s in steps)      # exactly once
+    for s in steps:
+        rel, ok, nin, npairs, its = reg.step_results(s)          # (pack_results asserts the pair numbers 0 .. p - 1, each once)
+        want = fs.step_pairs(n, s)
+        assert len(rel) == len(want) and (npairs == 100).all()
+        assert [(int(r[0]), int(r[1])) for r in rel] == want and [int(r[9]) for r in rel] == fs.step_seeds(n, s, seed_base)
+        ks = np.concatenate([k for k, _ in reg.results[s]])
+        assert ks.tolist() == list(range(len(want)))              # registered in step order, chunk after chunk
