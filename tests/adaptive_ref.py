@@ -10,6 +10,9 @@ Beside the result every run reports how close it came to a decision that roundin
                      alone and that a trial count can reach (100 < N <= 10 001): only such an N is ever compared with a trial
                      count it could be mistaken about (a larger N ends no walk before the limit does, a smaller one is 100)
 The tests assert margins on these for their cases before they compare anything with the library.
+
+Two registries of inputs: cases() (drawn at random) and, further down, the edge cases -- walks planted to stop at the kernel's chunk
+and limit edges, residuals known to the bit around the threshold, degenerate and non-finite triples, the sample rule's edge draws.
 """
 import functools
 
@@ -229,3 +232,294 @@ def compare(record, mask, name):
     Rt = ref["Rt"] if ref["Rt"] is not None else np.c_[np.eye(3), np.zeros(3)]
     return max(np.abs(record["R"].reshape(3, 3) - Rt[:, :3]).max(), np.abs(record["T"] - Rt[:, 3]).max(),
                np.abs(record["R_ransac"].reshape(3, 3) - ref["Rt_ransac"][:, :3]).max(), np.abs(record["T_ransac"] - ref["Rt_ransac"][:, 3]).max())
+
+
+# ---- the edge cases: walks steered to the kernel's chunk, limit and threshold edges -------------------------------------------------
+# (a registry of their own: cases() above and the tables measured on it stay as they are)
+
+CHUNK = 128            # the kernel scores this many trials ahead of the walk (csrc/adaptive.hip AD_C)
+TOP = 1.0 - 2.0 ** -53
+IDENTITY = np.c_[np.eye(3), np.zeros(3)]
+
+
+def trials_needed(c, n):
+    """ransac.m's N for a best trial with c of n inliers, before the clamp max(N, 100)."""
+    p_no = min(1.0 - EPS, max(EPS, 1.0 - (c / n) ** 3))
+    return np.log(1.0 - 0.99) / np.log(p_no)
+
+
+@functools.lru_cache(maxsize=None)
+def _trials_needed_table(n_hi):
+    """N[n, c] for 3 <= c < n <= n_hi (NaN elsewhere)."""
+    n, c = np.meshgrid(np.arange(n_hi + 1, dtype=np.float64), np.arange(n_hi + 1, dtype=np.float64), indexing="ij")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        p_no = np.minimum(1.0 - EPS, np.maximum(EPS, 1.0 - (c / n) ** 3))
+        N = np.log(1.0 - 0.99) / np.log(p_no)
+    N[(c < 3) | (c >= n)] = np.nan
+    return N
+
+
+def find_nc(k, n_lo=64, n_hi=1024):
+    """-> (n, c, N): the pair n_lo <= n <= n_hi, 3 <= c < n whose N lies in (k - 1, k) farthest from both ends (the first such pair in
+    the order of n, then c).  None when the enumeration finds no pair."""
+    N = _trials_needed_table(1024)[n_lo:n_hi + 1]
+    margin = np.where((N > k - 1) & (N < k), np.minimum(N - (k - 1), k - N), -1.0)
+    i, c = np.unravel_index(int(np.argmax(margin)), margin.shape)
+    if margin[i, c] < 0:
+        return None
+    n = n_lo + int(i)
+    return n, int(c), trials_needed(int(c), n)
+
+
+def _sv_gaps(x, y, idx):
+    """(S3 - S4) / S1 of estimate_rt's B for many triples at once: x, y [3, n], idx [k, 3] -> [k]."""
+    xs, ys = x.T[idx], y.T[idx]                                # [k, 3, 3] (triple, point, axis)
+    xz, yz = xs - xs.sum(axis=1, keepdims=True) / 3, ys - ys.sum(axis=1, keepdims=True) / 3
+    d, s = yz - xz, yz + xz
+    A = np.zeros(idx.shape + (4, 4))
+    A[..., 0, 1:], A[..., 1:, 0] = d, -d
+    A[..., 1, 2], A[..., 1, 3], A[..., 2, 1], A[..., 2, 3], A[..., 3, 1], A[..., 3, 2] = -s[..., 2], s[..., 1], s[..., 2], -s[..., 0], -s[..., 1], s[..., 0]
+    S = np.linalg.svd(np.einsum("kiab,kiac->kbc", A, A), compute_uv=False)
+    return (S[:, 2] - S[:, 3]) / S[:, 0]
+
+
+def planted(n, c, good_at, seed):
+    """A walk that stops where it is told to: c of the n pairs are exact inliers (x1 = R x2 + T, no noise), the others lie hundreds
+    of metres away in z, and the draw table is filled by rejection so that trial t samples an all-inlier triple if and only if
+    t is in ``good_at`` (every other trial samples at least one outlier and scores a handful).  Triples whose (S3 - S4) / S1 is below
+    1e-4 are rejected as well (near-collinear outlier triples otherwise reach 3e-6).  -> (x1, x2, draws, inlier mask [n] u8)."""
+    rng = np.random.RandomState(seed)
+    x2 = rng.uniform(-40.0, 40.0, (n, 3)) * np.array([1.0, 1.0, 0.1])
+    R, T = random_rigid(rng)
+    x1 = (R @ x2.T).T + T
+    inl = np.ones(n, bool)
+    inl[rng.permutation(n)[:n - c]] = False
+    far = np.flatnonzero(~inl)
+    x1[far, 2] += rng.uniform(200.0, 800.0, len(far)) * rng.choice([-1.0, 1.0], len(far))
+    x, y = x1.T, x2.T
+    good = np.zeros(MAX_TRIALS + 1, bool)
+    good[list(good_at)] = True
+    draws = np.empty((MAX_TRIALS + 1, 3))
+    todo = np.arange(MAX_TRIALS + 1)
+    while len(todo):   # rejection, a round over every trial still open
+        u = rng.random_sample((max(len(todo), 4096), 3))
+        idx = np.array([sample_indices(v, n) for v in u])
+        all_in, determined = inl[idx].all(axis=1), _sv_gaps(x, y, idx) >= 1e-4
+        ok, bad = np.flatnonzero(all_in & determined), np.flatnonzero(~all_in & determined)
+        open_good, open_bad = todo[good[todo]], todo[~good[todo]]
+        k_good, k_bad = min(len(open_good), len(ok)), min(len(open_bad), len(bad))
+        draws[open_good[:k_good]], draws[open_bad[:k_bad]] = u[ok[:k_good]], u[bad[:k_bad]]
+        todo = np.r_[open_good[k_good:], open_bad[k_bad:]]
+    return np.ascontiguousarray(x1), np.ascontiguousarray(x2), draws, inl.astype(np.uint8)
+
+
+# name -> (where N has to lie: ("window", k, n_lo, n_hi) = in (k - 1, k) by find_nc | ("nc", n, c) = as given, good_at, seed,
+#          expected (trials, best_trial, status, n_inliers or None = c))
+PLANTED = {
+    "stop_128_n_small": (("window", 128, 65, 127), (0,), 1, (128, 0, 0, None)),             # exactly one chunk; a partial last wavefront
+    "stop_128_n_large": (("window", 128, 1000, 1024), (0,), 2, (128, 0, 0, None)),
+    "stop_129": (("window", 129, 64, 1024), (0,), 3, (129, 0, 0, None)),                     # one trial of chunk 2
+    "stop_256": (("window", 256, 64, 1024), (0,), 4, (256, 0, 0, None)),
+    "stop_257": (("window", 257, 64, 1024), (0,), 5, (257, 0, 0, None)),
+    "slot_63": (("nc", 200, 100), (63,), 6, (100, 63, 0, None)),                              # N = 100 after the clamp
+    "slot_64": (("nc", 200, 100), (64,), 7, (100, 64, 0, None)),
+    "slot_127": (("nc", 200, 100), (127,), 8, (128, 127, 0, None)),
+    "slot_128": (("nc", 200, 100), (128,), 9, (129, 128, 0, None)),
+    "late_good": (("nc", 200, 100), (200,), 10, (201, 200, 0, None)),                         # N <= trials as soon as it is found
+    "tie_across_chunks": (("window", 132, 64, 1024), (5, 130), 11, (132, 130, 0, None)),
+    "tie_past_the_stop_in_chunk": (("window", 130, 64, 1024), (5, 130), 12, (130, 5, 0, None)),      # trial 130 was computed: it must not win
+    "tie_first_slot_past_the_stop": (("window", 128, 64, 1024), (0, 128), 13, (128, 0, 0, None)),
+    "tie_first_slot_walked": (("window", 129, 64, 1024), (0, 128), 14, (129, 128, 0, None)),
+    "stop_9984": (("window", 9984, 64, 1024), (0,), 15, (9984, 0, 0, None)),                 # the 78 full chunks, the short one not needed
+    "stop_9985": (("window", 9985, 64, 1024), (0,), 16, (9985, 0, 0, None)),                 # the first trial of the 17-trial chunk
+    "last_trial_wins": (("nc", 200, 100), (9999,), 17, (10000, 9999, 0, None)),
+    "one_too_late": (("nc", 200, 100), (10000,), 18, (10000, -1, 1, 0)),
+    "found_yet_limit": (("window", 10001, 64, 1024), (0,), 19, (10000, -1, 1, 0)),           # ransac.m:217-226, though trial 0 was perfect
+}
+
+
+def planted_nc(name):
+    """-> (n, c, N) of a planted case."""
+    where = PLANTED[name][0]
+    if where[0] == "window":
+        return find_nc(*where[1:])
+    return where[1], where[2], trials_needed(where[2], where[1])
+
+
+@functools.lru_cache(maxsize=None)
+def planted_inputs(name):
+    """-> planted(...) of a planted case.  Built once per process."""
+    n, c, _ = planted_nc(name)
+    return planted(n, c, PLANTED[name][1], PLANTED[name][2])
+
+
+# ---- the threshold, exactly ----------------------------------------------------------------------------------------------------------
+def _probe(e):
+    """A pair (x, y) whose residual under the identity is EXACTLY e: y is zero wherever e is not, and x = y + e there."""
+    e = np.asarray(e, np.float64)
+    y = np.where(e == 0.0, np.array([7.25, -3.5, 1.75]), 0.0)
+    return y + e, y
+
+
+def threshold_band(t):
+    """Exact pairs (x == y bit for bit) at the first indices, every draw among them: every trial's model is exactly the identity.  Behind
+    them probe pairs with residual vectors known to the bit, at, just below and just above t, and pairs far out so that N lies in
+    (100, 256), at least 0.1 from an integer.
+    -> (x1, x2, draws, want: the mask np.sqrt(e0*e0 + e1*e1 + e2*e2) < t gives in float64, operations in that order)."""
+    m = 12
+    rng = np.random.RandomState(41)
+    exact = rng.uniform(-40.0, 40.0, (m, 3)) * np.array([1.0, 1.0, 0.3])
+    lo, hi = np.nextafter(t, 0.0), np.nextafter(t, np.inf)
+    es = []
+    for axis in range(3):
+        for v in (t, lo, hi, -t, -lo, -hi):
+            e = np.zeros(3)
+            e[axis] = v
+            es.append(e)
+    if t == 5.0:
+        es += [np.array([3.0, 4.0, 0.0]), np.array([3.0, np.nextafter(4.0, 0.0), 0.0]), np.array([0.0, np.nextafter(3.0, 0.0), 4.0]),
+               np.array([np.nextafter(3.0, np.inf), 0.0, 4.0]), np.array([4.0, 0.0, np.nextafter(3.0, 0.0)])]
+    for k in range(1, 7):
+        for sign in (-1.0, 1.0):
+            e = np.zeros(3)
+            e[k % 3] = t * (1.0 + sign * k * 2.0 ** -53)
+            es.append(e)
+            e = np.zeros(3)                          # the same number of steps of the format itself
+            v = t
+            for _ in range(k):
+                v = np.nextafter(v, np.inf if sign > 0 else 0.0)
+            e[(k + 1) % 3] = v
+            es.append(e)
+    es = np.array(es)
+    want_probe = np.array([bool(np.sqrt(e[0] * e[0] + e[1] * e[1] + e[2] * e[2]) < t) for e in es])
+    count = m + int(want_probe.sum())
+    pad = 0
+    while True:   # pairs far out until N is in (100, 256) and away from an integer
+        N = trials_needed(count, m + len(es) + pad)
+        if 100.5 < N < 256 and abs(N - np.round(N)) > 0.1:
+            break
+        pad += 1
+    n = m + len(es) + pad
+    x1, x2 = np.zeros((n, 3)), np.zeros((n, 3))
+    x1[:m], x2[:m] = exact, exact
+    for i, e in enumerate(es):
+        x1[m + i], x2[m + i] = _probe(e)
+        assert np.array_equal(x1[m + i] - x2[m + i], e)
+    far = rng.uniform(-40.0, 40.0, (pad, 3))
+    x1[m + len(es):], x2[m + len(es):] = far + np.array([500.0, 0.0, 0.0]), far
+    draws = base_draws(7) * np.array([m / n, (m - 1) / (n - 1), (m - 2) / (n - 2)])
+    assert all(max(sample_indices(u, n)) < m for u in draws)
+    want = np.r_[np.ones(m, bool), want_probe, np.zeros(pad, bool)].astype(np.uint8)
+    return x1, x2, draws, want
+
+
+# ---- degenerate and non-finite triples -----------------------------------------------------------------------------------------------
+def repeat_draw(u):
+    return np.ascontiguousarray(np.tile(np.asarray(u, np.float64), (MAX_TRIALS + 1, 1)))
+
+
+def degenerate_inputs():
+    """name -> (x1, x2, draws): small hand-made clouds whose every trial samples the pairs 0, 1, 2 (u = 0)."""
+    d = repeat_draw((0.0, 0.0, 0.0))
+    out = {}
+    # all three sampled pairs are ONE pair: the 4 x 4 matrix is exactly zero
+    x = np.array([[1.5, -2.25, 0.5]] * 3 + [[30.0, 4.0, 1.0], [-20.0, 9.0, 2.0]])
+    y = np.array([[0.25, 4.0, -1.0]] * 3 + [[-7.0, 11.0, 0.5], [13.0, -8.0, 1.5]])
+    out["one_pair_thrice"] = (x, y, d)
+    # two of the three share one y with different x (several points of frame a matched to ONE point of frame b)
+    rs = np.random.RandomState(61)
+    y = rs.uniform(-20.0, 20.0, (6, 3))
+    R, T = random_rigid(rs)
+    y[1] = y[0] + np.array([0.2, -0.1, 0.1])
+    x = (R @ y.T).T + T
+    y[1] = y[0]          # (the true motion leaves 0.25 m at pair 1 and nothing elsewhere: the least-squares fit to the triple no more)
+    out["shared_y"] = (np.ascontiguousarray(x), y, d)
+    # an exactly collinear rigid triple: the rotation about the line is open
+    y = rs.uniform(-20.0, 20.0, (7, 3))
+    p, v = np.array([1.0, -2.0, 0.5]), np.array([0.5, 0.25, -1.0])
+    y[:3] = p + np.array([[-2.0], [0.5], [3.0]]) * v          # (exact in float64)
+    R = quat2rot(np.array([0.5, 0.5, 0.5, 0.5]))              # an exact rotation: a cyclic permutation of the axes
+    x = (R @ y.T).T + np.array([2.0, -1.0, 0.25])
+    out["collinear_rigid"] = (np.ascontiguousarray(x), y, d)
+    return out
+
+
+def nonfinite_inputs():
+    """name -> (x1, x2, draws, bad index): exact rigid pairs of which ONE holds a NaN or an infinity, draws from base_draws."""
+    out = {}
+    for name, n, bad, side, axis, value in (("nan_x_first", 8, 0, 0, 1, np.nan), ("inf_y_last", 8, 7, 1, 0, np.inf),
+                                            ("minus_inf_x_middle", 6, 3, 0, 2, -np.inf), ("nan_y_second_wavefront", 65, 64, 1, 2, np.nan)):
+        rs = np.random.RandomState(70 + n + bad)
+        y = rs.uniform(-40.0, 40.0, (n, 3)) * np.array([1.0, 1.0, 0.1])
+        R, T = random_rigid(rs)
+        x = (R @ y.T).T + T
+        (x, y)[side][bad, axis] = value
+        out[name] = (np.ascontiguousarray(x), np.ascontiguousarray(y), base_draws(0), bad)
+    return out
+
+
+def nonfinite_expected(name):
+    """The walk by hand: a trial that samples the bad pair scores 0, every other trial all the n - 1 finite pairs (they are exact
+    inliers): N is 100 after the clamp, the best trial is the last of the first 100 that does not sample the bad pair."""
+    x1, _, draws, bad = nonfinite_inputs()[name]
+    n = len(x1)
+    clean = [t for t in range(100) if bad not in sample_indices(draws[t], n)]
+    want = np.ones(n, np.uint8)
+    want[bad] = 0
+    assert trials_needed(n - 1, n) < 100 and clean
+    return dict(trials=100, best_trial=clean[-1], status=0, n_inliers=n - 1), want
+
+
+def sample_rule_inputs(n):
+    """-> (x1, x2, [u]): a noisy cloud whose every triple gives another motion, and the draws every trial repeats: the rule's edges
+    (u = 0 and the largest draw there is, u = 1 - 2^-53) and a few in between."""
+    x1, x2 = make_pair(900 + n, n, 1.0, noise=0.3)
+    rs = np.random.RandomState(50 + n)
+    return x1, x2, [np.zeros(3), np.full(3, TOP), np.array([TOP, 0.0, TOP]), np.array([0.0, TOP, 0.0])] + list(rs.random_sample((4, 3)))
+
+
+@functools.lru_cache(maxsize=None)
+def edge_cases():
+    """name -> (x1, x2, draws, threshold, expected facts, expected mask or None).  Built once per process."""
+    out = {}
+    for name, (_, good_at, seed, (trials, best, status, n_in)) in PLANTED.items():
+        n, c, _ = planted_nc(name)
+        x1, x2, d, inl = planted_inputs(name)
+        want = inl if status == 0 else np.zeros(n, np.uint8)
+        out[name] = (x1, x2, d, THRESHOLD, dict(trials=trials, best_trial=best, status=status, n_inliers=c if n_in is None else n_in), want)
+    return out
+
+
+@functools.lru_cache(maxsize=None)
+def edge_reference(name):
+    """-> (result dict of ransacfit_rt, stats) of an edge case.  Computed once per process."""
+    x1, x2, d, t = edge_cases()[name][:4]
+    stats = new_stats()
+    return ransacfit_rt(x1, x2, t, d, stats), stats
+
+
+def compare_edge(record, mask, name):
+    """compare() for an edge case."""
+    ref, _ = edge_reference(name)
+    n = len(edge_cases()[name][0])
+    want = np.zeros(n, np.uint8)
+    want[ref["inliers"]] = 1
+    got = (int(record["trials"]), int(record["best_trial"]), int(record["status"]), int(record["n_inliers"]), int(record["n_pairs"]))
+    assert got == (ref["trials"], ref["best_trial"], ref["status"], len(ref["inliers"]), n), (name, got)
+    assert np.array_equal(np.asarray(mask, np.uint8), want), name
+    return rt_error(record, ref["Rt"], ref["Rt_ransac"])
+
+
+def rt_error(record, Rt, Rt_ransac):
+    """The worst absolute difference of a library record's R, T, R_ransac, T_ransac from two [3, 4] matrices."""
+    return max(np.abs(record["R"].reshape(3, 3) - Rt[:, :3]).max(), np.abs(record["T"] - Rt[:, 3]).max(),
+               np.abs(record["R_ransac"].reshape(3, 3) - Rt_ransac[:, :3]).max(), np.abs(record["T_ransac"] - Rt_ransac[:, 3]).max())
+
+
+def same_walk(a, amask, b, bmask, tol=1e-12):
+    """Two library results (device and host twin): the integers and the mask EQUAL, R_ransac and T_ransac within tol."""
+    for f in ("trials", "best_trial", "status", "n_inliers", "n_pairs"):
+        assert int(a[f]) == int(b[f]), (f, int(a[f]), int(b[f]))
+    assert np.array_equal(amask, bmask)
+    diff = np.abs(np.r_[a["R_ransac"], a["T_ransac"]] - np.r_[b["R_ransac"], b["T_ransac"]])
+    assert not np.isnan(diff).any() and diff.max() <= tol, diff.max()
