@@ -139,6 +139,7 @@ SIGNATURES = [
     ("caelo_voxelize", c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     ("caelo_voxelize_fast", c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_vp]),
     ("caelo_voxmap_dump", c_int, [c_vp, c_vp, c_int, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    ("caelo_voxmap_counts", c_int, [c_vp, c_vp, c_vp, c_vp]),
     ("caelo_voxmap_export", c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
     ("caelo_voxmap_order", c_int, [c_vp, c_vp, c_int, c_vp]),
     ("caelo_voxmap_from_lists", c_int, [c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp]),

@@ -1301,6 +1301,12 @@ class Engine:
         vox = (base[br] + np.stack([x, y, z], 1)).astype(np.int32)
         return vox[np.lexsort((vox[:, 2], vox[:, 1], vox[:, 0]))]
 
+    def voxmap_counts(self, vmap):
+        """caelo_voxmap_counts: the map's build counters -> int32 [8] (host; synchronises)."""
+        out = self.empty((8,), torch.int32)
+        _ffi.check(self.lib.caelo_voxmap_counts(self.ctx, vmap.h, _ptr(out), self.stream))
+        return out.cpu().numpy()
+
     def voxmap_export(self, vmap, capacity):
         outs = [self.empty((capacity, 3), torch.int16) for _ in range(3)]
         counts = self.empty((3,), torch.int64)

@@ -261,6 +261,9 @@ int ring_keypoints_launch(const float *ring, int ring_w, int ring_c, int dist_c,
 int ring_project_set(caelo_ctx *c, const caelo_frame_set &fs, hipStream_t s);
 int ring_respond_set(caelo_ctx *c, const caelo_frame_set &fs, int in_w, int in_c, hipStream_t s, int row0, int rows);
 int ring_keypoints_set(const caelo_frame_set &fs, int ring_w, int ring_c, int cnt_w, hipStream_t s);
+int ring_keypoints_select_set(const caelo_frame_set &fs, int ring_w, int ring_c, hipStream_t s);  // its last two launches: gather, emit
+// fast voxel build + ring image -> response -> key points of a set on ONE stream, the two chains sharing launches (ring.hip)
+int front_fused_set(caelo_ctx *c, caelo_voxmap *const *maps, const caelo_frame_set &fs, hipStream_t s);
 void vox_clear_items(caelo_voxmap *m, int level, caelo_clear_list &list);  // 0 brick keys only, 1 + scale-0 first-touch table, 2 everything
 // clear for a fused build: if the map holds nothing but the previous fused build, its listed bricks are wiped by a
 // kernel launched here (before the caller's clear list runs) and only the small scale-2 table + counters join the list

@@ -243,28 +243,33 @@ int extract_front_set(const caelo_extract_args *args, int n, hipStream_t s, hipS
     }
     if (!exact_vox && (rc = vox_clear_for_fast_build_set(maps, n, cl, s))) return rc;  // wipes the previous frames' bricks only
     if ((rc = caelo_clear_many_set(cl, n, s))) return rc;
-    // The voxel map only needs the points: with a second stream (the frame pipeline passes one when the runtime has hardware
-    // queues to spare) it is built beside the ring image -> response -> key points chain; both meet before the patch gather.
-    hipStream_t sv = s_vox ? s_vox : s;
-    if (s_vox) {
-        CAELO_HIP(hipEventRecord(ev_fork, s));
-        CAELO_HIP(hipStreamWaitEvent(s_vox, ev_fork, 0));
-    }
-    // ---- voxel map
-    if (exact_vox) rc = vox_build_set(maps, fs, exact_pat, sv);
-    else rc = vox_build_fast_set(maps, fs, sv);
-    if (rc) return rc;
-    if (s_vox) CAELO_HIP(hipEventRecord(ev_join, s_vox));
-    // ---- ring image, response, keypoints (or the caller's key points, checked)
-    if (given) {
-        if ((rc = given_keypts_set(fs, s))) return rc;
+    // The voxel map only needs the points: it is built beside the ring image -> response -> key points chain, and both meet before
+    // the patch gather.  Without a second stream the fast build and the detector's chain share launches (front_fused_set); with
+    // one (the frame pipeline passes it when the runtime has hardware queues to spare) each chain keeps its own kernels.
+    if (!exact_vox && !given && !s_vox) {
+        if ((rc = front_fused_set(args[0].ctx, maps, fs, s))) return rc;
     } else {
-        if ((rc = ring_project_set(args[0].ctx, fs, s))) return rc;
-        // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
-        if ((rc = ring_respond_set(args[0].ctx, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52))) return rc;
-        if ((rc = ring_keypoints_set(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W, s))) return rc;
+        hipStream_t sv = s_vox ? s_vox : s;
+        if (s_vox) {
+            CAELO_HIP(hipEventRecord(ev_fork, s));
+            CAELO_HIP(hipStreamWaitEvent(s_vox, ev_fork, 0));
+        }
+        // ---- voxel map
+        if (exact_vox) rc = vox_build_set(maps, fs, exact_pat, sv);
+        else rc = vox_build_fast_set(maps, fs, sv);
+        if (rc) return rc;
+        if (s_vox) CAELO_HIP(hipEventRecord(ev_join, s_vox));
+        // ---- ring image, response, keypoints (or the caller's key points, checked)
+        if (given) {
+            if ((rc = given_keypts_set(fs, s))) return rc;
+        } else {
+            if ((rc = ring_project_set(args[0].ctx, fs, s))) return rc;
+            // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
+            if ((rc = ring_respond_set(args[0].ctx, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52))) return rc;
+            if ((rc = ring_keypoints_set(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W, s))) return rc;
+        }
+        if (s_vox) CAELO_HIP(hipStreamWaitEvent(s, ev_join, 0));
     }
-    if (s_vox) CAELO_HIP(hipStreamWaitEvent(s, ev_join, 0));
     // ---- patches
     // equal patches are encoded once (dedup.hip): k_patches enters every patch into the hash table, the tables land
     // behind the frame's bits

@@ -158,9 +158,10 @@ static int proj_edge_table(double **out) {
 }
 
 // every kernel below: blockIdx.z = frame of the set (caelo_internal.h)
-__global__ void __launch_bounds__(256) k_project_points(const caelo_frame_set fs, ProjConst k) {
-    const caelo_frame_dev &F = fs.f[blockIdx.z];
-    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+// The kernels that have a partner in the fused front launches further down (k_front_*) are bodies, one definition each, behind a
+// stand-alone kernel and a fused one: a body is told which workgroup of its role it is instead of reading blockIdx itself.
+static __device__ __forceinline__ void project_points_body(const caelo_frame_dev &F, const ProjConst &k, const unsigned int block) {
+    const int64_t i = (int64_t)block * blockDim.x + threadIdx.x;
     if (i >= F.n) return;
     int32_t *const winner = F.winner, *const counter = F.counter, *const status = F.status;
     const float4 p = ((const float4 *)F.pc)[i];
@@ -198,12 +199,15 @@ __global__ void __launch_bounds__(256) k_project_points(const caelo_frame_set fs
                                                                                       //  a pixel is occupied iff it has a winner)
 }
 
-__global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) {
-    const caelo_frame_dev &F = fs.f[blockIdx.z];
+__global__ void __launch_bounds__(256) k_project_points(const caelo_frame_set fs, ProjConst k) {
+    project_points_body(fs.f[blockIdx.z], k, blockIdx.x);
+}
+
+static __device__ __forceinline__ void ring_fill_body(const caelo_frame_dev &F, const unsigned int block) {
     const float4 *__restrict__ pc = (const float4 *)F.pc;
     const int32_t *__restrict__ winner = F.winner;
     float *__restrict__ ring = F.ring;
-    const int pix = blockIdx.x * blockDim.x + threadIdx.x;
+    const int pix = block * blockDim.x + threadIdx.x;
     if (pix >= CAELO_RING_H * CAELO_RING_W) return;
     const int w = winner[pix];
     float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
@@ -229,7 +233,7 @@ __global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) {
     // are four cache lines; one atomic per wave and word, ~2000 per frame, cost the kernel 3 us of 9.5).
     // (The image's last workgroup is cut short by the return above; it lies below the net rows and leaves here before the barriers.)
     unsigned long long *const kmap = F.kp_elig;
-    const int wg0 = blockIdx.x * blockDim.x;
+    const int wg0 = block * blockDim.x;
     if (!kmap || wg0 >= CAELO_NET_H * CAELO_RING_W) return;
     __shared__ unsigned long long s_rows[2];
     if (threadIdx.x < 2) s_rows[threadIdx.x] = 0ull;
@@ -262,6 +266,8 @@ __global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) {
     caelo_lds_barrier();
     if (threadIdx.x < 2 && s_rows[threadIdx.x] != 0ull) atomicOr(&kmap[rw + threadIdx.x], s_rows[threadIdx.x]);   // (a set bit: a net row)
 }
+
+__global__ void __launch_bounds__(256) k_ring_fill(const caelo_frame_set fs) { ring_fill_body(fs.f[blockIdx.z], blockIdx.x); }
 
 static int64_t set_max_points(const caelo_frame_set &fs) {
     int64_t n = 0;
@@ -550,8 +556,12 @@ __device__ __host__ inline unsigned int kp_bin(unsigned int score_bits) {
 #define KS_HR (KS_ROWS + 4)
 #define KS_HC (KS_COLS + 4)
 
-__global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int ring_w, int ring_c, int cnt_w) {
-    const caelo_frame_dev &F = fs.f[blockIdx.z];
+#define KS_TILES_X (CAELO_NET_W / KS_COLS)   // the tiles of a frame: KS_TILES_X x KS_TILES_Y
+#define KS_TILES_Y (48 / KS_ROWS)
+
+// (bx, by): the workgroup's tile
+static __device__ __forceinline__ void kp_score_body(const caelo_frame_dev &F, int ring_w, int ring_c, int cnt_w, const unsigned int bx,
+                                                     const unsigned int by) {
     const float *__restrict__ ring = F.ring;
     const int dist_c = F.dist_c;
     const int32_t *__restrict__ counter = F.counter, *__restrict__ winner = F.winner;  // counter == null: occupied = has a winner
@@ -561,7 +571,7 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     __shared__ float4 sR[KS_HR * KS_HC * 2];
     __shared__ unsigned int sBits[KS_HR][4];   // occupancy of a halo row as bits (68 columns: three words)
     const int tid = threadIdx.x;
-    const int x0 = blockIdx.x * KS_COLS, y0 = 8 + blockIdx.y * KS_ROWS;  // rows 8..55 only
+    const int x0 = bx * KS_COLS, y0 = 8 + by * KS_ROWS;  // rows 8..55 only
     // The rule's conditions are ANDed and the range gate (:197-198) needs nothing but the centre's own ring pixel: it comes first.
     // A tile none of whose centres passes it (k_ring_fill's map: the tile's four rows, its two 32-column blocks; the staged entry
     // points have no map) is left before its halo is staged, and a centre that fails it skips its 24 distances below.  In the fused
@@ -570,7 +580,7 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     static_assert(KS_COLS == 64 && 8 + 48 <= CAELO_NET_H, "a tile spans two map bits of four row words");
     if (const unsigned long long *__restrict__ kmap = F.kp_elig) {
         const unsigned long long m = kmap[y0] | kmap[y0 + 1] | kmap[y0 + 2] | kmap[y0 + 3];
-        if (((m >> (2 * blockIdx.x)) & 3ull) == 0ull) return;
+        if (((m >> (2 * bx)) & 3ull) == 0ull) return;
     }
     // (the centre's ring pixel is requested here, ahead of the halo, and used behind it)
     float pxv[5];
@@ -673,6 +683,10 @@ __global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int 
     }
 }
 
+__global__ void __launch_bounds__(256) k_kp_score(const caelo_frame_set fs, int ring_w, int ring_c, int cnt_w) {
+    kp_score_body(fs.f[blockIdx.z], ring_w, ring_c, cnt_w, blockIdx.x, blockIdx.y);
+}
+
 // ------------------------------------------------------------------------------------------------
 // K4: stable top-(1025) select.  Keys are unique, so "ascending by (score, flat index)" (the stable
 // argsort of :194) is plain ascending key order.  One 1024-thread workgroup:
@@ -743,20 +757,22 @@ static_assert(CAELO_KP_HIST_BINS == 2 * SEL_THREADS, "a thread owns two bins");
 #define KP_STATE_LISTED 1  //   the selection list holds every key from the cut bin upwards
 #define KP_STATE_FALLBACK 2
 
-__global__ void __launch_bounds__(SEL_THREADS) k_kp_hist(const caelo_frame_set fs) {
-    const caelo_frame_dev &F = fs.f[blockIdx.z];
+// block: the workgroup's number among the KP_WGS that histogram
+static __device__ __forceinline__ void kp_hist_body(const caelo_frame_dev &F, const unsigned int block) {
     const int M = *F.cand_count, tid = threadIdx.x;
     if (M <= 1025) return;
     __shared__ unsigned int lh[CAELO_KP_HIST_BINS];
     lh[2 * tid] = 0u;
     lh[2 * tid + 1] = 0u;
     __syncthreads();
-    const int per = (M + KP_WGS - 1) / KP_WGS, i0 = blockIdx.x * per, i1 = min(M, i0 + per);
+    const int per = (M + KP_WGS - 1) / KP_WGS, i0 = block * per, i1 = min(M, i0 + per);
     for (int i = i0 + tid; i < i1; i += SEL_THREADS) atomicAdd(&lh[kp_bin((unsigned int)(F.cand[i] >> 32))], 1u);
     __syncthreads();
-    uint2 *out = (uint2 *)(F.cand + KP_SCRATCH_OFF) + (size_t)blockIdx.x * SEL_THREADS;
+    uint2 *out = (uint2 *)(F.cand + KP_SCRATCH_OFF) + (size_t)block * SEL_THREADS;
     out[tid] = make_uint2(lh[2 * tid], lh[2 * tid + 1]);
 }
+
+__global__ void __launch_bounds__(SEL_THREADS) k_kp_hist(const caelo_frame_set fs) { kp_hist_body(fs.f[blockIdx.z], blockIdx.x); }
 
 // inclusive suffix sum over the 1024 threads of the workgroup (wave shuffles + one LDS hop)
 __device__ inline unsigned int kp_suffix_sum(unsigned int v, unsigned int *s_wave) {
@@ -1009,11 +1025,94 @@ int ring_keypoints_set(const caelo_frame_set &fs, int ring_w, int ring_c, int cn
     CAELO_LAUNCH_CHECK();
     k_kp_hist<<<dim3(KP_WGS, 1, fs.n), SEL_THREADS, 0, s>>>(fs);
     CAELO_LAUNCH_CHECK();
+    return ring_keypoints_select_set(fs, ring_w, ring_c, s);
+}
+
+// the selection behind the partial histograms (front_fused_set launches the score and the histograms itself)
+int ring_keypoints_select_set(const caelo_frame_set &fs, int ring_w, int ring_c, hipStream_t s) {
     k_kp_gather<<<dim3(KP_WGS, 1, fs.n), SEL_THREADS, 0, s>>>(fs);
     CAELO_LAUNCH_CHECK();
     k_kp_emit<<<dim3(SEL_N / 64, 1, fs.n), SEL_THREADS, 0, s>>>(fs, ring_w, ring_c);   // (falls back to the one-workgroup select on > 2048 tied keys)
     CAELO_LAUNCH_CHECK();
     return CAELO_OK;
+}
+
+// ------------------------------------------------------------------------------------------------
+// The front chain without a voxel stream.  The one-pass voxel build (voxel.hip; its bodies: voxel_front.inc) and the ring image ->
+// response -> key point chain above only meet at the patch gather, and both are chains of dependent memory round trips that leave
+// the CUs idle.  Behind one stream they used to be ten launches in a row; here launches of the ring chain carry a body of the build
+// in further workgroups (as k_vox_coarse carries vox_suspects_first).  Every dependency is a launch boundary of that stream
+// (DESIGN.md 5.3 has the table):
+//   k_front_points   vox_points_body           + project_points_body     (both only read the scan)
+//   k_front_coarse   vox_coarse_body (+ first) + ring_fill_body          (the bricks' list | the pixels' winners)
+//   k_respond_mfma   (alone: its 64-thread blocks and its register budget are its own)
+//   k_front_score    vox_coarse2_body          + kp_score_body           (list1 of k_front_coarse | the response)
+//   k_front_hist     vox_suspects_resolve_body + kp_hist_body            (behind coarse2, whose counts it corrects | the candidates)
+// A workgroup's role is a function of blockIdx.x alone, so it is uniform, and a body's early return -- ring_fill_body's for the
+// image's last workgroup comes before its barriers -- is the return of every thread of the workgroup.  The build's workgroups
+// come first in blockIdx.x, the ring chain's behind them: the second role fills the CUs as the first one's tail drains.
+// The grid is sized by the set's largest frame: each body checks its own frame's bounds as it does stand-alone.
+// ------------------------------------------------------------------------------------------------
+#include "voxel_front.inc"
+
+// workgroup `bx` of a launch shared by role 0 (n0 workgroups) and role 1 (n1): role 0's workgroups come first, then role 1's.
+// (Alternating the roles in blockIdx.x was measured and lost: k_front_points 98 us against 62 + 16 for its parts inside the
+// pipeline, the rate 2 % below the parent's where this order is 2 % above it -- profiles/front_fused_times.txt.)
+static __device__ __forceinline__ unsigned int front_role(const unsigned int bx, const unsigned int n0, unsigned int *idx) {
+    *idx = bx < n0 ? bx : bx - n0;
+    return bx < n0 ? 0u : 1u;
+}
+
+#define FILL_WGS ((CAELO_RING_H * CAELO_RING_W + 255) / 256)
+
+// gp: the workgroups either role needs for the set's largest scan
+__global__ void __launch_bounds__(256) k_front_points(const caelo_frame_set fs, const ProjConst k, const unsigned int gp) {
+    const caelo_frame_dev &F = fs.f[blockIdx.z];
+    unsigned int b;
+    if (front_role(blockIdx.x, gp, &b) == 0u) vox_points_body(F, b);
+    else project_points_body(F, k, b);
+}
+
+__global__ void __launch_bounds__(256) k_front_coarse(const caelo_frame_set fs, const unsigned int gp) {
+    const caelo_frame_dev &F = fs.f[blockIdx.z];
+    unsigned int b;
+    if (front_role(blockIdx.x, COARSE_WGS + gp, &b) == 0u) vox_coarse_body(F, b);
+    else ring_fill_body(F, b);
+}
+
+__global__ void __launch_bounds__(256) k_front_score(const caelo_frame_set fs, int ring_w, int ring_c, int cnt_w) {
+    const caelo_frame_dev &F = fs.f[blockIdx.z];
+    unsigned int b;
+    if (front_role(blockIdx.x, COARSE2_WGS, &b) == 0u) vox_coarse2_body(F, b, COARSE2_WGS);
+    else kp_score_body(F, ring_w, ring_c, cnt_w, b % KS_TILES_X, b / KS_TILES_X);
+}
+
+// (one workgroup of 1024 threads resolves: the 4 x 256 of k_vox_suspects_resolve's own launch)
+__global__ void __launch_bounds__(SEL_THREADS) k_front_hist(const caelo_frame_set fs) {
+    const caelo_frame_dev &F = fs.f[blockIdx.z];
+    unsigned int b;
+    if (front_role(blockIdx.x, 1u, &b) == 0u) vox_suspects_resolve_body(F, b, 1u);
+    else kp_hist_body(F, b);
+}
+
+// vox_build_fast_set + ring_project_set + ring_respond_set + ring_keypoints_set of the fused extract, ten launches, in eight.
+// The caller has checked that the scans are float4 rows (ring_fill_body).
+int front_fused_set(caelo_ctx *c, caelo_voxmap *const *maps, const caelo_frame_set &fs, hipStream_t s) {
+    for (int i = 0; i < fs.n; ++i) { maps[i]->lists_valid = false; maps[i]->kd_lists = false; maps[i]->order_tracked = false; }  // until every kernel of the build is enqueued
+    const unsigned gp = (unsigned)((set_max_points(fs) + 255) / 256);
+    k_front_points<<<dim3(2 * gp, 1, fs.n), 256, 0, s>>>(fs, proj_const(c->proj_edge), gp);
+    CAELO_LAUNCH_CHECK();
+    k_front_coarse<<<dim3(COARSE_WGS + gp + FILL_WGS, 1, fs.n), 256, 0, s>>>(fs, gp);
+    CAELO_LAUNCH_CHECK();
+    // (the key point rule reads response rows 8..55 and their 5 x 5 neighbourhoods: rows 6..57 of 64)
+    const int rc = ring_respond_set(c, fs, CAELO_RING_W, CAELO_RING_C, s, 6, 52);
+    if (rc) return rc;
+    k_front_score<<<dim3(COARSE2_WGS + KS_TILES_X * KS_TILES_Y, 1, fs.n), 256, 0, s>>>(fs, CAELO_RING_W, CAELO_RING_C, CAELO_RING_W);
+    CAELO_LAUNCH_CHECK();
+    k_front_hist<<<dim3(1 + KP_WGS, 1, fs.n), SEL_THREADS, 0, s>>>(fs);
+    CAELO_LAUNCH_CHECK();
+    for (int i = 0; i < fs.n; ++i) maps[i]->lists_valid = true;
+    return ring_keypoints_select_set(fs, CAELO_RING_W, CAELO_RING_C, s);
 }
 
 // debug aid: copies the 16 phase timestamps of the last keypoint selection (100 MHz ticks) to the host

@@ -288,6 +288,10 @@ int caelo_voxelize_fast(caelo_ctx *ctx, caelo_voxmap *map, const float *pc, int6
  * then only `capacity` bricks were written).  Diagnostic / test access to the device voxel map. */
 int caelo_voxmap_dump(caelo_ctx *ctx, const caelo_voxmap *map, int scale, uint64_t *keys, uint64_t *bits, int64_t capacity,
                       int32_t *count, void *stream);
+/* The map's build counters, counts8 [8] i32 (device): [0..2] voxels of scales 0, 1, 2 (what the 496-voxel check reads); after a
+ * one-pass build also [4] entries of the scale-0 brick list (holes included), [5] scale-1 bricks listed, [6] points within an
+ * ulp of a voxel face.  Diagnostic / test access. */
+int caelo_voxmap_counts(caelo_ctx *ctx, const caelo_voxmap *map, int32_t *counts8, void *stream);
 /* AllVoxels0/1/2 in the reference's order (first touch; scale 0 block-grouped, Voxel.py:161-165).
  * out [capacity][3] i16 per scale, counts [3] i64 (device).  Valid after caelo_voxelize.  Asynchronous on `stream`: a count
  * above `capacity` means only the first `capacity` voxels of that scale were written (the caller checks after reading counts). */
