@@ -53,9 +53,9 @@ struct caelo_ctx {
     float *enc_w3;   // [27][16][32]
     float *enc_b3;   // [32]
     void *enc_w1f;   // conv1 as k_enc_stage1x's B operand (w1 scattered over the 4^3 receptive field): [k-step 2][n-tile 4][f16 term 2][lane 64] x 16 B
-    void *enc_w2x;   // conv2 as k_enc_stage1x's B operand: [tap row 9][fragment 3][lane 64] x 16 B (f16 terms, enc_stage1x.inc)
-    void *enc_w3x;   // W3 as the conv3 kernel's B operand: [ntile 2][tap pair 14][bf16 split 3][lane 64] x 16 B
-    void *enc_wd1x;  // dense_1 as the dense-1 kernel's B operand: [k-step 64][bf16 split 3][n-tile 13][lane 64] x 16 B
+    void *enc_w2x;   // conv2 as k_enc_stage1x's B operand: [tap row 9][fragment X, Y][lane 64] x 16 B (f16 terms, enc_stage1x.inc)
+    void *enc_w3x;   // W3 as k_enc_conv3's B operand: [ntile 2][tap pair 14][f16 term 2][lane 64] x 16 B (enc_conv3.inc)
+    void *enc_wd1x;  // dense_1 as k_enc_dense1p's B operand: [k-step 64][f16 term 2][n-tile 13][lane 64] x 16 B (enc_dense1.inc)
     float *enc_bd1;  // [208]
     float *enc_wd2;  // [200][20]
     void *enc_wd2q;  // the same as k_enc_head_mfma's B operand: [hidden group 13][n-tile 2][lane 64] x float4, zero padded
@@ -320,9 +320,9 @@ struct caelo_enc_out {
 // input side of a launch set.  dedup = 0: n_patches patches, contiguous at bits.  dedup = 1: n_frames frame buffers
 // (bits + f * frame_stride u64 words: [per_frame][64] patches followed by the frame's caelo_dedup_tables); only the
 // distinct patches of each frame are encoded, into rows f * per_frame + (position in the frame's list), and
-// k_enc_head hands patch p of frame f the result of row f * per_frame + slot_of[p].
-// encoder workspace header: [0] work counter of the per-workgroup stage-1 / conv-2 kernels, [8..15] executed-MFMA count of the
-// last counting launch, [1024..2047] eight per-XCD queue counters of k_enc_stage1x (a 128-byte line each), [2048..3071] the same for
+// k_enc_head_mfma hands patch p of frame f the result of row f * per_frame + slot_of[p].
+// encoder workspace header (bytes): [0] work counter of k_enc_stage1, [3072..4095] executed-MFMA counts of the last counting
+// launch (CAELO_ENC_WS_MFMA), [1024..2047] eight per-XCD queue counters of k_enc_stage1x (a 128-byte line each), [2048..3071] the same for
 // k_enc_conv3 (each kernel zeroes the other's).  Zero between calls.
 #define CAELO_ENC_WS_HEADER 4096
 #define CAELO_ENC_WS_MFMA 3072     // bytes 3072 .. 4095 of the header: stage 1's MFMA counters (profiling launches only)

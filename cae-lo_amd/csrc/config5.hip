@@ -16,24 +16,20 @@
 // Data layout: a patch is 512 u64 words, voxel (ix,iy,iz) at bit (lin & 63) of word (lin >> 6),
 // lin = (ix*32 + iy)*32 + iz; activations are channels-last f32 ([x][y][z][c]) like the 16^3 path.
 //
-// Kernels: all four GEMM-shaped layers run on the f32 matrix cores -- the three conv stages as dense implicit GEMMs
-// over LDS-resident x slabs (k5_conv1pool, k5_conv_mfma), Dense(200) through the 16^3 path's kernel instantiated for
-// K = 16384 (k_enc_dense1<16384>, encoder.hip).  Dense scans leave little of the sparsity the 16^3 stage-1 kernel
+// Kernels: all four GEMM-shaped layers run on the matrix cores -- the three conv stages as dense implicit GEMMs over
+// LDS-resident x slabs with f32 products from 3-way bf16 operand splits (k5_conv1pool_x3, k5_conv2_x3, k5_conv3_x3), Dense(200)
+// and Dense(20) through the 16^3 path's kernels, Dense(200) instantiated for K = 16384 (k_enc_dense1p<16384, MTW>,
+// k_enc_head_mfma: enc_dense32_head_launch, encoder.hip).  Dense scans leave little of the sparsity the 16^3 stage-1 kernel
 // lives on, so nothing is skipped here.  See DESIGN.md section 4.5 for measured times.
 #include <math.h>
 #include <stdlib.h>
 
-#include "caelo_internal.h"
+#include "enc_common.h"
 
 #define VOX_SIZE 0.02
 #define VIS_L 99.84
 #define VIS_W 99.84
 #define VIS_H 14.72
-
-__device__ inline float c5_tanh(float x) {
-    const float e = __builtin_amdgcn_exp2f(x * 2.8853900817779268f);  // exp(2x), same form as enc_tanh (encoder.hip)
-    return 1.0f - 2.0f * __builtin_amdgcn_rcpf(e + 1.0f);
-}
 
 // ---- patches: one workgroup per (key point, scale); the 5x5x5 bricks the window can touch staged in LDS --------
 __global__ void __launch_bounds__(256) k5_patches(const float *__restrict__ pts, int pts_ld, int64_t k_max,
@@ -86,27 +82,16 @@ __global__ void __launch_bounds__(256) k5_patches(const float *__restrict__ pts,
 
 // (Round 1's f32-input MFMA kernels for the three conv layers -- k5_conv1pool, k5_conv_mfma: 1.95 ms per frame against 1.28 ms
 // for the split-operand kernels below, DESIGN.md 4.5 -- are gone from the library: one arithmetic, no environment switch.)
-typedef float c5_f32x4 __attribute__((ext_vector_type(4)));
-// ---- conv3 with f32 products evaluated on the bf16 matrix pipe (3-way operand split) ------------------------------------
-// v_mfma_f32_16x16x32_bf16 retires 16x the FLOPs per cycle of the f32-input MFMA.  An f32 value splits exactly into
-// three bf16 terms, x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid) (both differences
-// are exact in f32; |x - hi - mid - lo| <= 2^-27 |x|), and a product a b is the sum of the six partial products
+// ---- f32 products evaluated on the bf16 matrix pipe (3-way operand split) -----------------------------------------------
+// v_mfma_f32_16x16x32_bf16 retires 16x the FLOPs per cycle of the f32-input MFMA (MI355X_MICROARCH: 2.5 PF vs 157 TF).  An f32
+// value splits exactly into three bf16 terms, x = hi + mid + lo with hi = bf16(x), mid = bf16(x - hi), lo = bf16(x - hi - mid)
+// (both differences are exact in f32; |x - hi - mid - lo| <= 2^-27 |x|), and a product a b is the sum of the six partial products
 // a_hi b_hi + a_hi b_mid + a_mid b_hi + a_mid b_mid + a_hi b_lo + a_lo b_hi up to 2^-27 |a b| -- below the 2^-24
 // rounding of an f32 multiply.  Each partial product of two bf16 is exact in f32 and the MFMA accumulates in f32, so
-// the result is f32-grade at 6/16 of the f32 MFMA's time.
-// Layout: the activations are split ONCE, when the x slab is staged in LDS: per split and channel half h (8 channels)
-// an array [pos][8] bf16, so a lane's ds_read_b128 is one position's 8 channels and 16 lanes read 256 contiguous
-// bytes; an m-tile is 8 z of two x planes, and the plane pitch (104 positions) puts the two 128-byte runs on
-// complementary bank halves.  K = 32 per instruction = two taps x 16 channels: lanes g < 2 carry tap A of the pair,
-// lanes g >= 2 tap B.  Taps are paired so that B - A is one of three constant position offsets (+1 z, +1 y, +1 x);
-// the upper lanes fold that offset into their base address and every other offset is an instruction immediate.
+// the result is f32-grade at 6/16 of the f32 MFMA's time.  (The 16^3 encoder ran this arithmetic in round 2 and has since moved
+// to two f16 terms and three partial products, enc_common.h; this stress case is the 3-way split's one user.)
 typedef __bf16 c5_bf16x8 __attribute__((ext_vector_type(8)));
-#define X3_PLANE 104                 // positions per padded x plane (10 x 10 used)
-#define X3_NPOS (6 * X3_PLANE)       // 4 output planes + 2 halo planes
-#define X3_ARR (X3_NPOS * 16)        // bytes of one (split, half) array
-#define X3_NPAIR 14
-
-__device__ inline uint32_t c5_bf16_rne(float x) {  // bf16(x) as the high half of an f32 bit pattern
+__device__ inline uint32_t c5_bf16_rne(float x) {  // bf16(x), round to nearest even, as the high half of an f32 bit pattern
     const uint32_t u = __float_as_uint(x);
     return (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
 }
@@ -116,10 +101,51 @@ __device__ inline void c5_split3(float x, uint32_t &hi, uint32_t &mid, uint32_t 
     mid = c5_bf16_rne(r);
     lo = c5_bf16_rne(r - __uint_as_float(mid));
 }
-// tap pairs (A, B) with B - A in {+1 z, +1 y, +1 x}; class 3 = no partner (B operand zero)
-__device__ constexpr int c5_pairA(int p) { return p < 9 ? p * 3 : (p < 12 ? (p - 9) * 9 + 2 : (p == 12 ? 8 : 26)); }
-__device__ constexpr int c5_pairClass(int p) { return p < 9 ? 0 : (p < 12 ? 1 : (p == 12 ? 2 : 3)); }
-__device__ constexpr int c5_pairB(int p) { return p < 9 ? p * 3 + 1 : (p < 12 ? (p - 9) * 9 + 5 : (p == 12 ? 17 : -1)); }
+// Eight floats -> their three planes of 8 bf16, a uint4 each (element 0 in the low half of .x): OUT[0] = hi, OUT[1] = mid, OUT[2] = lo.
+// (Macros, not functions: as force-inlined functions the same steps compile to other registers and code sizes in all three kernels.)
+#define C5_PK(A) make_uint4((A[0] >> 16) | A[1], (A[2] >> 16) | A[3], (A[4] >> 16) | A[5], (A[6] >> 16) | A[7])
+// the B operands: VALUE is an expression in i = 0 .. 7
+#define C5_SPLIT3X8(OUT, VALUE)                                                                    \
+    {                                                                                              \
+        uint32_t h_[8], m_[8], l_[8];                                                              \
+        _Pragma("unroll") for (int i = 0; i < 8; ++i) c5_split3((VALUE), h_[i], m_[i], l_[i]);     \
+        (OUT)[0] = C5_PK(h_);                                                                      \
+        (OUT)[1] = C5_PK(m_);                                                                      \
+        (OUT)[2] = C5_PK(l_);                                                                      \
+    }
+// staging: the eight channels at Q of one position, or zeros where !LIVE (the halo), to the three planes' addresses D0, D1, D2 in LDS
+#define C5_STAGE3X8(LIVE, Q, D0, D1, D2)                                                           \
+    {                                                                                              \
+        uint32_t h_[8], m_[8], l_[8];                                                              \
+        if (LIVE) {                                                                                \
+            const float4 *q_ = (const float4 *)(Q);                                                \
+            const float4 v0 = q_[0], v1 = q_[1];                                                   \
+            const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};                   \
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) c5_split3(v[k], h_[k], m_[k], l_[k]);    \
+        } else {                                                                                   \
+            _Pragma("unroll") for (int k = 0; k < 8; ++k) h_[k] = m_[k] = l_[k] = 0u;              \
+        }                                                                                          \
+        *(uint4 *)(D0) = C5_PK(h_);                                                                \
+        *(uint4 *)(D1) = C5_PK(m_);                                                                \
+        *(uint4 *)(D2) = C5_PK(l_);                                                                \
+    }
+// one K = 32 slab of NT m-tiles: the six partial products, smallest terms first; the accumulators alternate so that no MFMA waits
+// for its predecessor.  Reads the A fragments ah / am / al [NT] and the B fragments bh / bm / bl, adds into acc[NT].
+#define C5_MAC(NT, A, B) _Pragma("unroll") for (int j = 0; j < (NT); ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[j], B, acc[j], 0, 0, 0);
+#define C5_MAC6(NT) C5_MAC(NT, al, bh) C5_MAC(NT, ah, bl) C5_MAC(NT, am, bm) C5_MAC(NT, am, bh) C5_MAC(NT, ah, bm) C5_MAC(NT, ah, bh)
+
+// ---- conv3 ----------------------------------------------------------------------------------------------------------------
+// Layout: the activations are split ONCE, when the x slab is staged in LDS: per split and channel half h (8 channels)
+// an array [pos][8] bf16, so a lane's ds_read_b128 is one position's 8 channels and 16 lanes read 256 contiguous
+// bytes; an m-tile is 8 z of two x planes, and the plane pitch (104 positions) puts the two 128-byte runs on
+// complementary bank halves.  K = 32 per instruction = two taps x 16 channels: lanes g < 2 carry tap A of the pair,
+// lanes g >= 2 tap B.  Taps are paired so that B - A is one of three constant position offsets (+1 z, +1 y, +1 x);
+// the upper lanes fold that offset into their base address and every other offset is an instruction immediate
+// (the pairs: enc_pairA / B / Class, enc_common.h).
+#define X3_PLANE 104                 // positions per padded x plane (10 x 10 used)
+#define X3_NPOS (6 * X3_PLANE)       // 4 output planes + 2 halo planes
+#define X3_ARR (X3_NPOS * 16)        // bytes of one (split, half) array
+#define X3_NPAIR 14
 __device__ constexpr int c5_tapPos(int t) { return (t / 9) * X3_PLANE + ((t / 3) % 3) * 10 + (t % 3); }
 
 __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ in, const float *__restrict__ w,
@@ -132,17 +158,8 @@ __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ 
     uint4 bq[X3_NPAIR][3];
 #pragma unroll
     for (int p = 0; p < X3_NPAIR; ++p) {
-        const int tap = g < 2 ? c5_pairA(p) : c5_pairB(p);
-        uint32_t h[8], mi[8], lo[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
-            const float v = tap >= 0 ? w[(size_t)(tap * 16 + 8 * (g & 1) + i) * 32 + nt * 16 + m] : 0.0f;
-            c5_split3(v, h[i], mi[i], lo[i]);
-        }
-#define C5_PK(A) make_uint4((A[0] >> 16) | A[1], (A[2] >> 16) | A[3], (A[4] >> 16) | A[5], (A[6] >> 16) | A[7])
-        bq[p][0] = C5_PK(h);
-        bq[p][1] = C5_PK(mi);
-        bq[p][2] = C5_PK(lo);
+        const int tap = g < 2 ? enc_pairA(p) : enc_pairB(p);
+        C5_SPLIT3X8(bq[p], tap >= 0 ? w[(size_t)(tap * 16 + 8 * (g & 1) + i) * 32 + nt * 16 + m] : 0.0f)
     }
     const float bias = b[nt * 16 + m];
     for (int item = blockIdx.x; item < n_items; item += gridDim.x) {
@@ -154,20 +171,8 @@ __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ 
             const int h = i & 1, pos = i >> 1;
             const int xl = pos / X3_PLANE, rem = pos % X3_PLANE;
             const int x = xb * 4 - 1 + xl, y = rem / 10 - 1, z = rem % 10 - 1;
-            uint32_t hh[8], mm[8], ll[8];
-            if (rem < 100 && x >= 0 && x < 8 && y >= 0 && y < 8 && z >= 0 && z < 8) {
-                const float4 *q = (const float4 *)(src + (((size_t)x * 8 + y) * 8 + z) * 16 + 8 * h);
-                const float4 v0 = q[0], v1 = q[1];
-                const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) c5_split3(v[k], hh[k], mm[k], ll[k]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) hh[k] = mm[k] = ll[k] = 0u;
-            }
-            *(uint4 *)(lds + (0 * 2 + h) * X3_ARR + pos * 16) = C5_PK(hh);
-            *(uint4 *)(lds + (1 * 2 + h) * X3_ARR + pos * 16) = C5_PK(mm);
-            *(uint4 *)(lds + (2 * 2 + h) * X3_ARR + pos * 16) = C5_PK(ll);
+            C5_STAGE3X8(rem < 100 && x >= 0 && x < 8 && y >= 0 && y < 8 && z >= 0 && z < 8, src + (((size_t)x * 8 + y) * 8 + z) * 16 + 8 * h,
+                        lds + (0 * 2 + h) * X3_ARR + pos * 16, lds + (1 * 2 + h) * X3_ARR + pos * 16, lds + (2 * 2 + h) * X3_ARR + pos * 16)
         }
         __syncthreads();
         // m-tile (xpair, y): lane m -> output (x = 2 xpair + (m >> 3), y, z = m & 7); padded corner of its taps
@@ -176,9 +181,9 @@ __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ 
         const unsigned char *ab[4] = {base + (g >= 2 ? 1 * 16 : 0), base + (g >= 2 ? 10 * 16 : 0),
                                       base + (g >= 2 ? X3_PLANE * 16 : 0), base};
         for (int round = 0; round < 4; ++round) {
-            c5_f32x4 acc[2];
+            f32x4 acc[2];
 #pragma unroll
-            for (int j = 0; j < 2; ++j) acc[j] = (c5_f32x4){bias, bias, bias, bias};
+            for (int j = 0; j < 2; ++j) acc[j] = (f32x4){bias, bias, bias, bias};
 #pragma unroll
             for (int p = 0; p < X3_NPAIR; ++p) {
                 const c5_bf16x8 bh = __builtin_bit_cast(c5_bf16x8, bq[p][0]), bm = __builtin_bit_cast(c5_bf16x8, bq[p][1]),
@@ -186,24 +191,12 @@ __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ 
                 c5_bf16x8 ah[2], am[2], al[2];
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
-                    const unsigned char *a = ab[c5_pairClass(p)] + (c5_tapPos(c5_pairA(p)) + (round * 2 + j) * 10) * 16;
+                    const unsigned char *a = ab[enc_pairClass(p)] + (c5_tapPos(enc_pairA(p)) + (round * 2 + j) * 10) * 16;
                     ah[j] = __builtin_bit_cast(c5_bf16x8, *(const uint4 *)(a));
                     am[j] = __builtin_bit_cast(c5_bf16x8, *(const uint4 *)(a + 2 * X3_ARR));
                     al[j] = __builtin_bit_cast(c5_bf16x8, *(const uint4 *)(a + 4 * X3_ARR));
                 }
-                // smallest terms first; the two accumulators alternate so that no MFMA waits for its predecessor
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(al[j], bh, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bl, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bm, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(am[j], bh, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bm, acc[j], 0, 0, 0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ah[j], bh, acc[j], 0, 0, 0);
+                C5_MAC6(2)
             }
             // C row 4 g + r of tile j: output (x = xb*4 + 2 xpair + (row >> 3), y = round*2 + j, z = row & 7)
 #pragma unroll
@@ -212,11 +205,10 @@ __global__ void __launch_bounds__(256, 2) k5_conv3_x3(const float *__restrict__ 
                 for (int r = 0; r < 4; ++r) {
                     const int row = 4 * g + r;
                     const int x = xb * 4 + 2 * xpair + (row >> 3), y = round * 2 + j, z = row & 7;
-                    out[((((size_t)patch * 8 + x) * 8 + y) * 8 + z) * 32 + nt * 16 + m] = c5_tanh(acc[j][r]);
+                    out[((((size_t)patch * 8 + x) * 8 + y) * 8 + z) * 32 + nt * 16 + m] = enc_tanh(acc[j][r]);
                 }
         }
     }
-#undef C5_PK
 }
 
 // ---- conv2 + pool with the same arithmetic: K = 32 = four taps x 8 channels per MFMA ----------------------------------------
@@ -241,13 +233,7 @@ __global__ void __launch_bounds__(256, 2) k5_conv2_x3(const float *__restrict__ 
 #pragma unroll
     for (int q = 0; q < X2_NQ; ++q) {
         const int tap = 4 * q + g;
-        uint32_t h[8], mi[8], lo[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) c5_split3(tap < 27 ? w[(size_t)(tap * 8 + i) * 16 + m] : 0.0f, h[i], mi[i], lo[i]);
-#define C5_PK(A) make_uint4((A[0] >> 16) | A[1], (A[2] >> 16) | A[3], (A[4] >> 16) | A[5], (A[6] >> 16) | A[7])
-        bq[q][0] = C5_PK(h);
-        bq[q][1] = C5_PK(mi);
-        bq[q][2] = C5_PK(lo);
+        C5_SPLIT3X8(bq[q], tap < 27 ? w[(size_t)(tap * 8 + i) * 16 + m] : 0.0f)
         // tap index is lane dependent: spell the position offset out (t / 9, (t / 3) % 3, t % 3 of a runtime t)
         const int t = tap < 27 ? tap : 26;  // the empty slot reads a valid address, its weights are zero
         aoff[q] = ((t / 9) * X2_DP * X2_DP + ((t / 3) % 3) * X2_DP + (t % 3)) * 16;
@@ -260,29 +246,17 @@ __global__ void __launch_bounds__(256, 2) k5_conv2_x3(const float *__restrict__ 
         __syncthreads();
         for (int pos = tid; pos < X2_NPOS; pos += 256) {
             const int x = 2 * px - 1 + pos / (X2_DP * X2_DP), y = (pos / X2_DP) % X2_DP - 1, z = pos % X2_DP - 1;
-            uint32_t hh[8], mm[8], ll[8];
-            if (x >= 0 && x < 16 && y >= 0 && y < 16 && z >= 0 && z < 16) {
-                const float4 *q4 = (const float4 *)(src + (((size_t)x * 16 + y) * 16 + z) * 8);
-                const float4 v0 = q4[0], v1 = q4[1];
-                const float v[8] = {v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w};
-#pragma unroll
-                for (int k = 0; k < 8; ++k) c5_split3(v[k], hh[k], mm[k], ll[k]);
-            } else {
-#pragma unroll
-                for (int k = 0; k < 8; ++k) hh[k] = mm[k] = ll[k] = 0u;
-            }
-            *(uint4 *)(lds + 0 * X2_ARR + pos * 16) = C5_PK(hh);
-            *(uint4 *)(lds + 1 * X2_ARR + pos * 16) = C5_PK(mm);
-            *(uint4 *)(lds + 2 * X2_ARR + pos * 16) = C5_PK(ll);
+            C5_STAGE3X8(x >= 0 && x < 16 && y >= 0 && y < 16 && z >= 0 && z < 16, src + (((size_t)x * 16 + y) * 16 + z) * 8,
+                        lds + 0 * X2_ARR + pos * 16, lds + 1 * X2_ARR + pos * 16, lds + 2 * X2_ARR + pos * 16)
         }
         __syncthreads();
         for (int pi = 0; pi < 2; ++pi) {
             const int py = 2 * wave + pi;
             // tile (xa, yb): output (xa, y = 2 py + yb, z = m); padded corner = position (xa, y, m)
             const unsigned char *base = lds + ((2 * py) * X2_DP + m) * 16;
-            c5_f32x4 acc[4];
+            f32x4 acc[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = (c5_f32x4){bias, bias, bias, bias};
+            for (int j = 0; j < 4; ++j) acc[j] = (f32x4){bias, bias, bias, bias};
 #pragma unroll
             for (int q = 0; q < X2_NQ; ++q) {
                 const c5_bf16x8 bh = __builtin_bit_cast(c5_bf16x8, bq[q][0]), bm = __builtin_bit_cast(c5_bf16x8, bq[q][1]),
@@ -296,13 +270,7 @@ __global__ void __launch_bounds__(256, 2) k5_conv2_x3(const float *__restrict__ 
                     am[j] = __builtin_bit_cast(c5_bf16x8, *(const uint4 *)(a + o + X2_ARR));
                     al[j] = __builtin_bit_cast(c5_bf16x8, *(const uint4 *)(a + o + 2 * X2_ARR));
                 }
-#define X2_MAC(A, B) _Pragma("unroll") for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[j], B, acc[j], 0, 0, 0);
-                X2_MAC(al, bh)
-                X2_MAC(ah, bl)
-                X2_MAC(am, bm)
-                X2_MAC(am, bh)
-                X2_MAC(ah, bm)
-                X2_MAC(ah, bh)
+                C5_MAC6(4)
             }
             // C rows 4 g + r = z; pooled z = 2 g + zp
             float *dst = out + ((((size_t)patch * 8 + px) * 8 + py) * 8 + 2 * g) * 16 + m;
@@ -310,16 +278,14 @@ __global__ void __launch_bounds__(256, 2) k5_conv2_x3(const float *__restrict__ 
             for (int zp = 0; zp < 2; ++zp) {
                 float v = fmaxf(fmaxf(acc[0][2 * zp], acc[0][2 * zp + 1]), fmaxf(acc[1][2 * zp], acc[1][2 * zp + 1]));
                 v = fmaxf(v, fmaxf(fmaxf(acc[2][2 * zp], acc[2][2 * zp + 1]), fmaxf(acc[3][2 * zp], acc[3][2 * zp + 1])));
-                dst[zp * 16] = c5_tanh(v);
+                dst[zp * 16] = enc_tanh(v);
             }
         }
     }
-#undef C5_PK
-#undef X2_MAC
 }
 
 // ---- conv1 + pool on the bf16 pipe: the input is binary, so only the weights need the 3-way split ------------------------
-// Same GEMM view as k5_conv1pool (n = (z parity, channel), m = the 16 even z of a row, k = the 3 x 3 x 4 tap window), with
+// The GEMM view: n = (z parity, channel), m = the 16 even z of a row, k = the 3 x 3 x 4 tap window, with
 // the voxels stored as bf16 0 / 1 (exact): a product is A (B_hi + B_mid + B_lo), three MFMAs per k slab.  The window's
 // 36 k go into two K = 32 slabs: lane group g carries window rows 2g and 2g + 1 (4 consecutive z each = two dwords of
 // the voxel row), the ninth row sits alone in the second slab.  6 x 16 cycles per 32-voxel row instead of 9 x 32.
@@ -335,18 +301,11 @@ __global__ void __launch_bounds__(256) k5_conv1pool_x3(const unsigned long long 
     uint4 bq[2][3];
 #pragma unroll
     for (int sl = 0; sl < 2; ++sl) {
-        uint32_t h[8], mi[8], lo[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) {
+        C5_SPLIT3X8(bq[sl], ({
             const int r = sl == 0 ? 2 * g + (i >> 2) : (g == 0 && i < 4 ? 8 : -1);
             const int kc = (i & 3) - dz;
-            c5_split3(r >= 0 && kc >= 0 && kc < 3 ? w1[(r * 3 + kc) * 8 + ch] : 0.0f, h[i], mi[i], lo[i]);
-        }
-#define C5_PK(A) make_uint4((A[0] >> 16) | A[1], (A[2] >> 16) | A[3], (A[4] >> 16) | A[5], (A[6] >> 16) | A[7])
-        bq[sl][0] = C5_PK(h);
-        bq[sl][1] = C5_PK(mi);
-        bq[sl][2] = C5_PK(lo);
-#undef C5_PK
+            r >= 0 && kc >= 0 && kc < 3 ? w1[(r * 3 + kc) * 8 + ch] : 0.0f;
+        }))
     }
     // element offsets (bf16 units) of this lane's two window rows in slab 0; slab 1 reads row 8 everywhere
     const int r0 = 2 * g, r1 = 2 * g + 1;
@@ -377,9 +336,9 @@ __global__ void __launch_bounds__(256) k5_conv1pool_x3(const unsigned long long 
             const int py = 4 * wave + pi;
             // tile (xa, yb): output (xa, y = 2 py + yb, z = 2 m + dz) reads padded (xa + ka, y + kb, 2 m + kc')
             const unsigned short *base = &vox[(2 * py) * C1X_PITCH + 2 * m];
-            c5_f32x4 acc[4];
+            f32x4 acc[4];
 #pragma unroll
-            for (int j = 0; j < 4; ++j) acc[j] = (c5_f32x4){bias, bias, bias, bias};
+            for (int j = 0; j < 4; ++j) acc[j] = (f32x4){bias, bias, bias, bias};
             c5_bf16x8 a0[4], a1[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {  // j = 2 xa + yb
@@ -403,7 +362,7 @@ __global__ void __launch_bounds__(256) k5_conv1pool_x3(const unsigned long long 
             for (int r = 0; r < 4; ++r) {
                 float v = fmaxf(fmaxf(acc[0][r], acc[1][r]), fmaxf(acc[2][r], acc[3][r]));
                 v = fmaxf(v, __shfl_xor(v, 8));
-                if (dz == (r >> 1)) dst[r * 8] = c5_tanh(v);
+                if (dz == (r >> 1)) dst[r * 8] = enc_tanh(v);
             }
         }
     }
@@ -491,13 +450,13 @@ CAELO_API int caelo_encode32(caelo_ctx *c, const uint64_t *bits, int64_t n_patch
 CAELO_API int caelo_encode32_profile(caelo_ctx *c, const uint64_t *bits, int64_t n_patches, int group, float *out, int out_stride,
                                      void *ws, void *stream, float *ms_host) {
     CAELO_REQUIRE(ms_host != nullptr, "null argument");
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; ++i) CAELO_HIP(hipEventCreate(&ev[i]));
+    enc_prof_events pe;
+    CAELO_HIP(pe.create());
+    hipEvent_t *ev = pe.ev;
     int rc = encode32_impl(c, bits, n_patches, group, out, out_stride, ws, stream, ev);
     if (rc == CAELO_OK) {
         CAELO_HIP(hipEventSynchronize(ev[4]));
         for (int i = 0; i < 4; ++i) CAELO_HIP(hipEventElapsedTime(&ms_host[i], ev[i], ev[i + 1]));
     }
-    for (int i = 0; i < 5; ++i) (void)hipEventDestroy(ev[i]);
     return rc;
 }

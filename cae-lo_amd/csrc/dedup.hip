@@ -7,7 +7,7 @@
 // plus one or two neighbours in a handful of arrangements: a 64-beam frame has ~1.9 k distinct patches among its
 // 3072 (283 / 950 / 622 at the three scales).  Equal bits => equal descriptor, bit for bit (the encoder kernels do
 // not depend on a patch's position in the launch: tests/test_gpu_parity.py), so the encoder runs once per distinct
-// patch and k_enc_head hands the result to every key point that owns a copy.
+// patch and k_enc_head_mfma hands the result to every key point that owns a copy.
 //
 // Exactness: patches are grouped by a 40-bit hash (computed and entered into the table by k_patches, which has the
 // words in registers), then every patch is compared word by word with the
@@ -82,7 +82,7 @@ __global__ void __launch_bounds__(1024) k_dd_scan(const caelo_frame_set fs, int 
             ++pos;
         } else {
             // a copy: -(representative + 1), the representative being (frame * 3072 + patch) of any frame of the set; the one
-            // reader (k_enc_head) follows it to that patch's own row -- a second lookup for the copies instead of a kernel
+            // reader (k_enc_head_mfma) follows it to that patch's own row -- a second lookup for the copies instead of a kernel
             // (k_dd_link, 5 us on the front stream's serial chain) that resolved it for them
             T->slot_of[p[j]] = -(S->rep[p[j]] + 1);
         }

@@ -45,13 +45,7 @@ typedef _Float16 enc_h8 __attribute__((ext_vector_type(8)));
 #define S1X_RP 20
 #define S1X_W1F_U4 (16 * 64)   // conv1 B operand: [k-step 2][n-tile 4][term 2][lane 64] uint4
 #define S1X_W2X_U4 (18 * 64)   // conv2 B operand: [tap row 9][X, Y][lane 64] uint4
-
-__host__ __device__ inline uint16_t enc_f16_bits(float x) { return __builtin_bit_cast(uint16_t, (_Float16)x); }
-__host__ __device__ inline float enc_f16_val(uint16_t b) { return (float)__builtin_bit_cast(_Float16, b); }
-__host__ __device__ inline void enc_split2h(float x, uint16_t &hi, uint16_t &lo) {
-    hi = enc_f16_bits(x);
-    lo = enc_f16_bits(x - enc_f16_val(hi));
-}
+#define S1X_BGO_OFF (512 * 16 + 16)   // floats of the C0 table in front of k_enc_bgo_table's [16 pairs][64 lanes] float2
 
 // conv2 A fragment f, k group g -> z tap and term (0 = d_hi, 1 = d_lo); B fragment b (0 = X, 1 = Y), group g -> z tap and weight term
 __host__ __device__ constexpr int s1x_tap(int f, int g) { return f < 2 ? (g == 3 ? 0 : g) : 1 + (g & 1); }
@@ -78,8 +72,8 @@ static void stage1x_split_weights(const float *w1, const float *w2, uint4 *w1f, 
                     enc_split2h(in ? w1[((ka * 3 + kb) * 3 + kc) * 8 + ch] : 0.0f, h[i], l[i]);
                 }
                 uint4 *o = w1f + (size_t)((ks * 4 + nt) * 2) * 64 + lane;
-                o[0] = make_uint4(h[0] | (uint32_t)h[1] << 16, h[2] | (uint32_t)h[3] << 16, h[4] | (uint32_t)h[5] << 16, h[6] | (uint32_t)h[7] << 16);
-                o[64] = make_uint4(l[0] | (uint32_t)l[1] << 16, l[2] | (uint32_t)l[3] << 16, l[4] | (uint32_t)l[5] << 16, l[6] | (uint32_t)l[7] << 16);
+                o[0] = enc_pack_h8(h);
+                o[64] = enc_pack_h8(l);
             }
     // conv2: B fragment b of tap row (ka, kb), lane (g, n): group g carries the 8 input channels of (z tap, weight term) = s1x_btap /
     // s1x_bterm [b][g] for output channel n
@@ -94,8 +88,7 @@ static void stage1x_split_weights(const float *w1, const float *w2, uint4 *w1f, 
                     enc_split2h(w2[(tap * 8 + i) * 16 + n], h, l);
                     v[i] = s1x_bterm(b, g) ? l : h;
                 }
-                w2x[(size_t)(row * 2 + b) * 64 + lane] = make_uint4(v[0] | (uint32_t)v[1] << 16, v[2] | (uint32_t)v[3] << 16,
-                                                                    v[4] | (uint32_t)v[5] << 16, v[6] | (uint32_t)v[7] << 16);
+                w2x[(size_t)(row * 2 + b) * 64 + lane] = enc_pack_h8(v);
             }
 }
 

@@ -1569,7 +1569,7 @@ LAYER_BUDGET = {"P2": 1.5e-6, "F3": 2.5e-6, "hidden": 4.0e-6, "descriptors": 5.0
 @pytest.mark.gpu
 def test_encoder_layer_error_budget(engine, models):
     """the element-wise descriptor error (1.4e-5 relative at the 0.1 floor in round 2) has a budget per
-    layer -- 5-instruction tanh, f16 x 2 conv1 / conv2, bf16 x 3 conv3 / Dense(200) -- so that headroom cannot erode unnoticed."""
+    layer -- 5-instruction tanh, f16 x 2 conv1 / conv2 (four partial products), f16 x 2 conv3 / Dense(200) (three) -- so that headroom cannot erode unnoticed."""
     import torch
     bits = np.ascontiguousarray(np.load(os.path.join(GOLDEN, "frame_q0.npz"))["patch_bits"].reshape(-1, 64))
     enc_m = models[1]
